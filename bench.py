@@ -1,10 +1,12 @@
 #!/usr/bin/env python3
 """bench.py - images/sec of forward + GaussTaylor decode, ResNet50-DConv 256x192, bs=128 per GPU, fp32.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--arch dconv|duc] [--no-cpu-baseline]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--batch 128] [--arch dconv|duc] [--dump-outputs DIR] [--full] [--no-cpu-baseline]
 
 One "step" = one pass of the hot path (network forward + key-point decode) over one batch of synthetic images that
-are already resident in HBM.  N > 1: one process per GPU - either started by `python -m torch.distributed.run` (RANK /
+are already resident in HBM.  A plain run sets up, warms up, times the K steps and prints the line; everything else the benchmark
+measures or checks (the other BASELINE configs, the CPU baseline, the one-batch-in-flight rerun, per-kernel HIP events, the train
+step's phase split, the extra N > 1 jobs, the RCCL census) runs only with --full.  N > 1: one process per GPU - either started by `python -m torch.distributed.run` (RANK /
 LOCAL_RANK / WORLD_SIZE / MASTER_* in the environment) or, when invoked plainly as `python bench.py --gpus N`, by this
 file itself: the parent starts N fresh child interpreters BEFORE importing torch or touching the GPU and forwards rank
 0's line.  The path shards by image (independent replicas, no data-path collective) -> weak scaling; barrier + device
@@ -38,6 +40,13 @@ def parse():
                     help="dconv / duc only: another factory of the reference's nets.pose_resnet_* (resnet18 ... resnet152, wide_resnet50_2, resnext50_32x4d, "
                          "resnext101_32x8d; nets/pose_resnet_dconv.py:282-368).  Not a BASELINE config: no tracked tile table (tuned on this GPU, untimed setup), "
                          "no cpu_baseline; the line's metric names the backbone")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline figure: the other BASELINE configs (default command), the "
+                         "CPU baseline, the one-batch-in-flight rerun, per-kernel HIP events (roofline), the train step's phase split, the "
+                         "self-check and train jobs at N > 1 and the RCCL census.  Off: set up, warm up, time the steps, print the line")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32): keypoints.npy and "
+                         "scores.npy (infer), loss.npy (train); rank 0 only.  Inputs and weights are seeded, so two builds can be compared")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--dist-backend", default="nccl", choices=["nccl", "gloo"],
                     help="nccl (= RCCL over xGMI, default); gloo only to exercise the N > 1 code path on a single-GPU box")
@@ -62,7 +71,7 @@ def parse():
                     "table of this (arch, dtype) under profiles/ when the batch is 128 (the table the committed rocprofv3 summaries were taken with)")
     ap.add_argument("--no-train-autotune", action="store_true", help="train mode: keep the built-in tile heuristic")
     ap.add_argument("--retune", action="store_true", help="ignore the tracked tile table: time every (tile, kernel) per layer shape on this GPU")
-    ap.add_argument("--layers-out", default=None, help="write the per-layer timing table (JSON) here")
+    ap.add_argument("--layers-out", default=None, help="write the per-layer timing table (JSON) here (runs the per-kernel HIP-event pass, with or without --full)")
     ap.add_argument("--no-kernel-events", action="store_true", help="skip the per-launch HIP events (roofline object)")
     ap.add_argument("--fuse-bottlenecks", action="store_true", help="(default since round 3; kept so that older command lines still parse)")
     ap.add_argument("--pipeline-decode", action="store_true", help="infer mode: decode of step i on its own stream while the forward of step i + 1 runs "
@@ -89,7 +98,7 @@ def parse():
                          "check the rank -> device mapping, one barrier and the MAX/SUM reductions of the measurement, print ONE JSON line; "
                          "non-zero exit when any rank dies")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="default run (N = 1, infer, dconv f32 bs=128) only: skip the other BASELINE configs that are otherwise timed after the "
+                    help="--full default run (N = 1, infer, dconv f32 bs=128) only: skip the other BASELINE configs that are otherwise timed after the "
                          "headline with the same --steps / --warmup and appended as `other_configs` (DUC bf16 bs=128, HRNet-W32 bf16 bs=128, the "
                          "32-image bf16 train step)")
     ap.add_argument("--self-check-only", action="store_true",
@@ -97,15 +106,18 @@ def parse():
                          "RCCL path and through torch.distributed, compared bit for bit), every rank prints the agreed verdict as one JSON line; a "
                          "rank that cannot complete it exits 13.  Started by the supervisor (launch.run_job) under a deadline, never inside a training process")
     ap.add_argument("--no-extra-jobs", action="store_true",
-                    help="N > 1, the driver's command (infer, dconv f32 bs=128): skip the two extra N-rank jobs that otherwise follow the headline "
+                    help="N > 1 with --full, the driver's command (infer, dconv f32 bs=128): skip the two extra N-rank jobs that otherwise follow the headline "
                          "job - the collective self-check and the bf16 32-image-per-GPU train step (BASELINE config 4), appended as `other_configs`")
-    ap.add_argument("--by-kernel", action="store_true", help="keep the per-instantiation table (`roofline.by_kernel`) in the JSON line")
+    ap.add_argument("--by-kernel", action="store_true", help="keep the per-instantiation table (`roofline.by_kernel`) in the JSON line (--full or --layers-out)")
     ap.add_argument("--native-comm", action="store_true", help="train mode, N > 1: the step's collectives through our own RCCL communicators on the "
                     "step's streams (sp_comm_*) instead of torch.distributed; opt-in until it has run on a multi-GPU box")
     ap.add_argument("--hsa-ipc-legacy", default="0", choices=["0", "1", "inherit"],
                     help="HSA_ENABLE_IPC_MODE_LEGACY for the ranks (recorded in config): 0 = dmabuf IPC, what this pool's host driver supports "
                          "(RCCL / tensor sharing across processes fails with hipIpcGetMemHandle otherwise); inherit = leave the environment alone")
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.dump_outputs and (args.mode == "micro" or args.dry_launch):
+        ap.error("--dump-outputs writes what an infer or train step computed: not with --mode micro or --dry-launch")
+    return args
 
 
 def apply_ipc_mode(args, env) -> str:
@@ -270,10 +282,10 @@ TRAIN_JOB_CONFIG = "ResNet50-DConv 256x192 bf16 train step (fwd+bwd+Adam), batch
 
 
 def wants_extra_jobs(args) -> bool:
-    """N > 1 and the command the driver runs (the headline config, nothing overridden): the supervisor then also runs the collective
+    """N > 1, --full and the command the driver runs (the headline config, nothing overridden): the supervisor then also runs the collective
     self-check job and the N-rank train-step job, so that the first multi-GPU run measures BASELINE config 4 and proves (or safely
     rejects) the RCCL path."""
-    return (args.gpus > 1 and args.mode == "infer" and args.arch == "dconv" and args.backbone == "resnet50" and args.dtype == "f32" and args.batch == 128 and
+    return (args.gpus > 1 and args.full and args.mode == "infer" and args.arch == "dconv" and args.backbone == "resnet50" and args.dtype == "f32" and args.batch == 128 and
             not args.graph and not args.no_extra_jobs and not args.no_other_configs and not args.self_check_only)
 
 
@@ -357,7 +369,7 @@ def supervise(args, managed, world: int) -> int:
     if rc == 0 and wants_extra_jobs(args):
         dec = agreed(run("self_check", check_argv, _deadline("CHECK", 300.0)))
         train_argv = ["--gpus", str(world), "--mode", "train", "--dtype", "bf16", "--batch", "32", "--steps", str(args.steps), "--warmup", str(args.warmup),
-                      "--no-cpu-baseline", "--no-other-configs"] + common
+                      "--full", "--no-cpu-baseline", "--no-other-configs"] + common
         tjob = run("train", train_argv, _deadline("TRAIN", 420.0),
                    {"SP_NATIVE_COMM": "1" if dec["native"] else "0", "SP_COLLECTIVE_DECISION": json.dumps(dec)})
         rec = {"config": TRAIN_JOB_CONFIG.format(n=world), "n_gpus": world, "command": "python3 bench.py " + " ".join(train_argv),
@@ -504,7 +516,7 @@ def main():
     if others is not None and line is not None:
         line["other_configs"] = others                    # LAST key of the one JSON line
     abandoned = False
-    if dist.is_initialized() and dist.get_backend() == "nccl":
+    if args.full and dist.is_initialized() and dist.get_backend() == "nccl":
         # N > 1 over RCCL (or the 1-rank preflight group): ask RCCL itself who is in the job - AFTER the measurement, on a helper thread
         # with a deadline: a census that never answers must not cost the line (the process then leaves without tearing the group down)
         import threading
@@ -558,8 +570,8 @@ OTHER_CONFIGS = [
 
 
 def is_default_command(args) -> bool:
-    """The command the driver runs: N = 1, the headline config, nothing overridden."""
-    return (args.gpus == 1 and os.environ.get("WORLD_SIZE", "1") == "1" and args.mode == "infer" and args.arch == "dconv" and args.dtype == "f32" and
+    """The command the driver runs with --full: N = 1, the headline config, nothing overridden."""
+    return (args.full and args.gpus == 1 and os.environ.get("WORLD_SIZE", "1") == "1" and args.mode == "infer" and args.arch == "dconv" and args.dtype == "f32" and
             args.batch == 128 and not args.graph and args.tiles is None and not args.retune and args.interleave is None and
             not args.no_other_configs and not args.dry_launch and args.backbone == "resnet50")
 
@@ -575,7 +587,7 @@ def measure_other_configs(args):
     out = []
     for oc in OTHER_CONFIGS:
         cmd = [sys.executable, os.path.abspath(__file__)] + oc["argv"] + ["--steps", str(args.steps), "--warmup", str(args.warmup),
-                                                                        "--no-cpu-baseline", "--no-other-configs"]
+                                                                        "--full", "--no-cpu-baseline", "--no-other-configs"]
         t0 = time.perf_counter()
         try:
             r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, text=True, timeout=240)
@@ -767,11 +779,16 @@ def run_once(args, ctx):
     assert os.environ.get("SP_CONV_DEBUG") or torch.isfinite(out[0]).all()
 
     ms_per_step = 1e3 * elapsed / args.steps
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, ("loss",) if args.mode == "train" else ("keypoints", "scores"), out)
 
-    # ---- the same steps with ONE batch in flight on one stream (rank 0, untimed extra: the mode of rounds 1-2 and of the per-kernel events,
-    #      kept in every line so that rounds stay comparable whatever the default number of batches in flight becomes) ----
+    # per-kernel HIP events take untimed passes of their own: with --full, or when --layers-out asks for the per-layer table
+    kernel_events = (args.full or args.layers_out is not None) and not args.no_kernel_events
+
+    # ---- --full: the same steps with ONE batch in flight on one stream (rank 0, untimed extra: the mode of rounds 1-2 and of the per-kernel
+    #      events, kept in every full line so that rounds stay comparable whatever the default number of batches in flight becomes) ----
     one_in_flight = None
-    if prog is not None and not args.graph and (args.interleave or 1) > 1:
+    if args.full and prog is not None and not args.graph and (args.interleave or 1) > 1:
         keep_ms = prog.multi_stream
         prog.multi_stream = False
         hm1 = torch.empty((B,) + tuple(prog.out_shape), dtype=torch.float32, device=dev)
@@ -790,7 +807,7 @@ def run_once(args, ctx):
 
     # ---- per-kernel roofline: HIP events around every conv launch, on the launch stream, same inputs ----
     roofline = None
-    if rank == 0 and not args.no_kernel_events and prog is not None:
+    if rank == 0 and kernel_events and prog is not None:
         roofline = kernel_roofline(prog, x, steps=max(3, min(args.steps, 10)), layers_out=args.layers_out,
                                    peak=FP32_MATRIX_PEAK_TFLOPS if args.dtype == "f32" else BF16_MATRIX_PEAK_TFLOPS,
                                    arch=args.arch, dtype=args.dtype)
@@ -801,20 +818,21 @@ def run_once(args, ctx):
             roofline.pop("by_kernel", None)                   # (kept in --layers-out / --by-kernel; profiles/*_kernel_stats.csv has the same table)
 
     step_split = None
-    if args.mode == "train":                                  # untimed extra steps with phase events (every rank: collectives inside)
+    if args.mode == "train" and (args.full or kernel_events):     # untimed extra steps with phase events (every rank: collectives inside)
         if graphed_step is not None:                          # (timing events cannot live inside a graph: these steps run eagerly)
             graphed_step.release()
             step = eager_step
-        trainer.profile = True
-        acc = {}
-        with torch.no_grad():
-            for _ in range(5):
-                step()
-                for k, v in trainer.phase_ms().items():
-                    acc[k] = acc.get(k, 0.0) + v / 5
-        trainer.profile = False
-        step_split = {k: round(v, 3) for k, v in acc.items()}
-        if not args.no_kernel_events:      # every rank runs the extra steps (collectives inside); rank 0 reports its own events
+        if args.full:
+            trainer.profile = True
+            acc = {}
+            with torch.no_grad():
+                for _ in range(5):
+                    step()
+                    for k, v in trainer.phase_ms().items():
+                        acc[k] = acc.get(k, 0.0) + v / 5
+            trainer.profile = False
+            step_split = {k: round(v, 3) for k, v in acc.items()}
+        if kernel_events:                  # every rank runs the extra steps (collectives inside); rank 0 reports its own events
             roofline = train_roofline(trainer, step, B, FP32_MATRIX_PEAK_TFLOPS if args.dtype == "f32" else BF16_MATRIX_PEAK_TFLOPS,
                                       layers_out=args.layers_out)
     if rank == 0:
@@ -863,7 +881,7 @@ def run_once(args, ctx):
                 "roofline": roofline,
                 "one_batch_in_flight": one_in_flight,
                 "host_enqueue_ms_per_step": round(host_enqueue_ms, 3),
-                "cpu_baseline": None if (args.no_cpu_baseline or world > 1 or args.backbone != "resnet50") else cpu_baseline(args.arch),   # rank 0 at N = 1 only
+                "cpu_baseline": None if (not args.full or args.no_cpu_baseline or world > 1 or args.backbone != "resnet50") else cpu_baseline(args.arch),   # rank 0 at N = 1 only
             }
     else:
         line = None
@@ -879,6 +897,17 @@ def run_once(args, ctx):
     torch.cuda.synchronize()
     torch.cuda.empty_cache()
     return line
+
+
+def dump_outputs(out_dir: str, names, tensors) -> None:
+    """--dump-outputs: the arrays one call of the timed step hands its caller, as float32 DIR/<name>.npy (26 KB at bs=128)."""
+    import numpy as np
+
+    if len(names) != len(tensors):
+        raise RuntimeError(f"--dump-outputs: the step returned {len(tensors)} arrays, expected {len(names)} ({', '.join(names)})")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, t in zip(names, tensors):
+        np.save(os.path.join(out_dir, name + ".npy"), t.detach().float().cpu().numpy())
 
 
 def rccl_census(dev, rank: int, world: int):

@@ -2082,7 +2082,7 @@ def test_bench_self_launches_two_ranks(mode):
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT")}
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--batch", "8",
-           "--dist-backend", backend, "--no-cpu-baseline", "--mode", mode]   # (kernel events on: the roofline passes run on every rank)
+           "--dist-backend", backend, "--full", "--no-cpu-baseline", "--mode", mode]   # (kernel events on: the roofline passes run on every rank)
     if mode == "train":
         cmd += ["--dtype", "bf16"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900)
@@ -2123,7 +2123,7 @@ def test_bench_two_ranks_driver_command_runs_the_three_jobs(launcher):
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "SP_NATIVE_COMM", "SP_BENCH_CHILD")}
     backend = "nccl" if torch.cuda.device_count() >= 2 else "gloo"
-    cmd = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--dist-backend", backend, "--no-kernel-events"]
+    cmd = [os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "2", "--dist-backend", backend, "--full", "--no-kernel-events"]
     if launcher == "torchrun":
         from simple_pose_amd.launch import free_port
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",

@@ -364,7 +364,7 @@ def _dry_three_jobs(n, hook, torchrun=False, deadline="25"):
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_PORT", "SP_BENCH_DRY_FAIL_RANK", "SP_NATIVE_COMM", "SP_BENCH_CHILD"):
         env.pop(k, None)
     env.update(SP_BENCH_TEST_SELF_CHECK=hook, SP_BENCH_CHECK_DEADLINE_S=deadline)
-    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-launch", "--steps", "3", "--warmup", "1"]
+    tail = [os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--dry-launch", "--full", "--steps", "3", "--warmup", "1"]
     if torchrun:
         from simple_pose_amd.launch import free_port
         cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(n), "--master-addr", "127.0.0.1",
