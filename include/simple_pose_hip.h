@@ -27,7 +27,7 @@ extern "C" {
 #define SP_EINVAL (-1)   /* bad argument / unsupported shape (message in sp_last_error) */
 #define SP_ELAUNCH (-2)  /* HIP launch or runtime failure */
 
-#define SP_ABI_VERSION 35
+#define SP_ABI_VERSION 36
 
 /* epilogue / layout flags of sp_conv_desc.flags */
 #define SP_CONV_RELU 0x1u          /* y = max(y, 0) after scale/shift (+ residual) */
@@ -274,6 +274,13 @@ int sp_u8hwc_bgr_to_nchw_f32(const unsigned char* img, float* out, int batch, in
  * fixed-point bilinear arithmetic restated (not pinned against cv2: it is absent from the build image) - naive_data.py:50 */
 int sp_warp_affine_u8c3(const unsigned char* src, int src_h, int src_w, const double* m_fwd, int crops, unsigned char* dst, int out_h,
                         int out_w, void* stream);
+/* training batches (commons/transforms.py RefineSimpleTransform.__call__ + datasets/coco.py collate_fn): sample n is
+ * cv.warpAffine(flip[n] ? np.fliplr(src[n]) : src[n], m_fwd[n], (out_w, out_h), flags=INTER_LINEAR) - the pixels of sp_warp_affine_u8c3,
+ * the flip mirrored at read time - normalised as sp_u8hwc_bgr_to_nchw_f32 does into out fp32 [batch,3,out_h,out_w] RGB.  srcs[n] (device
+ * pointers to uint8 [H,W,3] BGR), src_hw [batch,2] (H, W each <= 32767), flip [batch] (NULL: no flip), m_fwd [batch,2,3] and mean_rgb are
+ * HOST arrays; out and crops are device memory; crops (uint8 [batch,out_h,out_w,3] BGR, what sp_warp_affine_u8c3 writes) may be NULL. */
+int sp_warp_affine_batch_u8c3_to_nchw_f32(const unsigned char* const* srcs, const int* src_hw, const int* flip, const double* m_fwd, int batch,
+                                          int out_h, int out_w, const float* mean_rgb_host, float* out, unsigned char* crops, void* stream);
 
 /* ---- after decode: result scores and per-image OKS-NMS -----------------------------------
  * kps_to_dict_ (metrics/pose_metrics.py:172-179): score[b] = mean_j(max_val[b,j]) + max_j(max_val[b,j]) */

@@ -21,7 +21,7 @@ SP_CONV_BF16 = 0x8
 SP_CONV_OUT_F32 = 0x10
 SP_CONV_BN_Y_MASK = 0x20
 CONV_TILES = ((128, 128), (64, 128), (128, 64), (64, 64), (256, 64), (128, 32))
-ABI_VERSION = 35
+ABI_VERSION = 36
 SP_CONV_KERNEL_IGEMM, SP_CONV_KERNEL_RING, SP_CONV_KERNEL_PW, SP_CONV_KERNEL_RING_LW, SP_CONV_KERNEL_RING_LW4 = 0, 1, 2, 3, 4
 RING_LW4_TILES = ((192, 128), (128, 128), (96, 128), (256, 128), (128, 256), (96, 256), (64, 128))   # kernel = SP_CONV_KERNEL_RING_LW4 (four MFMA waves + four loader waves)
 RING_LW_TILES = ((256, 128), (128, 256), (256, 64), (128, 128), (192, 128))   # kernel = SP_CONV_KERNEL_RING_LW (bf16; the ring with loader waves)
@@ -120,6 +120,7 @@ SYMBOLS = {
     "sp_maxpool3x3s2_bwd_idx_nhwc": (c_int, [_P, _P, c_int, _P, c_int, c_int, c_int, c_int, _P]),
     "sp_nchw_to_nhwc_pad": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, _P]),
     "sp_warp_affine_u8c3": (c_int, [_P, c_int, c_int, _P, c_int, _P, c_int, c_int, _P]),
+    "sp_warp_affine_batch_u8c3_to_nchw_f32": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(c_float), _P, _P, _P]),
     "sp_conv2d_bn_stats_rows": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int)]),
     "sp_conv2d_fwd_bn_stats": (c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, c_int, _P]),
     "sp_conv2d_fwd_bn_stats_abn": (c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, _P]),
