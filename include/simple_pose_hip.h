@@ -39,6 +39,13 @@ extern "C" {
                                     * ReLU bit mask sp_bn_fold_apply_nhwc / sp_bn_apply_nhwc left (one byte per 8 channels), not the tensor y */
 #define SP_CONV_BF16 0x8u          /* x, w_packed, residual and NHWC y are bf16 (fp32 accumulate; scale/shift and the NCHW
                                       output stay fp32); c_in % 8 == 0, k_pad % 64 == 0 */
+#define SP_CONV_HARDSWISH 0x40u    /* y = h(acc * scale + shift) (+ residual, added AFTER h: the YOLOv5 BottleNeck shortcut), h(v) = v * min(max(v + 3, 0), 6) / 6
+                                    * in torch's operation order (nn.Hardswish).  fp32 implicit-GEMM launches only (kernel 0, no SP_CONV_RELU, NHWC output);
+                                    * every other kernel structure and every *_ok predicate refuses it */
+#define SP_CONV_OUT_SLICE 0x80u    /* y is the channel slice [c0, c0 + c_out) of an NHWC tensor with out_c channels per pixel; the caller passes y already
+                                    * offset by c0 elements (c0 % 4 == 0: 16-byte aligned).  out_c % 4 == 0, c_out % 4 == 0, c_out <= out_c, no residual.
+                                    * fp32 implicit-GEMM launches only.  (Without the flag out_c must equal c_out, as before.)  Producers of a concat
+                                    * write their slices of one buffer - torch.cat without a copy */
 
 /*
  * One launch of the fp32 implicit-GEMM convolution family:
@@ -612,6 +619,50 @@ int sp_pack_deconv_k4s2p1(const float* w, int c_in, int c_out, int n_pad, void* 
  * pixel_shuffle: outputs in the packed row order of sp_pack_conv_weights */
 int sp_fold_bn(const float* weight, const float* bias, const float* running_mean, const float* running_var, int c, float eps,
                int pixel_shuffle, float* scale, float* shift, void* stream);
+
+/* ---- person detector: detector/yolov5_detector.py + detector/nets/yolov5.py (csrc/detect.hip; fp32 throughout) ------------------------
+ * ScalePadding.make_border (yolov5_detector.py:145) + the input glue of single_predict (:223-226) + Focus (commons.py:51) in one launch.
+ * src: uint8 BGR [B, src_h, src_w, 3]; the image is resized to new_h x new_w (OpenCV INTER_LINEAR on 8-bit data restated: 11-bit
+ * fixed-point coefficients, an exact 2x downscale in both axes takes INTER_AREA's 2x2 mean; new == src copies), placed at (top, left) of an
+ * out_h x out_w canvas of 114.  mode SP_LETTERBOX_FOCUS: out = fp32 NHWC [B, out_h/2, out_w/2, 12], channel 3*g + c = RGB channel c / 255 of
+ * canvas pixel (2*fy + dy_g, 2*fx + dx_g), (dy, dx)_g = (0,0), (1,0), (0,1), (1,1) (torch.cat order of Focus.forward); out_h, out_w even.
+ * mode SP_LETTERBOX_U8: out = the uint8 BGR canvas [B, out_h, out_w, 3] (what make_border returns). */
+#define SP_LETTERBOX_FOCUS 0
+#define SP_LETTERBOX_U8 1
+int sp_yolo_letterbox(const unsigned char* src, int batch, int src_h, int src_w, int new_h, int new_w, int top, int left, int out_h, int out_w,
+                      int mode, void* out, void* stream);
+/* Focus on an fp32 NCHW RGB image [B, 3, h, w] (YOLOv5.forward on a prepared tensor) -> fp32 NHWC [B, h/2, w/2, 12] as above */
+int sp_yolo_focus_nchw(const float* x, int batch, int h, int w, float* out, void* stream);
+/* SPP (commons.py:124): buf is fp32 NHWC [B, h, w, c_total]; slice [0, c) holds x; slices [c, 2c), [2c, 3c), [3c, 4c) receive
+ * max_pool2d(x, k, stride 1, padding k // 2) for k = 5, 9, 13 (padding never wins: -inf).  c % 4 == 0, c_total % 4 == 0, c_total >= 4c */
+int sp_yolo_spp_nhwc(float* buf, int batch, int h, int w, int c, int c_total, void* stream);
+/* nn.UpsamplingNearest2d(scale_factor=2) from a channel slice into a channel slice: dst[b, y, x, j] = src[b, y/2, x/2, j], j < c; src / dst
+ * point at channel c0 of NHWC tensors with src_c_total / dst_c_total channels; dst is [B, 2h, 2w, .].  c, both totals and both offsets % 4 == 0 */
+int sp_upsample2_slice_nhwc(const float* src, int src_c_total, float* dst, int dst_c_total, int batch, int h, int w, int c, void* stream);
+/* YOLOv5Head.forward, eval branch (yolov5.py:134-149): level l's head conv output heads[l] is NHWC [B, ny_l, nx_l, anchors * a_stride] with
+ * anchor a's `no` values at [a * a_stride, a * a_stride + no) (a_stride >= no, % 4 == 0: the packed head pads every anchor's columns).
+ * out[b, row, k] (fp32 [B, N, no], N = sum anchors * ny_l * nx_l, rows ordered (level, anchor, y, x)) = sigmoid(v), then
+ * k < 2: (s * 2 - 0.5 + grid) * stride_l, k in {2, 3}: (s * 2)^2 * anchor_grid[l][a]; grid = (x, y).  3 levels; anchors <= 4;
+ * grid_hw / strides / anchor_wh are HOST arrays: [3][2] (ny, nx), [3], [3][anchors][2] */
+int sp_yolo_head_decode(const float* head0, const float* head1, const float* head2, int batch, const int* grid_hw, int anchors, int no, int a_stride,
+                        const float* strides, const float* anchor_wh, float* out, void* stream);
+/* non_max_suppression (yolov5_detector.py:52-128) of a batch: per image the candidates obj > conf_thresh, cls *= obj, multi-label expansion
+ * (multi_label: every (row, class) with cls*obj > conf_thresh in row-major order; else the best class (first on ties) if > conf_thresh),
+ * xywh -> xyxy, boxes offset by cls * 4096 unless agnostic, a descending score sort whose ties go to the lower candidate index, the greedy
+ * scan of torchvision.ops.nms (suppress IoU > iou_thresh) truncated at max_det, then - merge and 1 < n < 3000 - merge-NMS (kept box =
+ * score-weighted mean of the candidates with IoU > iou_thresh) and the redundancy filter (keep only kept boxes with another such candidate).
+ * Exact (no truncation) up to SP_YOLO_NMS_MAX_CANDIDATES candidates per image after the expansion; above that it returns SP_EINVAL.
+ * pred: fp32 [B, N, no]; out: fp32 [B, max_det, 6] (x1, y1, x2, y2, score, cls), rows [0, counts[b]) valid; counts: HOST int[B]; n_candidates: HOST int[B] or NULL, the
+ * candidates after the expansion (0: the reference's None).
+ * max_det <= SP_YOLO_NMS_MAX_DET.  Deterministic.  SYNCHRONOUS: it waits for the stream twice (candidate counts, then result counts). */
+#define SP_YOLO_NMS_MAX_CANDIDATES 32768
+#define SP_YOLO_NMS_MAX_DET 1024
+int sp_yolo_nms_workspace(int batch, int64_t* bytes);
+int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, float conf_thresh, float iou_thresh, int merge, int multi_label, int agnostic,
+                int max_det, void* workspace, int64_t workspace_bytes, float* out, int* counts, int* n_candidates, void* stream);
+/* clip_coords + the un-letterbox of single_predict (yolov5_detector.py:233-237) on `rows` rows of 6 floats (in place):
+ * x1, x2 clamped to [0, img_w], y1, y2 to [0, img_h], then x = (x - left) / ratio, y = (y - top) / ratio */
+int sp_yolo_boxes_to_source(float* det, int rows, float img_h, float img_w, float left, float top, float ratio, void* stream);
 
 #ifdef __cplusplus
 }

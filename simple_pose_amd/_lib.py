@@ -20,6 +20,10 @@ SP_CONV_PIXEL_SHUFFLE = 0x4
 SP_CONV_BF16 = 0x8
 SP_CONV_OUT_F32 = 0x10
 SP_CONV_BN_Y_MASK = 0x20
+SP_CONV_HARDSWISH = 0x40      # y = hardswish(acc*scale + shift) (+ residual after it): fp32 implicit GEMM only
+SP_CONV_OUT_SLICE = 0x80      # y = channel slice [c0, c0 + c_out) of an out_c-channel NHWC tensor (y pre-offset by c0)
+SP_LETTERBOX_FOCUS, SP_LETTERBOX_U8 = 0, 1
+SP_YOLO_NMS_MAX_CANDIDATES, SP_YOLO_NMS_MAX_DET = 32768, 1024
 CONV_TILES = ((128, 128), (64, 128), (128, 64), (64, 64), (256, 64), (128, 32))
 ABI_VERSION = 36
 SP_CONV_KERNEL_IGEMM, SP_CONV_KERNEL_RING, SP_CONV_KERNEL_PW, SP_CONV_KERNEL_RING_LW, SP_CONV_KERNEL_RING_LW4 = 0, 1, 2, 3, 4
@@ -165,6 +169,14 @@ SYMBOLS = {
     "sp_conv2d_wgrad_grouped": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, c_int64, _P]),
     "sp_pack_deconv_k4s2p1": (c_int, [_P, c_int, c_int, c_int, _P, c_int, _P]),
     "sp_fold_bn": (c_int, [_P, _P, _P, _P, c_int, c_float, c_int, _P, _P, _P]),
+    "sp_yolo_letterbox": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "sp_yolo_focus_nchw": (c_int, [_P, c_int, c_int, c_int, _P, _P]),
+    "sp_yolo_spp_nhwc": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "sp_upsample2_slice_nhwc": (c_int, [_P, c_int, _P, c_int, c_int, c_int, c_int, c_int, _P]),
+    "sp_yolo_head_decode": (c_int, [_P, _P, _P, c_int, ctypes.POINTER(c_int32), c_int, c_int, c_int, ctypes.POINTER(c_float), ctypes.POINTER(c_float), _P, _P]),
+    "sp_yolo_nms_workspace": (c_int, [c_int, ctypes.POINTER(c_int64)]),
+    "sp_yolo_nms": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, _P, c_int64, _P, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32), _P]),
+    "sp_yolo_boxes_to_source": (c_int, [_P, c_int, c_float, c_float, c_float, c_float, c_float, _P]),
 }
 
 _lib = None

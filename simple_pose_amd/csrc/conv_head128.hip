@@ -139,7 +139,7 @@ __global__ __launch_bounds__(THREADS_H, 1) void conv3x3_c128_head_kernel(const H
 bool sp_head128_ok(const sp_conv_desc* d) {
     if (d && d->c_in_group > 0) return false;
     const unsigned need = SP_CONV_BF16 | SP_CONV_OUT_NCHW;
-    return d && d->c_in == CH && (d->flags & need) == need && !(d->flags & SP_CONV_PIXEL_SHUFFLE) && d->c_out > 0 && d->c_out <= NH && d->n_pad == NH &&
+    return d && d->c_in == CH && (d->flags & need) == need && !(d->flags & (SP_CONV_PIXEL_SHUFFLE | SP_CONV_HARDSWISH | SP_CONV_OUT_SLICE)) && d->c_out > 0 && d->c_out <= NH && d->n_pad == NH &&
            d->out_c == d->c_out && d->taps_h == 3 && d->taps_w == 3 && d->stride == 1 && (d->stride_x == 0 || d->stride_x == 1) && d->dy0 == -1 && d->dx0 == -1 &&
            d->dy_step == 1 && d->dx_step == 1 && d->phases_y == 1 && d->phases_x == 1 && d->k_pad == 9 * CH && d->grid_h == d->in_h && d->grid_w == d->in_w &&
            d->out_h == d->in_h && d->out_w == d->in_w && d->oy_mul == 1 && d->ox_mul == 1 && d->oy_add == 0 && d->ox_add == 0;

@@ -118,6 +118,12 @@ struct ConvArgs {
 
 constexpr int BK = 32;  // floats per K tile (8 chunks of 16 B)
 
+// nn.Hardswish in torch's operation order: v * min(max(v + 3, 0), 6) / 6 (a division, not a multiplication by 1/6)
+__device__ __forceinline__ float hardswish(float v) {
+#pragma clang fp contract(off)
+    return v * fminf(fmaxf(v + 3.f, 0.f), 6.f) / 6.f;
+}
+
 __device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
@@ -579,6 +585,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     const bool nchw = p.flags & SP_CONV_OUT_NCHW;
     const bool pshuf = p.flags & SP_CONV_PIXEL_SHUFFLE;
     const bool relu = p.flags & SP_CONV_RELU;
+    const bool hsw = (!BF16 && !STATS && !BSTATS) && (p.flags & SP_CONV_HARDSWISH);   // (host-checked: fp32 inference launches only)
     const int hw_out = p.out_h * p.out_w;
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, p.y_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res ? p.res : p.y), (short)0, p.y_bytes, 0x00020000);
@@ -665,6 +672,10 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
             }
 #pragma unroll
             for (int e = 0; e < CPL; ++e) v[e] = v[e] * sc[e] + sh[e];
+            if (hsw) {                        // the activation comes BEFORE the residual add (YOLOv5 BottleNeck: x + cbr(x))
+#pragma unroll
+                for (int e = 0; e < CPL; ++e) v[e] = hardswish(v[e]);
+            }
             if (p.res) {
                 if constexpr (OUT16) {
                     const bf16x8 r8 = __builtin_bit_cast(bf16x8, rv[it]);
@@ -841,6 +852,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             v[e] = acc[i][n][4 * g + e] * sc + sh;
+                            if (hsw) v[e] = hardswish(v[e]);
                             if (relu) v[e] = v[e] > 0.f ? v[e] : 0.f;
                         }
                         __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, o, 0, 0);
@@ -850,6 +862,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
                             const int ro = rowtab[(row + e) * 4 + 3];
                             const unsigned o = (col_ok && ro >= 0) ? (unsigned)((ro + col_off) * 4) : OOB;
                             float v = acc[i][n][4 * g + e] * sc + sh;
+                            if (hsw) v = hardswish(v);
                             if (p.res) v += __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rr, o, 0, 0));
                             if (relu) v = v > 0.f ? v : 0.f;
                             __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, v), yr, o, 0, 0);
@@ -1028,7 +1041,23 @@ static int conv_fwd_impl(const sp_conv_desc* d, const void* x, const void* w_pac
     const bool uniform = (cg % bke == 0) && d->taps_h * d->taps_w <= 32;  // tap-validity bit mask is 32 bits wide
     if (uniform) SP_REQUIRE(d->k_pad == d->taps_h * d->taps_w * cg, "sp_conv2d_fwd: k_pad must equal taps*c_in when c_in fills whole K tiles");
     SP_REQUIRE((d->phases_y == 1 || d->phases_y == 2) && (d->phases_x == 1 || d->phases_x == 2), "sp_conv2d_fwd: phases must be 1 or 2");
-    const unsigned known = SP_CONV_RELU | SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE | SP_CONV_BF16 | SP_CONV_OUT_F32 | SP_CONV_BN_Y_MASK;
+    const unsigned known = SP_CONV_RELU | SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE | SP_CONV_BF16 | SP_CONV_OUT_F32 | SP_CONV_BN_Y_MASK |
+                           SP_CONV_HARDSWISH | SP_CONV_OUT_SLICE;
+    const bool slice = d->flags & SP_CONV_OUT_SLICE;
+    if (d->flags & (SP_CONV_HARDSWISH | SP_CONV_OUT_SLICE)) {
+        // the detector's epilogues: fp32 inference launches of the implicit GEMM only (the other kernel structures refuse the bits themselves)
+        SP_REQUIRE(!bf16 && !stats_s && !bsrc && !phs && !abn && d->c_in_group == 0 && d->kernel == SP_CONV_KERNEL_IGEMM &&
+                       !(d->flags & (SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE | SP_CONV_BN_Y_MASK)) &&
+                       !((d->flags & SP_CONV_HARDSWISH) && (d->flags & SP_CONV_RELU)),
+                   "sp_conv2d_fwd: SP_CONV_HARDSWISH / SP_CONV_OUT_SLICE need an fp32 NHWC inference launch on the implicit-GEMM kernel (no ReLU, "
+                   "no statistics, not grouped)");
+    }
+    if (slice) {
+        SP_REQUIRE(!residual, "sp_conv2d_fwd: SP_CONV_OUT_SLICE takes no residual");
+        SP_REQUIRE(d->out_c % 4 == 0 && d->c_out % 4 == 0 && d->c_out <= d->out_c && (reinterpret_cast<uintptr_t>(y) & 15) == 0,
+                   "sp_conv2d_fwd: SP_CONV_OUT_SLICE needs out_c %% 4 == 0, c_out %% 4 == 0, c_out <= out_c and y 16-byte aligned (c0 %% 4 == 0) "
+                   "(out_c %d, c_out %d)", d->out_c, d->c_out);
+    }
     const bool out16 = bf16 && !(d->flags & SP_CONV_OUT_F32);
     SP_REQUIRE(!(d->flags & SP_CONV_BN_Y_MASK) || (bsrc && out16) || sp_name_query_active(),
                "sp_conv2d_fwd: SP_CONV_BN_Y_MASK belongs to a BSTATS dgrad launch with bf16 activations and gradients");
@@ -1044,7 +1073,7 @@ static int conv_fwd_impl(const sp_conv_desc* d, const void* x, const void* w_pac
         SP_REQUIRE(d->c_out % 4 == 0 && d->out_c * 4 == d->c_out && d->oy_mul == 2 && d->ox_mul == 2 && d->n_pad == d->c_out,
                    "sp_conv2d_fwd: pixel shuffle needs out_c == c_out/4 == n_pad/4, oy_mul == ox_mul == 2");
         max_oy += 1; max_ox += 1;
-    } else {
+    } else if (!slice) {
         SP_REQUIRE(d->out_c == d->c_out, "sp_conv2d_fwd: out_c=%d != c_out=%d", d->out_c, d->c_out);
     }
     SP_REQUIRE(d->oy_mul > 0 && d->ox_mul > 0 && min_oy >= 0 && min_ox >= 0 && max_oy < d->out_h && max_ox < d->out_w,
@@ -1072,6 +1101,8 @@ static int conv_fwd_impl(const sp_conv_desc* d, const void* x, const void* w_pac
     a.phases_x = d->phases_x; a.flags = d->flags; a.tiles_m = a.tiles_n = 0;
     a.x_bytes = (int)(in_elems * es); a.w_bytes = (int)(w_elems * es);
     a.y_bytes = (int)(out_elems * (((d->flags & SP_CONV_OUT_NCHW) || !out16) ? 4 : 2));
+    if (slice)          // y starts c0 channels into the tensor: the extent ends with the last pixel's slice
+        a.y_bytes = (int)((out_elems - d->out_c + d->c_out) * 4);
     a.stats_s = stats_s; a.stats_q = stats_q; a.stats_stride = d->n_pad;
     a.by = bsrc ? bsrc->y : nullptr; a.bz = bsrc ? bsrc->z : nullptr; a.bmean = bsrc ? bsrc->mean : nullptr; a.binvstd = bsrc ? bsrc->invstd : nullptr;
     a.bz2 = bsrc ? bsrc->z2 : nullptr; a.bmean2 = bsrc ? bsrc->mean2 : nullptr; a.binvstd2 = bsrc ? bsrc->invstd2 : nullptr; a.stats_q2 = bsrc ? bsrc->q2 : nullptr;

@@ -348,7 +348,7 @@ int launch_pw(const PwArgs& a, hipStream_t stream) {
 extern "C" int sp_conv2d_pw_ok(const sp_conv_desc* d) {
     if (d && d->c_in_group > 0) return 0;
     if (!d) return 0;
-    if (d->flags & (SP_CONV_BF16 | SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE | SP_CONV_OUT_F32)) return 0;
+    if (d->flags & (SP_CONV_BF16 | SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE | SP_CONV_OUT_F32 | SP_CONV_HARDSWISH | SP_CONV_OUT_SLICE)) return 0;
     if (d->taps_h != 1 || d->taps_w != 1 || d->stride != 1 || (d->stride_x != 0 && d->stride_x != 1)) return 0;
     if (d->phases_y != 1 || d->phases_x != 1 || d->dy0 != 0 || d->dx0 != 0) return 0;
     if (d->grid_h != d->in_h || d->grid_w != d->in_w || d->out_h != d->in_h || d->out_w != d->in_w) return 0;

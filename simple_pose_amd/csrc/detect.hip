@@ -1,0 +1,563 @@
+// detect.hip - the YOLOv5 person detector's non-convolution launches (fp32): letterbox + Focus input, SPP, slice-to-slice nearest
+// upsampling, the head decode and the batched YOLO NMS with merge (detector/yolov5_detector.py, detector/nets/{commons,yolov5}.py).
+// The convolutions run on the implicit GEMM (conv_igemm.hip: SP_CONV_HARDSWISH, SP_CONV_OUT_SLICE).
+#include "sp_common.h"
+
+#include <stdint.h>
+
+namespace {
+
+// ---- letterbox: OpenCV's 8-bit INTER_LINEAR restated -------------------------------------------------------------------------------------
+// fx = (float)((dx + 0.5) * scale - 0.5), sx = floor(fx), fx -= sx, clamped at both borders (fx = 0); coefficients saturate_cast<short>(c * 2048)
+// (round half to even) for c = 1 - fx and c = fx separately; rows: S[x0] * a0 + S[x1] * a1 (int), columns: (h0 * b0 + h1 * b1 + 2^21) >> 22.
+__device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0, int& s1, int& a0, int& a1) {
+    float f = (float)((d + 0.5) * scale - 0.5);
+    int s = (int)floorf(f);
+    f -= (float)s;
+    if (s < 0) { f = 0.f; s = 0; }
+    if (s >= ssize - 1) { f = 0.f; s = ssize - 1; }
+    s0 = s;
+    s1 = s + 1 < ssize ? s + 1 : ssize - 1;
+    a0 = __float2int_rn((1.f - f) * 2048.f);
+    a1 = __float2int_rn(f * 2048.f);
+}
+
+struct LbArgs {
+    const unsigned char* src;
+    int B, sh, sw, nh, nw, top, left, oh, ow, mode;
+    double sy, sx;      // source / destination size ratios (OpenCV's scale_y / scale_x)
+    int kind;           // 0 copy, 1 bilinear, 2 INTER_AREA 2x
+};
+
+// BGR values of canvas pixel (oy, ox) of image b: the source coefficients are computed once per pixel for its three channels
+__device__ __forceinline__ void canvas_px(const LbArgs& a, int b, int oy, int ox, int v[3]) {
+    const int y = oy - a.top, x = ox - a.left;
+    if (y < 0 || y >= a.nh || x < 0 || x >= a.nw) { v[0] = v[1] = v[2] = 114; return; }
+    const unsigned char* S = a.src + (size_t)b * a.sh * a.sw * 3;
+    if (a.kind == 0) {
+        const unsigned char* p = S + ((size_t)y * a.sw + x) * 3;
+        for (int c = 0; c < 3; ++c) v[c] = p[c];
+        return;
+    }
+    if (a.kind == 2) {
+        const unsigned char* p0 = S + ((size_t)(2 * y) * a.sw + 2 * x) * 3;
+        const unsigned char* p1 = p0 + (size_t)a.sw * 3;
+        for (int c = 0; c < 3; ++c) v[c] = (p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2;
+        return;
+    }
+    int x0, x1, ax0, ax1, y0, y1, by0, by1;
+    lin_coef(x, a.sx, a.sw, x0, x1, ax0, ax1);
+    lin_coef(y, a.sy, a.sh, y0, y1, by0, by1);
+    const unsigned char* R0 = S + (size_t)y0 * a.sw * 3;
+    const unsigned char* R1 = S + (size_t)y1 * a.sw * 3;
+    for (int c = 0; c < 3; ++c) {
+        const int h0 = R0[x0 * 3 + c] * ax0 + R0[x1 * 3 + c] * ax1;
+        const int h1 = R1[x0 * 3 + c] * ax0 + R1[x1 * 3 + c] * ax1;
+        const long long t = ((long long)h0 * by0 + (long long)h1 * by1 + (1ll << 21)) >> 22;
+        v[c] = t < 0 ? 0 : (t > 255 ? 255 : (int)t);
+    }
+}
+
+__global__ void letterbox_kernel(const LbArgs a, void* out) {
+    int px[3];
+    if (a.mode == SP_LETTERBOX_U8) {
+        const long long n = (long long)a.B * a.oh * a.ow;
+        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+        if (i >= n) return;
+        const int b = (int)(i / ((long long)a.oh * a.ow));
+        const int r = (int)(i - (long long)b * a.oh * a.ow), oy = r / a.ow, ox = r - oy * a.ow;
+        unsigned char* o = reinterpret_cast<unsigned char*>(out) + i * 3;
+        canvas_px(a, b, oy, ox, px);
+        for (int c = 0; c < 3; ++c) o[c] = (unsigned char)px[c];
+        return;
+    }
+    const int fh = a.oh / 2, fw = a.ow / 2;
+    const long long n = (long long)a.B * fh * fw;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = (int)(i / ((long long)fh * fw));
+    const int r = (int)(i - (long long)b * fh * fw), fy = r / fw, fx = r - fy * fw;
+    float v[12];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int oy = 2 * fy + (g & 1), ox = 2 * fx + (g >> 1);         // Focus: (::2, ::2), (1::2, ::2), (::2, 1::2), (1::2, 1::2)
+        canvas_px(a, b, oy, ox, px);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[3 * g + c] = (float)px[2 - c] / 255.f;     // BGR -> RGB, .div(255.0)
+    }
+    f32x4* o = reinterpret_cast<f32x4*>(reinterpret_cast<float*>(out) + i * 12);
+    o[0] = f32x4{v[0], v[1], v[2], v[3]};
+    o[1] = f32x4{v[4], v[5], v[6], v[7]};
+    o[2] = f32x4{v[8], v[9], v[10], v[11]};
+}
+
+__global__ void focus_nchw_kernel(const float* __restrict__ x, int B, int h, int w, float* __restrict__ out) {
+    const int fh = h / 2, fw = w / 2;
+    const long long n = (long long)B * fh * fw;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = (int)(i / ((long long)fh * fw));
+    const int r = (int)(i - (long long)b * fh * fw), fy = r / fw, fx = r - fy * fw;
+    float v[12];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        const int y = 2 * fy + (g & 1), xx = 2 * fx + (g >> 1);
+#pragma unroll
+        for (int c = 0; c < 3; ++c) v[3 * g + c] = x[(((size_t)b * 3 + c) * h + y) * w + xx];
+    }
+    f32x4* o = reinterpret_cast<f32x4*>(out + i * 12);
+    o[0] = f32x4{v[0], v[1], v[2], v[3]};
+    o[1] = f32x4{v[4], v[5], v[6], v[7]};
+    o[2] = f32x4{v[8], v[9], v[10], v[11]};
+}
+
+// ---- SPP: max pools 5 / 9 / 13 (stride 1, padding k // 2) of slice 0 into slices 1..3; one thread per (pixel, 4 channels) --------------
+__global__ void spp_kernel(float* buf, int B, int h, int w, int c, int ct) {
+    const int c4 = c / 4;
+    const long long n = (long long)B * h * w * c4;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int q = (int)(i % c4);
+    const long long pix = i / c4;
+    const int b = (int)(pix / ((long long)h * w));
+    const int r = (int)(pix - (long long)b * h * w), y = r / w, x = r - y * w;
+    const float NEG = -__builtin_huge_valf();
+    f32x4 m5 = {NEG, NEG, NEG, NEG}, m9 = m5, m13 = m5;
+    for (int dy = -6; dy <= 6; ++dy) {
+        const int yy = y + dy;
+        if (yy < 0 || yy >= h) continue;
+        const int ay = dy < 0 ? -dy : dy;
+        for (int dx = -6; dx <= 6; ++dx) {
+            const int xx = x + dx;
+            if (xx < 0 || xx >= w) continue;
+            const int ax = dx < 0 ? -dx : dx;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(buf + (((size_t)b * h + yy) * w + xx) * ct + 4 * q);
+            const int rr = ay > ax ? ay : ax;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                m13[e] = fmaxf(m13[e], v[e]);
+                if (rr <= 4) m9[e] = fmaxf(m9[e], v[e]);
+                if (rr <= 2) m5[e] = fmaxf(m5[e], v[e]);
+            }
+        }
+    }
+    float* o = buf + pix * ct + 4 * q;
+    *reinterpret_cast<f32x4*>(o + c) = m5;
+    *reinterpret_cast<f32x4*>(o + 2 * c) = m9;
+    *reinterpret_cast<f32x4*>(o + 3 * c) = m13;
+}
+
+__global__ void upsample2_slice_kernel(const float* __restrict__ src, int sct, float* __restrict__ dst, int dct, int B, int h, int w, int c) {
+    const int c4 = c / 4, H = 2 * h, W = 2 * w;
+    const long long n = (long long)B * H * W * c4;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int q = (int)(i % c4);
+    const long long pix = i / c4;
+    const int b = (int)(pix / ((long long)H * W));
+    const int r = (int)(pix - (long long)b * H * W), y = r / W, x = r - y * W;
+    *reinterpret_cast<f32x4*>(dst + pix * dct + 4 * q) =
+        *reinterpret_cast<const f32x4*>(src + (((size_t)b * h + y / 2) * w + x / 2) * sct + 4 * q);
+}
+
+// ---- head decode -------------------------------------------------------------------------------------------------------------------------
+struct HeadArgs {
+    const float* in[3];
+    int ny[3], nx[3], row0[4];
+    float stride[3];
+    float anchor[3][4][2];
+    int B, A, no, as, N;
+};
+
+__global__ void head_decode_kernel(const HeadArgs a, float* __restrict__ out) {
+    const long long n = (long long)a.B * a.N;
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const int b = (int)(i / a.N), row = (int)(i - (long long)b * a.N);
+    const int l = row < a.row0[1] ? 0 : (row < a.row0[2] ? 1 : 2);
+    const int ny = a.ny[l], nx = a.nx[l];
+    int r = row - a.row0[l];
+    const int an = r / (ny * nx);
+    r -= an * ny * nx;
+    const int y = r / nx, x = r - y * nx;
+    const float* v = a.in[l] + (((size_t)b * ny + y) * nx + x) * (a.A * a.as) + an * a.as;
+    float* o = out + i * a.no;
+    for (int k = 0; k < a.no; ++k) {
+#pragma clang fp contract(off)
+        const float s = 1.f / (1.f + expf(-v[k]));
+        float t;
+        if (k < 2) t = (s * 2.f - 0.5f + (float)(k == 0 ? x : y)) * a.stride[l];
+        else if (k < 4) { const float u = s * 2.f; t = u * u * a.anchor[l][an][k - 2]; }
+        else t = s;
+        o[k] = t;
+    }
+}
+
+// ---- YOLO NMS ----------------------------------------------------------------------------------------------------------------------------
+constexpr int CAP = SP_YOLO_NMS_MAX_CANDIDATES;
+constexpr int NT = 256;
+
+struct NmsWs {          // per image: [CAP] boxes (x1, y1, x2, y2, not offset), [CAP] (score, cls), [CAP] order; then counts
+    float4* box;
+    float2* sc;
+    int* order;
+    int* n_cand;        // [B]
+    int* n_out;         // [B]
+};
+
+__device__ __forceinline__ float box_iou1(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    const float area_a = (a.z - a.x) * (a.w - a.y), area_b = (b.z - b.x) * (b.w - b.y);
+    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+    const float inter = w * h;
+    return inter / (area_a + area_b - inter);
+}
+
+// exclusive prefix sum over the 256 threads of the block; returns the prefix, `total` = the block sum
+__device__ __forceinline__ int block_scan(int v, int* lds, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += lds[w];
+    total = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return base + x - v;
+}
+
+// candidates of image blockIdx.x in (row, class) order; counts all, stores the first CAP
+__global__ __launch_bounds__(NT) void nms_candidates_kernel(const float* __restrict__ pred, int N, int no, float conf, int multi, NmsWs ws) {
+    __shared__ int lds[4];
+    const int b = blockIdx.x;
+    const float* P = pred + (size_t)b * N * no;
+    float4* box = ws.box + (size_t)b * CAP;
+    float2* sc = ws.sc + (size_t)b * CAP;
+    const int nc = no - 5;
+    int base = 0;
+    for (int r0 = 0; r0 < N; r0 += NT) {
+        const int r = r0 + threadIdx.x;
+        int cnt = 0, best = 0;
+        float obj = 0.f, bestv = 0.f;
+        if (r < N) {
+            obj = P[(size_t)r * no + 4];
+            if (obj > conf) {
+                if (multi) {
+                    for (int j = 0; j < nc; ++j) cnt += (P[(size_t)r * no + 5 + j] * obj > conf);
+                } else {
+                    bestv = P[(size_t)r * no + 5] * obj;
+                    for (int j = 1; j < nc; ++j) {
+                        const float v = P[(size_t)r * no + 5 + j] * obj;
+                        if (v > bestv) { bestv = v; best = j; }
+                    }
+                    cnt = bestv > conf;
+                }
+            }
+        }
+        int total;
+        int k = base + block_scan(cnt, lds, total);
+        if (cnt) {
+            const float* p = P + (size_t)r * no;
+            float4 bx;
+            {
+#pragma clang fp contract(off)
+                bx = make_float4(p[0] - p[2] / 2.f, p[1] - p[3] / 2.f, p[0] + p[2] / 2.f, p[1] + p[3] / 2.f);
+            }
+            if (multi) {
+                for (int j = 0; j < nc; ++j) {
+                    const float v = p[5 + j] * obj;
+                    if (v > conf) {
+                        if (k < CAP) { box[k] = bx; sc[k] = make_float2(v, (float)j); }
+                        ++k;
+                    }
+                }
+            } else if (k < CAP) {
+                box[k] = bx;
+                sc[k] = make_float2(bestv, (float)best);
+            }
+        }
+        base += total;
+    }
+    if (threadIdx.x == 0) ws.n_cand[b] = base;
+}
+
+// descending score, ties to the lower candidate index: order[rank(i)] = i
+__global__ __launch_bounds__(NT) void nms_rank_kernel(NmsWs ws) {
+    __shared__ float tile[NT];
+    const int b = blockIdx.y;
+    const int n = ws.n_cand[b];
+    if ((int)blockIdx.x * NT >= n) return;
+    const float2* sc = ws.sc + (size_t)b * CAP;
+    const int i = blockIdx.x * NT + threadIdx.x;
+    const float si = i < n ? sc[i].x : 0.f;
+    int rank = 0;
+    for (int t0 = 0; t0 < n; t0 += NT) {
+        const int j = t0 + threadIdx.x;
+        tile[threadIdx.x] = j < n ? sc[j].x : 0.f;
+        __syncthreads();
+        const int lim = n - t0 < NT ? n - t0 : NT;
+        for (int jj = 0; jj < lim; ++jj) {
+            const float sj = tile[jj];
+            rank += (sj > si) || (sj == si && t0 + jj < i);
+        }
+        __syncthreads();
+    }
+    if (i < n) ws.order[(size_t)b * CAP + rank] = i;
+}
+
+// greedy scan (torchvision.ops.nms order, truncated at max_det), merge, redundancy filter, output
+__global__ __launch_bounds__(NT) void nms_select_kernel(NmsWs ws, float iou_thr, int merge, int agnostic, int max_det, float* __restrict__ out) {
+    __shared__ float4 kb[SP_YOLO_NMS_MAX_DET];       // kept boxes (class-offset)
+    __shared__ int kidx[SP_YOLO_NMS_MAX_DET];
+    __shared__ float4 cb[NT];
+    __shared__ int alive[NT];
+    __shared__ unsigned long long masks[NT][NT / 64];
+    __shared__ int s_nk;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = ws.n_cand[b];
+    const float4* box = ws.box + (size_t)b * CAP;
+    const float2* sc = ws.sc + (size_t)b * CAP;
+    const int* order = ws.order + (size_t)b * CAP;
+    auto offset_box = [&](int ci) {
+#pragma clang fp contract(off)
+        const float4 v = box[ci];
+        const float c = agnostic ? 0.f : sc[ci].y * 4096.f;
+        return make_float4(v.x + c, v.y + c, v.z + c, v.w + c);
+    };
+    if (tid == 0) s_nk = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += NT) {
+        const int nk = s_nk;
+        if (nk >= max_det) break;
+        const int pos = base + tid;
+        const bool valid = pos < n;
+        const float4 bx = valid ? offset_box(order[pos]) : make_float4(0.f, 0.f, 0.f, 0.f);
+        bool a = valid;
+        for (int k = 0; k < nk && a; ++k)
+            if (box_iou1(kb[k], bx) > iou_thr) a = false;
+        cb[tid] = bx;
+        alive[tid] = a;
+        __syncthreads();
+        unsigned long long m[NT / 64] = {0ull, 0ull, 0ull, 0ull};
+        if (a)
+            for (int s = 0; s < tid; ++s)
+                if (alive[s] && box_iou1(cb[s], bx) > iou_thr) m[s >> 6] |= 1ull << (s & 63);
+#pragma unroll
+        for (int q = 0; q < NT / 64; ++q) masks[tid][q] = m[q];
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long keep[NT / 64] = {0ull, 0ull, 0ull, 0ull};
+            int k = nk;
+            for (int t = 0; t < NT && k < max_det; ++t) {
+                if (!alive[t]) continue;
+                if ((masks[t][0] & keep[0]) | (masks[t][1] & keep[1]) | (masks[t][2] & keep[2]) | (masks[t][3] & keep[3])) continue;
+                keep[t >> 6] |= 1ull << (t & 63);
+                kb[k] = cb[t];
+                kidx[k] = order[base + t];
+                ++k;
+            }
+            s_nk = k;
+        }
+        __syncthreads();
+    }
+    const int nk = s_nk;
+    float* O = out + (size_t)b * max_det * 6;
+    const bool do_merge = merge && n > 1 && n < 3000;
+    // merge: one wave per kept box, lanes over the candidates in index order, fixed butterfly -> deterministic.  The merged box and the
+    // redundancy count go back into kb / alive-sized scratch (cb is reused for nothing else from here)
+    __shared__ float4 mbox[SP_YOLO_NMS_MAX_DET];
+    __shared__ int mcnt[SP_YOLO_NMS_MAX_DET];
+    if (do_merge) {
+        const int lane = tid & 63, wave = tid >> 6;
+        for (int k = wave; k < nk; k += NT / 64) {
+            const float4 kbx = kb[k];
+            float sw = 0.f, s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+            int cnt = 0;
+            for (int j = lane; j < n; j += 64) {
+                if (box_iou1(kbx, offset_box(j)) > iou_thr) {
+                    const float w = sc[j].x;
+                    const float4 v = box[j];
+                    sw += w; s0 += w * v.x; s1 += w * v.y; s2 += w * v.z; s3 += w * v.w;
+                    ++cnt;
+                }
+            }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                sw += __shfl_xor(sw, o, 64); s0 += __shfl_xor(s0, o, 64); s1 += __shfl_xor(s1, o, 64);
+                s2 += __shfl_xor(s2, o, 64); s3 += __shfl_xor(s3, o, 64); cnt += __shfl_xor(cnt, o, 64);
+            }
+            if (lane == 0) { mbox[k] = make_float4(s0 / sw, s1 / sw, s2 / sw, s3 / sw); mcnt[k] = cnt; }
+        }
+        __syncthreads();
+    }
+    if (tid == 0) {
+        int r = 0;
+        for (int k = 0; k < nk; ++k) {
+            if (do_merge && mcnt[k] <= 1) continue;
+            const int ci = kidx[k];
+            const float4 v = do_merge ? mbox[k] : box[ci];
+            float* o = O + (size_t)r * 6;
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; o[4] = sc[ci].x; o[5] = sc[ci].y;
+            ++r;
+        }
+        ws.n_out[b] = r;
+    }
+}
+
+__global__ void boxes_to_source_kernel(float* det, int rows, float img_h, float img_w, float left, float top, float ratio) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= rows) return;
+    float* d = det + (size_t)i * 6;
+    d[0] = (fminf(fmaxf(d[0], 0.f), img_w) - left) / ratio;
+    d[1] = (fminf(fmaxf(d[1], 0.f), img_h) - top) / ratio;
+    d[2] = (fminf(fmaxf(d[2], 0.f), img_w) - left) / ratio;
+    d[3] = (fminf(fmaxf(d[3], 0.f), img_h) - top) / ratio;
+}
+
+int64_t nms_ws_layout(int B, NmsWs* ws, void* base) {
+    char* p = reinterpret_cast<char*>(base);
+    int64_t off = 0;
+    auto take = [&](int64_t bytes) { char* q = p ? p + off : nullptr; off += (bytes + 255) / 256 * 256; return q; };
+    NmsWs w;
+    w.box = reinterpret_cast<float4*>(take((int64_t)B * CAP * 16));
+    w.sc = reinterpret_cast<float2*>(take((int64_t)B * CAP * 8));
+    w.order = reinterpret_cast<int*>(take((int64_t)B * CAP * 4));
+    w.n_cand = reinterpret_cast<int*>(take((int64_t)B * 4));
+    w.n_out = reinterpret_cast<int*>(take((int64_t)B * 4));
+    if (ws) *ws = w;
+    return off;
+}
+
+}  // namespace
+
+extern "C" int sp_yolo_letterbox(const unsigned char* src, int batch, int src_h, int src_w, int new_h, int new_w, int top, int left, int out_h,
+                                 int out_w, int mode, void* out, void* stream) {
+    SP_REQUIRE(src && out, "sp_yolo_letterbox: null pointer");
+    SP_REQUIRE(batch > 0 && src_h > 0 && src_w > 0 && new_h > 0 && new_w > 0 && top >= 0 && left >= 0 && top + new_h <= out_h &&
+                   left + new_w <= out_w && (long long)batch * out_h * out_w * 12 < (1ll << 31),
+               "sp_yolo_letterbox: bad geometry (src %dx%d -> %dx%d at (%d, %d) in %dx%d)", src_h, src_w, new_h, new_w, top, left, out_h, out_w);
+    SP_REQUIRE(mode == SP_LETTERBOX_U8 || (mode == SP_LETTERBOX_FOCUS && out_h % 2 == 0 && out_w % 2 == 0),
+               "sp_yolo_letterbox: mode %d (Focus output needs an even canvas)", mode);
+    LbArgs a;
+    a.src = src; a.B = batch; a.sh = src_h; a.sw = src_w; a.nh = new_h; a.nw = new_w; a.top = top; a.left = left; a.oh = out_h; a.ow = out_w;
+    a.mode = mode;
+    a.sx = 1.0 / ((double)new_w / src_w);        // OpenCV: inv_scale = dsize / ssize, scale = 1 / inv_scale
+    a.sy = 1.0 / ((double)new_h / src_h);
+    a.kind = (new_h == src_h && new_w == src_w) ? 0 : ((src_w == 2 * new_w && src_h == 2 * new_h) ? 2 : 1);
+    const long long n = mode == SP_LETTERBOX_U8 ? (long long)batch * out_h * out_w : (long long)batch * (out_h / 2) * (out_w / 2);
+    hipLaunchKernelGGL(letterbox_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a, out);
+    return sp_check_launch("letterbox_kernel");
+}
+
+extern "C" int sp_yolo_focus_nchw(const float* x, int batch, int h, int w, float* out, void* stream) {
+    SP_REQUIRE(x && out, "sp_yolo_focus_nchw: null pointer");
+    SP_REQUIRE(batch > 0 && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0 && (long long)batch * h * w * 3 < (1ll << 31),
+               "sp_yolo_focus_nchw: bad shape %dx%dx%d", batch, h, w);
+    const long long n = (long long)batch * (h / 2) * (w / 2);
+    hipLaunchKernelGGL(focus_nchw_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, x, batch, h, w, out);
+    return sp_check_launch("focus_nchw_kernel");
+}
+
+extern "C" int sp_yolo_spp_nhwc(float* buf, int batch, int h, int w, int c, int c_total, void* stream) {
+    SP_REQUIRE(buf, "sp_yolo_spp_nhwc: null pointer");
+    SP_REQUIRE(batch > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && c_total % 4 == 0 && c_total >= 4 * c &&
+                   (long long)batch * h * w * c_total < (1ll << 31),
+               "sp_yolo_spp_nhwc: c %d / c_total %d (multiples of 4, c_total >= 4c)", c, c_total);
+    const long long n = (long long)batch * h * w * (c / 4);
+    hipLaunchKernelGGL(spp_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, buf, batch, h, w, c, c_total);
+    return sp_check_launch("spp_kernel");
+}
+
+extern "C" int sp_upsample2_slice_nhwc(const float* src, int src_c_total, float* dst, int dst_c_total, int batch, int h, int w, int c, void* stream) {
+    SP_REQUIRE(src && dst, "sp_upsample2_slice_nhwc: null pointer");
+    SP_REQUIRE(batch > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0 && src_c_total % 4 == 0 && dst_c_total % 4 == 0 && c <= src_c_total &&
+                   c <= dst_c_total && (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (reinterpret_cast<uintptr_t>(dst) & 15) == 0 &&
+                   (long long)batch * 4 * h * w * dst_c_total < (1ll << 31),
+               "sp_upsample2_slice_nhwc: channels %d of %d -> %d (multiples of 4, 16-byte aligned slices)", c, src_c_total, dst_c_total);
+    const long long n = (long long)batch * 4 * h * w * (c / 4);
+    hipLaunchKernelGGL(upsample2_slice_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, src, src_c_total, dst, dst_c_total,
+                       batch, h, w, c);
+    return sp_check_launch("upsample2_slice_kernel");
+}
+
+extern "C" int sp_yolo_head_decode(const float* head0, const float* head1, const float* head2, int batch, const int* grid_hw, int anchors, int no,
+                                   int a_stride, const float* strides, const float* anchor_wh, float* out, void* stream) {
+    SP_REQUIRE(head0 && head1 && head2 && grid_hw && strides && anchor_wh && out, "sp_yolo_head_decode: null pointer");
+    SP_REQUIRE(batch > 0 && anchors > 0 && anchors <= 4 && no >= 5 && a_stride >= no && a_stride % 4 == 0,
+               "sp_yolo_head_decode: anchors %d (1..4), no %d, a_stride %d (>= no, %% 4 == 0)", anchors, no, a_stride);
+    HeadArgs a;
+    a.in[0] = head0; a.in[1] = head1; a.in[2] = head2;
+    a.B = batch; a.A = anchors; a.no = no; a.as = a_stride;
+    a.row0[0] = 0;
+    for (int l = 0; l < 3; ++l) {
+        a.ny[l] = grid_hw[2 * l]; a.nx[l] = grid_hw[2 * l + 1];
+        SP_REQUIRE(a.ny[l] > 0 && a.nx[l] > 0, "sp_yolo_head_decode: level %d grid %dx%d", l, a.ny[l], a.nx[l]);
+        a.stride[l] = strides[l];
+        for (int an = 0; an < 4; ++an)
+            for (int k = 0; k < 2; ++k) a.anchor[l][an][k] = an < anchors ? anchor_wh[(l * anchors + an) * 2 + k] : 0.f;
+        a.row0[l + 1] = a.row0[l] + anchors * a.ny[l] * a.nx[l];
+    }
+    a.N = a.row0[3];
+    SP_REQUIRE((long long)batch * a.N * no < (1ll << 31), "sp_yolo_head_decode: output too large");
+    const long long n = (long long)batch * a.N;
+    hipLaunchKernelGGL(head_decode_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a, out);
+    return sp_check_launch("head_decode_kernel");
+}
+
+extern "C" int sp_yolo_nms_workspace(int batch, int64_t* bytes) {
+    SP_REQUIRE(bytes && batch > 0, "sp_yolo_nms_workspace: bad argument");
+    *bytes = nms_ws_layout(batch, nullptr, nullptr);
+    return SP_OK;
+}
+
+extern "C" int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, float conf_thresh, float iou_thresh, int merge, int multi_label,
+                           int agnostic, int max_det, void* workspace, int64_t workspace_bytes, float* out, int* counts, int* n_candidates,
+                           void* stream) {
+    SP_REQUIRE(pred && workspace && out && counts, "sp_yolo_nms: null pointer");
+    SP_REQUIRE(batch > 0 && n_rows > 0 && no >= 6 && max_det > 0 && max_det <= SP_YOLO_NMS_MAX_DET && (long long)batch * n_rows * no < (1ll << 31),
+               "sp_yolo_nms: batch %d, rows %d, no %d (>= 6), max_det %d (1..%d)", batch, n_rows, no, max_det, SP_YOLO_NMS_MAX_DET);
+    NmsWs ws;
+    const int64_t need = nms_ws_layout(batch, &ws, workspace);
+    SP_REQUIRE(workspace_bytes >= need, "sp_yolo_nms: workspace %lld bytes, need %lld (sp_yolo_nms_workspace)", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(nms_candidates_kernel, dim3(batch), dim3(NT), 0, s, pred, n_rows, no, conf_thresh, multi_label ? 1 : 0, ws);
+    int rc = sp_check_launch("nms_candidates_kernel");
+    if (rc != SP_OK) return rc;
+    if (hipMemcpyAsync(counts, ws.n_cand, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        sp_set_error("sp_yolo_nms: reading the candidate counts failed");
+        return SP_ELAUNCH;
+    }
+    int n_max = 0;
+    for (int b = 0; b < batch; ++b) {
+        SP_REQUIRE(counts[b] <= CAP, "sp_yolo_nms: image %d has %d candidates after the multi-label expansion, above the cap of %d "
+                   "(raise conf_thresh)", b, counts[b], CAP);
+        n_max = counts[b] > n_max ? counts[b] : n_max;
+        if (n_candidates) n_candidates[b] = counts[b];
+    }
+    if (n_max > 0) {
+        hipLaunchKernelGGL(nms_rank_kernel, dim3(sp_ceil_div(n_max, NT), batch), dim3(NT), 0, s, ws);
+        rc = sp_check_launch("nms_rank_kernel");
+        if (rc != SP_OK) return rc;
+    }
+    hipLaunchKernelGGL(nms_select_kernel, dim3(batch), dim3(NT), 0, s, ws, iou_thresh, merge ? 1 : 0, agnostic ? 1 : 0, max_det, out);
+    rc = sp_check_launch("nms_select_kernel");
+    if (rc != SP_OK) return rc;
+    if (hipMemcpyAsync(counts, ws.n_out, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
+        sp_set_error("sp_yolo_nms: reading the result counts failed");
+        return SP_ELAUNCH;
+    }
+    return SP_OK;
+}
+
+extern "C" int sp_yolo_boxes_to_source(float* det, int rows, float img_h, float img_w, float left, float top, float ratio, void* stream) {
+    SP_REQUIRE(det && rows >= 0 && ratio > 0.f, "sp_yolo_boxes_to_source: bad argument");
+    if (rows == 0) return SP_OK;
+    hipLaunchKernelGGL(boxes_to_source_kernel, dim3(sp_ceil_div(rows, 256)), dim3(256), 0, (hipStream_t)stream, det, rows, img_h, img_w, left, top, ratio);
+    return sp_check_launch("boxes_to_source_kernel");
+}

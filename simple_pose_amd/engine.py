@@ -22,7 +22,7 @@ from typing import Dict, List, Optional, Tuple
 import torch
 
 from . import _lib
-from ._lib import ConvDesc, SP_CONV_BF16, SP_CONV_OUT_NCHW, SP_CONV_PIXEL_SHUFFLE, SP_CONV_RELU
+from ._lib import ConvDesc, SP_CONV_BF16, SP_CONV_HARDSWISH, SP_CONV_OUT_NCHW, SP_CONV_OUT_SLICE, SP_CONV_PIXEL_SHUFFLE, SP_CONV_RELU
 
 BN_EPS = 1e-5
 
@@ -121,6 +121,7 @@ class Op:
     lane: int = 0                # HIP stream the op is issued on (0 = the caller's stream); independent branches get their own
     direct: bool = False         # conv: use sp_conv3x3_direct (bf16 3x3, 32 -> 32 channels) instead of the implicit GEMM; same bits
     dst2: Optional[str] = None   # second output ("htrans": HRNet's transition1 writes the high- and the half-resolution branch in one launch)
+    c0: int = 0                  # conv with SP_CONV_OUT_SLICE: first channel of `dst` this launch writes (a producer of a concat buffer)
 
     def writes(self) -> Tuple[str, ...]:
         return (self.dst,) + ((self.dst2,) if self.dst2 else ())
@@ -131,6 +132,8 @@ class Op:
             return (self.args[2],)
         if self.kind == "upsample_add_n":
             return tuple(self.args[4])
+        if self.kind == "yolo_decode":
+            return tuple(self.args[:2])
         return ()
 
     def reads(self) -> Tuple[str, ...]:
@@ -237,7 +240,7 @@ class Program:
             op.desc.batch = B
             fn = lib.sp_conv3x3_direct if op.direct else lib.sp_conv2d_fwd
             _lib.check(fn(op.desc, P(bufs[op.src]), P(op.w), P(op.scale), P(op.shift),
-                          P(bufs[op.res]) if op.res else None, P(bufs[op.dst]), stream), op.name)
+                          P(bufs[op.res]) if op.res else None, P(bufs[op.dst]) + 4 * op.c0, stream), op.name)
         elif op.kind in ("bb32", "bb64"):
             op.desc.batch = B
             w2, scale2, shift2 = op.args
@@ -316,6 +319,26 @@ class Program:
             h, w, c, f, relu = op.args
             fn = lib.sp_upsample_add_nhwc_bf16 if self.dtype == "bf16" else lib.sp_upsample_add_nhwc
             _lib.check(fn(P(bufs[op.src]), P(bufs[op.res]), P(bufs[op.dst]), B, h, w, c, f, relu, stream), op.name)
+        elif op.kind == "letterbox":
+            g = op.args[0]
+            if not g:
+                raise ValueError("letterbox: set the source geometry first (engine.set_letterbox)")
+            H, W, _ = self.shapes[op.dst]
+            _lib.check(lib.sp_yolo_letterbox(P(bufs[op.src]), B, g["src_h"], g["src_w"], g["new_h"], g["new_w"], g["top"], g["left"], 2 * H, 2 * W,
+                                             _lib.SP_LETTERBOX_FOCUS, P(bufs[op.dst]), stream), op.name)
+        elif op.kind == "focus_nchw":
+            h, w = op.args
+            _lib.check(lib.sp_yolo_focus_nchw(P(bufs[op.src]), B, h, w, P(bufs[op.dst]), stream), op.name)
+        elif op.kind == "spp":
+            h, w, c, ct = op.args
+            _lib.check(lib.sp_yolo_spp_nhwc(P(bufs[op.dst]), B, h, w, c, ct, stream), op.name)
+        elif op.kind == "upsample_slice":
+            h, w, c, s_ct, s0, d_ct = op.args
+            _lib.check(lib.sp_upsample2_slice_nhwc(P(bufs[op.src]) + 4 * s0, s_ct, P(bufs[op.dst]) + 4 * op.c0, d_ct, B, h, w, c, stream), op.name)
+        elif op.kind == "yolo_decode":
+            h1, h2, grid, A, no, a_stride, strides, anchors = op.args
+            _lib.check(lib.sp_yolo_head_decode(P(bufs[op.src]), P(bufs[h1]), P(bufs[h2]), B, (ctypes.c_int32 * 6)(*grid), A, no, a_stride,
+                                               (ctypes.c_float * 3)(*strides), (ctypes.c_float * len(anchors))(*anchors), P(bufs[op.dst]), stream), op.name)
         else:
             raise ValueError(op.kind)
 
@@ -603,13 +626,20 @@ class Program:
         return sum(op.flops for op in self.ops)
 
 
+def _graph_input(x: torch.Tensor) -> torch.Tensor:
+    """A graph's input: fp32 on the GPU, or the uint8 images a program whose first launch reads them takes (BGR crops, detector sources)."""
+    if isinstance(x, torch.Tensor) and x.is_cuda and x.dtype == torch.uint8:
+        return x.contiguous()
+    return _lib.require_cuda_f32(x, "input")
+
+
 class GraphedForward:
     """A Program (+ optional decoder) for one batch shape recorded as a hipGraph (torch.cuda.CUDAGraph is the recorder; every node
     is one of this library's kernels).  `static_input` / `static_trans_inv` are the graph's fixed input buffers: fill them in place
     (or pass tensors to __call__, which copies) and replay; the returned tensors are the graph's fixed outputs."""
 
     def __init__(self, prog: "Program", x: torch.Tensor, decoder=None, trans_inv: Optional[torch.Tensor] = None, warmup: int = 2):
-        x = _lib.require_cuda_f32(x, "input")
+        x = _graph_input(x)
         if decoder is not None and trans_inv is None:
             raise ValueError("capture with a decoder needs trans_inv")
         self.prog, self.decoder = prog, decoder
@@ -645,7 +675,7 @@ class GraphedForward:
         if x is not None and x.data_ptr() != self.static_input.data_ptr():
             if x.shape != self.static_input.shape:
                 raise ValueError(f"graph was captured for input {tuple(self.static_input.shape)}, got {tuple(x.shape)}")
-            self.static_input.copy_(_lib.require_cuda_f32(x, "input"))
+            self.static_input.copy_(_graph_input(x))
         if trans_inv is not None and self.static_trans_inv is not None and trans_inv.data_ptr() != self.static_trans_inv.data_ptr():
             self.static_trans_inv.copy_(_lib.require_cuda_f32(trans_inv, "trans_inv"))
         self.graph.replay()
@@ -863,7 +893,10 @@ class ProgramBuilder:
 
     def conv(self, src: str, weight: torch.Tensor, *, stride: int = 1, pad: int = 0, scale=None, shift=None,
              relu: bool = False, res: Optional[str] = None, pixel_shuffle: bool = False, out_nchw: bool = False,
-             dst: Optional[str] = None, name: str = "conv", groups: int = 1) -> str:
+             dst: Optional[str] = None, name: str = "conv", groups: int = 1, hardswish: bool = False,
+             out_slice: Optional[Tuple[str, int]] = None) -> str:
+        """`hardswish`: y = hardswish(bn(conv)) (+ res after it; SP_CONV_HARDSWISH).  `out_slice` = (buffer, c0): write channels [c0, c0 + O) of a
+        buffer made by `buffer()` (SP_CONV_OUT_SLICE: the producers of a concat fill their slices, nothing is copied)."""
         h, w, c_buf = self.p.shapes[src]
         O, I, kh, kw = weight.shape
         paired = False
@@ -920,12 +953,23 @@ class ProgramBuilder:
             flags |= SP_CONV_OUT_NCHW
         if self.bf16:
             flags |= SP_CONV_BF16
+        if hardswish:
+            flags |= SP_CONV_HARDSWISH
+        c0 = 0
+        if out_slice is not None:
+            dst, c0 = out_slice
+            sh_, sw_, sc_ = self.p.shapes[dst]
+            if (sh_, sw_) != (gh, gw) or c0 % 4 or c0 + O > sc_ or pixel_shuffle or out_nchw or res is not None:
+                raise ValueError(f"{name}: cannot write channels [{c0}, {c0 + O}) of {dst} {self.p.shapes[dst]} from a {gh}x{gw} launch")
+            d.out_c = sc_
+            flags |= SP_CONV_OUT_SLICE
         d.flags = flags
         if panel:
             d.c_in_group, d.tile_m, d.tile_n = panel, 128, panel
         dst = dst or self._fresh(name)
-        self.p.shapes[dst] = (d.out_h, d.out_w, d.out_c)
-        op = Op("conv", src, dst, res=res, desc=d, w=packed, scale=scale, shift=shift, name=name, flops=2 * gh * gw * O * I * kh * kw)
+        if out_slice is None:
+            self.p.shapes[dst] = (d.out_h, d.out_w, d.out_c)
+        op = Op("conv", src, dst, res=res, desc=d, w=packed, scale=scale, shift=shift, name=name, flops=2 * gh * gw * O * I * kh * kw, c0=c0)
         # small-channel 3x3 layers (HRNet's 32-channel branch): the direct kernel is the default, the tuner may still pick a GEMM tile
         op.direct = bool(self.bf16 and _lib.lib().sp_conv3x3_direct_ok(d))
         self._add(op)
@@ -1055,6 +1099,24 @@ class ProgramBuilder:
         self._add(Op("upsample_add", src, dst, res=base, args=(h, w, c, factor, int(relu)), name="upsample_add"))
         return dst
 
+
+    def buffer(self, stem: str, h: int, w: int, c: int) -> str:
+        """A buffer written in channel slices by several producers (a torch.cat); the planner keeps it from its first writer to its last reader."""
+        name = self._fresh(stem)
+        self.p.shapes[name] = (h, w, c)
+        return name
+
+    def spp(self, buf: str, c: int) -> None:
+        """SPP's three max pools (5 / 9 / 13, stride 1): slice 0 of `buf` -> slices 1..3 (sp_yolo_spp_nhwc)."""
+        h, w, ct = self.p.shapes[buf]
+        self._add(Op("spp", buf, buf, args=(h, w, c, ct), name="spp.pools"))
+
+    def upsample_slice(self, src: str, s0: int, c: int, dst: str, d0: int) -> None:
+        """Nearest x2 from channels [s0, s0 + c) of `src` into channels [d0, d0 + c) of `dst` (sp_upsample2_slice_nhwc)."""
+        h, w, sct = self.p.shapes[src]
+        H, W, dct = self.p.shapes[dst]
+        assert (H, W) == (2 * h, 2 * w) and s0 + c <= sct and d0 + c <= dct
+        self._add(Op("upsample_slice", src, dst, args=(h, w, c, sct, s0, dct), name="upsample", c0=d0))
 
     def upsample_add_n(self, base: str, terms: List[Tuple[str, int]], relu: bool = False) -> str:
         """dst = [relu](((base + up(t0, f0)) + up(t1, f1)) + up(t2, f2)): every term of an HRNet fuse output that is added AFTER the
@@ -1321,3 +1383,152 @@ def hrnet_program(sd: Dict[str, torch.Tensor], cfg: dict, in_h: int = 256, in_w:
     hh, ww, _ = b.p.shapes["heat"]
     b.p.out_shape = (sd["final_layer.weight"].shape[0], hh, ww)
     return b.p
+
+
+# ------------------------------------------------------------------------------------------------
+# YOLOv5 person detector (detector/nets/yolov5.py, detector/nets/commons.py), fp32 inference
+# ------------------------------------------------------------------------------------------------
+YOLO_STRIDES = (8.0, 16.0, 32.0)
+
+
+def _cbr(b: ProgramBuilder, sd, x: str, p: str, k: int, s: int, res: Optional[str] = None, out: Optional[Tuple[str, int]] = None) -> str:
+    """CBR (commons.py:32): conv (no bias) -> BatchNorm -> Hardswish, one launch; `res` is added after the activation (BottleNeck, :74-78)."""
+    sc, sh = _bn(b, sd, p + ".bn")
+    return b.conv(x, sd[p + ".conv.weight"], stride=s, pad=(k - 1) // 2, scale=sc, shift=sh, hardswish=True, res=res, out_slice=out, name=p)
+
+
+def _csp(b: ProgramBuilder, sd, x: str, p: str, shortcut: bool, also: Optional[Tuple[str, int]] = None) -> str:
+    """BottleNeckCSP (commons.py:80-99): y = conv3(hardswish(bn(cat[conv1_n(conv1_s(conv1_0(x))), conv2_0(x)]))).  The BatchNorm over the concat
+    is split between its two producers - conv1_n's epilogue applies channels [0, c_), conv2_0's channels [c_, 2c_) - which write their halves
+    of one buffer.  `also`: conv3 runs a second time into that slice of a later concat (the tensor is also a convolution's input elsewhere)."""
+    inner = sd[p + ".conv1_0.conv.weight"].shape[0]
+    h, w, _ = b.p.shapes[x]
+    cat = b.buffer("csp", h, w, 2 * inner)
+    t = _cbr(b, sd, x, p + ".conv1_0", 1, 1)
+    i = 0
+    while f"{p}.conv1_s.{i}.conv1.conv.weight" in sd:
+        q = f"{p}.conv1_s.{i}"
+        u = _cbr(b, sd, t, q + ".conv1", 1, 1)
+        t = _cbr(b, sd, u, q + ".conv2", 3, 1, res=t if shortcut else None)
+        i += 1
+    sc, sh = _bn(b, sd, p + ".bn")
+    b.conv(t, sd[p + ".conv1_n.weight"], scale=sc[:inner].clone(), shift=sh[:inner].clone(), hardswish=True, out_slice=(cat, 0), name=p + ".conv1_n")
+    b.conv(x, sd[p + ".conv2_0.weight"], scale=sc[inner:].clone(), shift=sh[inner:].clone(), hardswish=True, out_slice=(cat, inner), name=p + ".conv2_0")
+    y = _cbr(b, sd, cat, p + ".conv3", 1, 1)
+    if also is not None:
+        _cbr(b, sd, cat, p + ".conv3", 1, 1, out=also)
+    return y
+
+
+def _spp(b: ProgramBuilder, sd, x: str, p: str) -> str:
+    """SPP (commons.py:124-136): conv1 writes slice 0 of the concat, one launch pools it into slices 1..3, conv2 reads the whole buffer."""
+    inner = sd[p + ".conv1.conv.weight"].shape[0]
+    h, w, _ = b.p.shapes[x]
+    cat = b.buffer("spp", h, w, 4 * inner)
+    _cbr(b, sd, x, p + ".conv1", 1, 1, out=(cat, 0))
+    b.spp(cat, inner)
+    return _cbr(b, sd, cat, p + ".conv2", 1, 1)
+
+
+def yolo_head_columns(no: int, slice_idx: int) -> List[int]:
+    """Output columns of one anchor: all `no` (slice_idx < 0), or (x, y, w, h, obj, class slice_idx) - YOLOv5Detector's head cut (:196-209)."""
+    return list(range(no)) if slice_idx < 0 else [0, 1, 2, 3, 4, 5 + slice_idx]
+
+
+def yolo_anchor_stride(no_out: int) -> int:
+    """Columns per anchor in the packed head output: `no_out` rounded up to whole 16-byte chunks (the decoder skips the padding)."""
+    return _round_up(no_out, 4)
+
+
+def _head_conv(w: torch.Tensor, bias: torch.Tensor, anchors: int, no: int, cols: List[int]) -> Tuple[torch.Tensor, torch.Tensor]:
+    """Head conv weight [A * no, C, 1, 1] / bias -> the selected columns of every anchor at a stride of yolo_anchor_stride (zero rows between)."""
+    a_stride = yolo_anchor_stride(len(cols))
+    C = w.shape[1]
+    wv, bv = w.detach().reshape(anchors, no, C), bias.detach().reshape(anchors, no)
+    wp = torch.zeros((anchors, a_stride, C), dtype=w.dtype, device=w.device)
+    bp = torch.zeros((anchors, a_stride), dtype=bias.dtype, device=bias.device)
+    idx = torch.tensor(cols, device=w.device)
+    wp[:, :len(cols)] = wv.index_select(1, idx)
+    bp[:, :len(cols)] = bv.index_select(1, idx)
+    return wp.reshape(anchors * a_stride, C, 1, 1), bp.reshape(-1).contiguous()
+
+
+def yolov5_program(sd: Dict[str, torch.Tensor], num_cls: int = 80, in_h: int = 640, in_w: int = 640, slice_idx: int = -1,
+                   strides=YOLO_STRIDES, source: str = "u8", packer=None) -> Program:
+    """Lower a reference-layout YOLOv5 state_dict (any scale: depths and widths come from the tensors) into an fp32 Program for letterboxed
+    inputs of in_h x in_w (multiples of 32).  source "u8": the input is the uint8 BGR source image [B, h, w, 3] and the first launch letterboxes
+    it (set its geometry with set_letterbox); "nchw": the input is YOLOv5.forward's fp32 RGB tensor [B, 3, in_h, in_w].  The output `pred` is
+    the eval-mode head output [B, N, no] (no = num_cls + 5, or 6 with slice_idx >= 0: YOLOv5Detector's person-only head)."""
+    if in_h % 32 or in_w % 32:
+        raise ValueError(f"letterboxed input {in_h}x{in_w}: multiples of 32 expected")
+    b = ProgramBuilder(in_h, in_w, "fp32", packer)
+    f = b._fresh("focus")
+    b.p.shapes[f] = (in_h // 2, in_w // 2, 12)
+    if source == "u8":
+        b._add(Op("letterbox", "input", f, args=({},), name="letterbox+focus"))
+    elif source == "nchw":
+        b._add(Op("focus_nchw", "input", f, args=(in_h, in_w), name="focus"))
+    else:
+        raise ValueError(source)
+    bb = "backbones"
+    x = _cbr(b, sd, f, bb + ".stem.conv", 3, 1)
+    x = _cbr(b, sd, x, bb + ".layer1.0", 3, 2)
+    x = _csp(b, sd, x, bb + ".layer1.1", True)
+    x = _cbr(b, sd, x, bb + ".layer2.0", 3, 2)
+    c3ch = sd[bb + ".layer2.1.conv3.conv.weight"].shape[0]
+    c4ch = sd[bb + ".layer3.1.conv3.conv.weight"].shape[0]
+    h3, w3 = b.p.shapes[x][:2]
+    f3 = b.buffer("cat_f3", h3, w3, 2 * c3ch)                   # cat[up(latent_c4), c3]      (yolov5.py:97)
+    f4 = b.buffer("cat_f4", h3 // 2, w3 // 2, 2 * c4ch)         # cat[up(latent_c5), c4]      (:94)
+    g4 = b.buffer("cat_g4", h3 // 2, w3 // 2, 2 * c3ch)         # cat[c3_c4, latent_c4]       (:100)
+    g5 = b.buffer("cat_g5", h3 // 4, w3 // 4, 2 * c4ch)         # cat[c4_c5, latent_c5]       (:102)
+    # c3 and c4 are concat members AND the input of the next stage's stride-2 conv.  The implicit GEMM reads its input with a pixel stride of
+    # c_in (sp_conv_desc has no input channel stride, and its 31 ints are ABI), so it cannot read them out of the concat buffer: their conv3
+    # runs a second time into the concat slice instead (no copy, but 2 x 2*h*w*c^2 extra FLOPs: 0.42 of 17.13 GFLOP at s 640x640, 2.4 %).
+    c3 = _csp(b, sd, x, bb + ".layer2.1", True, also=(f3, c3ch))
+    x = _cbr(b, sd, c3, bb + ".layer3.0", 3, 2)
+    c4 = _csp(b, sd, x, bb + ".layer3.1", True, also=(f4, c4ch))
+    x = _cbr(b, sd, c4, bb + ".layer4.0", 3, 2)
+    x = _spp(b, sd, x, bb + ".layer4.1")
+    c5 = _csp(b, sd, x, bb + ".layer4.2", False)
+    nk = "neck"
+    _cbr(b, sd, c5, nk + ".latent_c5", 1, 1, out=(g5, c4ch))
+    b.upsample_slice(g5, c4ch, c4ch, f4, 0)
+    x = _csp(b, sd, f4, nk + ".c4_fuse", False)
+    _cbr(b, sd, x, nk + ".latent_c4", 1, 1, out=(g4, c3ch))
+    b.upsample_slice(g4, c3ch, c3ch, f3, 0)
+    p3 = _csp(b, sd, f3, nk + ".c3_out", False)
+    _cbr(b, sd, p3, nk + ".c3_c4", 3, 2, out=(g4, 0))
+    p4 = _csp(b, sd, g4, nk + ".c4_out", False)
+    _cbr(b, sd, p4, nk + ".c4_c5", 3, 2, out=(g5, 0))
+    p5 = _csp(b, sd, g5, nk + ".c5_out", False)
+    # head (yolov5.py:134-149): 1x1 conv + bias per level, then ONE decode launch over the three levels
+    anchor_grid = sd["head.anchor_grid"].detach().float().cpu().reshape(3, -1, 2)
+    A = anchor_grid.shape[1]
+    no = num_cls + 5
+    cols = yolo_head_columns(no, slice_idx)
+    outs, grid = [], []
+    for i, src in enumerate((p3, p4, p5)):
+        wp, bp = _head_conv(sd[f"head.heads.{i}.weight"], sd[f"head.heads.{i}.bias"], A, no, cols)
+        outs.append(b.conv(src, wp, shift=b.packer.bias(bp), name=f"head.heads.{i}"))
+        grid += list(b.p.shapes[src][:2])
+    N = sum(A * grid[2 * i] * grid[2 * i + 1] for i in range(3))
+    b.p.shapes["pred"] = (N, len(cols), 1)
+    b._add(Op("yolo_decode", outs[0], "pred", args=(outs[1], outs[2], tuple(grid), A, len(cols), yolo_anchor_stride(len(cols)),
+                                                    tuple(float(v) for v in strides), tuple(anchor_grid.reshape(-1).tolist())), name="head.decode"))
+    b.p.out_name = "pred"
+    b.p.out_shape = (N, len(cols))
+    return b.p
+
+
+def set_letterbox(prog: Program, src_h: int, src_w: int, new_h: int, new_w: int, top: int, left: int) -> None:
+    """Source geometry of a yolov5_program(source="u8"): the next run letterboxes [B, src_h, src_w, 3] images (resized to new_h x new_w at
+    (top, left)).  A graph captured after this call keeps the geometry it was captured with."""
+    H, W = prog.shapes["input"][:2]
+    if not (top >= 0 and left >= 0 and top + new_h <= H and left + new_w <= W):
+        raise ValueError(f"letterbox {src_h}x{src_w} -> {new_h}x{new_w} at ({top}, {left}) does not fit {H}x{W}")
+    for op in prog.ops:
+        if op.kind == "letterbox":
+            op.args[0].update(src_h=src_h, src_w=src_w, new_h=new_h, new_w=new_w, top=top, left=left)
+            return
+    raise ValueError("program has no letterbox launch (source='u8')")
