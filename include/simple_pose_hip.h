@@ -663,6 +663,37 @@ int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, float conf_thr
 /* clip_coords + the un-letterbox of single_predict (yolov5_detector.py:233-237) on `rows` rows of 6 floats (in place):
  * x1, x2 clamped to [0, img_w], y1, y2 to [0, img_h], then x = (x - left) / ratio, y = (y - top) / ratio */
 int sp_yolo_boxes_to_source(float* det, int rows, float img_h, float img_w, float left, float top, float ratio, void* stream);
+/* sp_yolo_nms without the two host reads: the same workspace and the same three kernels; counts is DEVICE int32 [B], and DEVICE int32
+ * status[B] receives bit 0 = "more than SP_YOLO_NMS_MAX_CANDIDATES candidates" (what sp_yolo_nms reports as SP_EINVAL; such an image gets
+ * count 0, its neighbours are not affected).  The rank kernel runs on the fixed grid the cap implies; workgroups beyond an image's candidate
+ * count return at once.  out[b, :counts[b]] and counts equal sp_yolo_nms's bit for bit; rows from counts[b] on are not written.  Plain launches
+ * only: no copy, no synchronisation, safe inside a stream capture. */
+int sp_yolo_nms_device(const float* pred, int batch, int n_rows, int no, float conf_thresh, float iou_thresh, int merge, int multi_label,
+                       int agnostic, int max_det, void* workspace, int64_t workspace_bytes, float* out, int32_t* counts, int32_t* status,
+                       void* stream);
+
+/* ---- top-down pipeline: detections -> crop geometry -> crops, without a host round trip ----------------------------------------------
+ * sp_topdown_plan: BasicTransform.__call__ (datasets/naive_data.py:33-56) for the selected rows of a batch of detections, on the device.
+ * det fp32 [B, max_det, 6] (x1, y1, x2, y2, score, cls) in SOURCE pixels, counts int32 [B] (rows valid per image).  A row is selected when
+ * cls == keep_cls (keep_cls < 0: every row) and score >= min_score.  Selected rows fill `capacity` (1 .. 2048) slots in (image, row)
+ * order; rows that do not fit are dropped from the END of that order and counted in dropped[b].  Every output is DEVICE memory:
+ *   seg int32 [B+1]           persons of image b are slots seg[b] .. seg[b+1]-1
+ *   src_index int32 [capacity] image of the slot (-1: dead slot)
+ *   m_inv double [capacity,6] dst -> src map of the in_w x in_h crop: get_affine_transform(center, scale, 0, (in_w, in_h))[0] inverted as
+ *                             cv::warpAffine / sp_warp_affine_u8c3 invert it
+ *   trans_inv fp32 [capacity,2,3]  heat-map (hm_w x hm_h) -> image, what the decoders take
+ *   center, scale fp32 [capacity,2]; area double [capacity] (the float32 product scale_w * scale_h, widened); box_score double [capacity]
+ *   (the float32 confidence, widened); box fp32 [capacity,5] (x1, y1, x2, y2, score of the row); dropped int32 [B].
+ * Dead slots (>= seg[B]) are written as zeros (src_index -1).  float32 box arithmetic and float64 Cramer solves in the host functions'
+ * operation order (commons/joint_utils.py), contraction off: every value has the host's bits. */
+int sp_topdown_plan(const float* det, const int32_t* counts, int batch, int max_det, int keep_cls, float min_score, int capacity, int in_w,
+                    int in_h, int hm_w, int hm_h, int32_t* seg, int32_t* src_index, double* m_inv, float* trans_inv, float* center,
+                    float* scale, double* area, double* box_score, float* box, int32_t* dropped, void* stream);
+/* The crops of a plan: src uint8 BGR [batch, src_h, src_w, 3]; m_inv, src_index, seg as sp_topdown_plan wrote them (DEVICE memory);
+ * dst uint8 BGR [capacity, out_h, out_w, 3].  Live slots hold sp_warp_affine_u8c3's pixels bit for bit (one pixel function for every warp
+ * kernel); dead slots are written as zeros, so that a forward over all `capacity` crops never reads undefined memory. */
+int sp_warp_affine_plan_u8c3(const unsigned char* src, int batch, int src_h, int src_w, const double* m_inv, const int32_t* src_index,
+                             const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream);
 
 #ifdef __cplusplus
 }

@@ -177,6 +177,9 @@ SYMBOLS = {
     "sp_yolo_nms_workspace": (c_int, [c_int, ctypes.POINTER(c_int64)]),
     "sp_yolo_nms": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, _P, c_int64, _P, ctypes.POINTER(c_int32), ctypes.POINTER(c_int32), _P]),
     "sp_yolo_boxes_to_source": (c_int, [_P, c_int, c_float, c_float, c_float, c_float, c_float, _P]),
+    "sp_yolo_nms_device": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P]),
+    "sp_topdown_plan": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sp_warp_affine_plan_u8c3": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
 }
 
 _lib = None

@@ -213,26 +213,10 @@ __device__ __forceinline__ float box_iou1(float4 a, float4 b) {
     return inter / (area_a + area_b - inter);
 }
 
-// exclusive prefix sum over the 256 threads of the block; returns the prefix, `total` = the block sum
-__device__ __forceinline__ int block_scan(int v, int* lds, int& total) {
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int x = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int y = __shfl_up(x, o, 64);
-        if (lane >= o) x += y;
-    }
-    if (lane == 63) lds[wave] = x;
-    __syncthreads();
-    int base = 0;
-    for (int w = 0; w < wave; ++w) base += lds[w];
-    total = lds[0] + lds[1] + lds[2] + lds[3];
-    __syncthreads();
-    return base + x - v;
-}
-
-// candidates of image blockIdx.x in (row, class) order; counts all, stores the first CAP
-__global__ __launch_bounds__(NT) void nms_candidates_kernel(const float* __restrict__ pred, int N, int no, float conf, int multi, NmsWs ws) {
+// candidates of image blockIdx.x in (row, class) order; counts all, stores the first CAP.  `status` (sp_yolo_nms_device; else null): the
+// overflow is decided here instead of on the host - bit 0 set and the image's candidate count forced to 0
+__global__ __launch_bounds__(NT) void nms_candidates_kernel(const float* __restrict__ pred, int N, int no, float conf, int multi, NmsWs ws,
+                                                            int* __restrict__ status) {
     __shared__ int lds[4];
     const int b = blockIdx.x;
     const float* P = pred + (size_t)b * N * no;
@@ -260,7 +244,7 @@ __global__ __launch_bounds__(NT) void nms_candidates_kernel(const float* __restr
             }
         }
         int total;
-        int k = base + block_scan(cnt, lds, total);
+        int k = base + sp_block_scan256(cnt, lds, total);
         if (cnt) {
             const float* p = P + (size_t)r * no;
             float4 bx;
@@ -283,7 +267,13 @@ __global__ __launch_bounds__(NT) void nms_candidates_kernel(const float* __restr
         }
         base += total;
     }
-    if (threadIdx.x == 0) ws.n_cand[b] = base;
+    if (threadIdx.x == 0) {
+        if (status) {
+            status[b] = base > CAP ? 1 : 0;
+            if (base > CAP) base = 0;
+        }
+        ws.n_cand[b] = base;
+    }
 }
 
 // descending score, ties to the lower candidate index: order[rank(i)] = i
@@ -311,7 +301,8 @@ __global__ __launch_bounds__(NT) void nms_rank_kernel(NmsWs ws) {
 }
 
 // greedy scan (torchvision.ops.nms order, truncated at max_det), merge, redundancy filter, output
-__global__ __launch_bounds__(NT) void nms_select_kernel(NmsWs ws, float iou_thr, int merge, int agnostic, int max_det, float* __restrict__ out) {
+__global__ __launch_bounds__(NT) void nms_select_kernel(NmsWs ws, float iou_thr, int merge, int agnostic, int max_det, float* __restrict__ out,
+                                                        int* __restrict__ counts_dev) {
     __shared__ float4 kb[SP_YOLO_NMS_MAX_DET];       // kept boxes (class-offset)
     __shared__ int kidx[SP_YOLO_NMS_MAX_DET];
     __shared__ float4 cb[NT];
@@ -406,6 +397,7 @@ __global__ __launch_bounds__(NT) void nms_select_kernel(NmsWs ws, float iou_thr,
             ++r;
         }
         ws.n_out[b] = r;
+        if (counts_dev) counts_dev[b] = r;                  // sp_yolo_nms_device: the result count stays on the device
     }
 }
 
@@ -526,7 +518,8 @@ extern "C" int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, flo
     SP_REQUIRE(workspace_bytes >= need, "sp_yolo_nms: workspace %lld bytes, need %lld (sp_yolo_nms_workspace)", (long long)workspace_bytes,
                (long long)need);
     hipStream_t s = (hipStream_t)stream;
-    hipLaunchKernelGGL(nms_candidates_kernel, dim3(batch), dim3(NT), 0, s, pred, n_rows, no, conf_thresh, multi_label ? 1 : 0, ws);
+    hipLaunchKernelGGL(nms_candidates_kernel, dim3(batch), dim3(NT), 0, s, pred, n_rows, no, conf_thresh, multi_label ? 1 : 0, ws,
+                       (int*)nullptr);
     int rc = sp_check_launch("nms_candidates_kernel");
     if (rc != SP_OK) return rc;
     if (hipMemcpyAsync(counts, ws.n_cand, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
@@ -545,7 +538,8 @@ extern "C" int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, flo
         rc = sp_check_launch("nms_rank_kernel");
         if (rc != SP_OK) return rc;
     }
-    hipLaunchKernelGGL(nms_select_kernel, dim3(batch), dim3(NT), 0, s, ws, iou_thresh, merge ? 1 : 0, agnostic ? 1 : 0, max_det, out);
+    hipLaunchKernelGGL(nms_select_kernel, dim3(batch), dim3(NT), 0, s, ws, iou_thresh, merge ? 1 : 0, agnostic ? 1 : 0, max_det, out,
+                       (int*)nullptr);
     rc = sp_check_launch("nms_select_kernel");
     if (rc != SP_OK) return rc;
     if (hipMemcpyAsync(counts, ws.n_out, (size_t)batch * sizeof(int), hipMemcpyDeviceToHost, s) != hipSuccess || hipStreamSynchronize(s) != hipSuccess) {
@@ -553,6 +547,28 @@ extern "C" int sp_yolo_nms(const float* pred, int batch, int n_rows, int no, flo
         return SP_ELAUNCH;
     }
     return SP_OK;
+}
+
+// sp_yolo_nms with every decision left on the device: nothing here reads a count, so the three launches can be captured
+extern "C" int sp_yolo_nms_device(const float* pred, int batch, int n_rows, int no, float conf_thresh, float iou_thresh, int merge, int multi_label,
+                                  int agnostic, int max_det, void* workspace, int64_t workspace_bytes, float* out, int32_t* counts, int32_t* status,
+                                  void* stream) {
+    SP_REQUIRE(pred && workspace && out && counts && status, "sp_yolo_nms_device: null pointer");
+    SP_REQUIRE(batch > 0 && n_rows > 0 && no >= 6 && max_det > 0 && max_det <= SP_YOLO_NMS_MAX_DET && (long long)batch * n_rows * no < (1ll << 31),
+               "sp_yolo_nms_device: batch %d, rows %d, no %d (>= 6), max_det %d (1..%d)", batch, n_rows, no, max_det, SP_YOLO_NMS_MAX_DET);
+    NmsWs ws;
+    const int64_t need = nms_ws_layout(batch, &ws, workspace);
+    SP_REQUIRE(workspace_bytes >= need, "sp_yolo_nms_device: workspace %lld bytes, need %lld (sp_yolo_nms_workspace)", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(nms_candidates_kernel, dim3(batch), dim3(NT), 0, s, pred, n_rows, no, conf_thresh, multi_label ? 1 : 0, ws, status);
+    int rc = sp_check_launch("nms_candidates_kernel");
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(nms_rank_kernel, dim3(CAP / NT, batch), dim3(NT), 0, s, ws);      // blocks beyond n_cand[b] return at once
+    rc = sp_check_launch("nms_rank_kernel");
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(nms_select_kernel, dim3(batch), dim3(NT), 0, s, ws, iou_thresh, merge ? 1 : 0, agnostic ? 1 : 0, max_det, out, counts);
+    return sp_check_launch("nms_select_kernel");
 }
 
 extern "C" int sp_yolo_boxes_to_source(float* det, int rows, float img_h, float img_w, float left, float top, float ratio, void* stream) {

@@ -50,3 +50,36 @@ __device__ __forceinline__ void sp_wave_argmax(float& v, int& i) {
         if (sp_better(ov, oi, v, i)) { v = ov; i = oi; }
     }
 }
+
+// exclusive prefix sum over the 256 threads of a block (four waves); returns the prefix, `total` = the block sum.  lds: 4 ints.
+__device__ __forceinline__ int sp_block_scan256(int v, int* lds, int& total) {
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int x = v;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int y = __shfl_up(x, o, 64);
+        if (lane >= o) x += y;
+    }
+    if (lane == 63) lds[wave] = x;
+    __syncthreads();
+    int base = 0;
+    for (int w = 0; w < wave; ++w) base += lds[w];
+    total = lds[0] + lds[1] + lds[2] + lds[3];
+    __syncthreads();
+    return base + x - v;
+}
+
+// cv::warpAffine without WARP_INVERSE_MAP: the forward 2x3 map inverted in double, this way.  ONE statement of it for the host callers
+// (sp_warp_affine_*) and the device caller (sp_topdown_plan), whose maps must agree bit for bit: contraction is off inside.
+__host__ __device__ inline void sp_invert_affine(const double* fwd, double* inv) {
+#pragma clang fp contract(off)
+    double M[6];
+    for (int i = 0; i < 6; ++i) M[i] = fwd[i];
+    double D = M[0] * M[4] - M[1] * M[3];
+    D = D != 0 ? 1. / D : 0;
+    const double A11 = M[4] * D, A22 = M[0] * D;
+    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
+    const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
+    M[2] = b1; M[5] = b2;
+    for (int i = 0; i < 6; ++i) inv[i] = M[i];
+}

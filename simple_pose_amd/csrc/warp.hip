@@ -6,7 +6,11 @@
 // HBM-bound gather: 3 B written per output pixel, <= 12 B read (neighbouring lanes share lines).
 // The training-side batch (sp_warp_affine_batch_u8c3_to_nchw_f32: RefineSimpleTransform's warp + horizontal flip + the collate
 // normalisation, one source image per sample) runs the same per-pixel function and writes 12 B of fp32 (+ 3 B of optional crop).
+// The top-down estimator's crops (sp_warp_affine_plan_u8c3) take their maps and source indices from DEVICE memory (sp_topdown_plan wrote
+// them), so that the launch can sit in a captured graph; same per-pixel function, dead slots zero-filled.
 #include "sp_common.h"
+
+#include <stdint.h>
 
 #pragma clang fp contract(off)
 
@@ -60,6 +64,39 @@ __global__ __launch_bounds__(256) void warp_affine_u8c3_kernel(const unsigned ch
     }
 }
 
+// The crops of a device-side plan (sp_topdown_plan): slot blockIdx.y reads its map and its source image index from device memory, so
+// the launch needs nothing from the host.  Slots from seg[B] on (and any slot whose index is not an image of the batch) are zero-filled.
+// Per live crop: out_h * out_w * 3 B written, the 48 B map read, and the box's footprint of the source read once from HBM / L2.
+__global__ __launch_bounds__(256) void warp_affine_plan_u8c3_kernel(const unsigned char* __restrict__ src, int B, int H, int W,
+                                                                    const double* __restrict__ m_inv, const int* __restrict__ src_index,
+                                                                    const int* __restrict__ seg, unsigned char* __restrict__ dst, int oh, int ow) {
+    const int n = blockIdx.y;
+    const int b = src_index[n];
+    const bool live = n < seg[B] && b >= 0 && b < B;
+    unsigned char* D = dst + (size_t)n * oh * ow * 3;
+    if (!live) {                                              // 16-byte stores where the slot allows it (256 x 192 x 3 B slots do)
+        const size_t bytes = (size_t)oh * ow * 3;
+        if ((reinterpret_cast<uintptr_t>(D) & 15) == 0 && bytes % 16 == 0) {
+            uint4* D4 = reinterpret_cast<uint4*>(D);
+            for (size_t i = blockIdx.x * 256 + threadIdx.x; i < bytes / 16; i += (size_t)gridDim.x * 256) D4[i] = make_uint4(0u, 0u, 0u, 0u);
+        } else {
+            for (size_t i = blockIdx.x * 256 + threadIdx.x; i < bytes; i += (size_t)gridDim.x * 256) D[i] = 0;
+        }
+        return;
+    }
+    double M[6];
+#pragma unroll
+    for (int i = 0; i < 6; ++i) M[i] = m_inv[(size_t)n * 6 + i];
+    const unsigned char* S = src + (size_t)b * H * W * 3;
+    for (int i = blockIdx.x * 256 + threadIdx.x; i < oh * ow; i += gridDim.x * 256) {
+        const int y = i / ow, x = i - y * ow;
+        unsigned char v[3];
+        warp_sample_u8c3(S, H, W, false, M, x, y, v);
+        unsigned char* d = D + (size_t)i * 3;
+        d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
+    }
+}
+
 // Training batches (RefineSimpleTransform + MSCOCO.collate_fn): every sample has its own source image, size, flip flag and map.
 struct WarpSample {
     const unsigned char* src;
@@ -96,19 +133,6 @@ __global__ __launch_bounds__(256) void warp_affine_batch_nchw_kernel(const WarpS
 
 }  // namespace
 
-// cv::warpAffine without WARP_INVERSE_MAP: the forward map inverted in double, this way
-static void invert_affine(const double* fwd, double* inv) {
-    double M[6];
-    for (int i = 0; i < 6; ++i) M[i] = fwd[i];
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
-    for (int i = 0; i < 6; ++i) inv[i] = M[i];
-}
-
 extern "C" int sp_warp_affine_u8c3(const unsigned char* src, int src_h, int src_w, const double* m_fwd_host, int crops, unsigned char* dst,
                                    int out_h, int out_w, void* stream) {
     SP_REQUIRE(src && m_fwd_host && dst, "sp_warp_affine_u8c3: null pointer");
@@ -118,11 +142,24 @@ extern "C" int sp_warp_affine_u8c3(const unsigned char* src, int src_h, int src_
     for (int c0 = 0; c0 < crops; c0 += WARP_BATCH) {
         const int nb = crops - c0 < WARP_BATCH ? crops - c0 : WARP_BATCH;
         WarpMaps maps;
-        for (int n = 0; n < nb; ++n) invert_affine(m_fwd_host + (size_t)(c0 + n) * 6, maps.m[n]);
+        for (int n = 0; n < nb; ++n) sp_invert_affine(m_fwd_host + (size_t)(c0 + n) * 6, maps.m[n]);
         hipLaunchKernelGGL(warp_affine_u8c3_kernel, dim3(blocks, nb), dim3(256), 0, (hipStream_t)stream, src, src_h, src_w, maps,
                            dst + (size_t)c0 * out_h * out_w * 3, out_h, out_w);
     }
     return sp_check_launch("warp_affine_u8c3_kernel");
+}
+
+extern "C" int sp_warp_affine_plan_u8c3(const unsigned char* src, int batch, int src_h, int src_w, const double* m_inv, const int32_t* src_index,
+                                        const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream) {
+    SP_REQUIRE(src && m_inv && src_index && seg && dst, "sp_warp_affine_plan_u8c3: null pointer");
+    SP_REQUIRE(batch > 0 && src_h > 0 && src_w > 0 && src_h <= 32767 && src_w <= 32767 && out_h > 0 && out_w > 0 &&
+                   (long long)out_h * out_w < (1ll << 28),
+               "sp_warp_affine_plan_u8c3: bad shape batch=%d src %dx%d out %dx%d", batch, src_h, src_w, out_h, out_w);
+    SP_REQUIRE(capacity >= 1 && capacity <= 2048, "sp_warp_affine_plan_u8c3: capacity %d (1..2048)", capacity);
+    const int blocks = sp_ceil_div((long long)out_h * out_w, 256 * 4);
+    hipLaunchKernelGGL(warp_affine_plan_u8c3_kernel, dim3(blocks, capacity), dim3(256), 0, (hipStream_t)stream, src, batch, src_h, src_w, m_inv,
+                       src_index, seg, dst, out_h, out_w);
+    return sp_check_launch("warp_affine_plan_u8c3_kernel");
 }
 
 extern "C" int sp_warp_affine_batch_u8c3_to_nchw_f32(const unsigned char* const* srcs_host, const int* src_hw_host, const int* flip_host,
@@ -147,7 +184,7 @@ extern "C" int sp_warp_affine_batch_u8c3_to_nchw_f32(const unsigned char* const*
             d.H = src_hw_host[2 * (c0 + n)];
             d.W = src_hw_host[2 * (c0 + n) + 1];
             d.flip = flip_host ? (flip_host[c0 + n] != 0) : 0;
-            invert_affine(m_fwd_host + (size_t)(c0 + n) * 6, d.m);
+            sp_invert_affine(m_fwd_host + (size_t)(c0 + n) * 6, d.m);
         }
         for (int n = nb; n < WARP_BATCH; ++n) s.s[n] = WarpSample{};   // unused slots: defined kernel arguments
         hipLaunchKernelGGL(warp_affine_batch_nchw_kernel, dim3(blocks, nb), dim3(256), 0, (hipStream_t)stream, s, out + (size_t)c0 * 3 * hw,

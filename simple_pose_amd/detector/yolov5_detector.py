@@ -53,6 +53,8 @@ def boxes_to_source(det: torch.Tensor, img_hw: Tuple[int, int], left: float = 0.
     if not (det.is_cuda and det.dtype == torch.float32 and det.is_contiguous() and det.shape[-1] == 6):
         raise HipLibraryError("boxes_to_source: expected a contiguous CUDA fp32 tensor [..., 6]")
     rows = det.numel() // 6
+    if rows == 0:                       # candidates but no box left (merge-NMS's redundancy filter): an empty view has no pointer to pass
+        return det
     _lib.check(_lib.lib().sp_yolo_boxes_to_source(_lib.ptr(det), rows, float(img_hw[0]), float(img_hw[1]), float(left), float(top), float(ratio),
                                                   _lib.current_stream(det.device)), "sp_yolo_boxes_to_source")
     return det

@@ -195,6 +195,11 @@ class Program:
         self._pools[key] = bufs
         return bufs
 
+    def pool_for(self, batch: int, device) -> Dict[str, torch.Tensor]:
+        """The activation pool a run of this batch shape on `device` uses (allocated if need be).  A captured graph keeps the returned
+        dict: its nodes hold raw pointers into these tensors, whatever `_alloc` evicts from its table later."""
+        return self._alloc(batch, device)
+
     # -- cross-lane ordering: which earlier ops (on OTHER lanes) an op has to wait for -----------------------------------
     def _plan_sync(self, batch: int, device, slot: int = 0) -> tuple:
         """Ops of one lane are ordered by their stream.  Across lanes an op waits (HIP event) for: the producers of what it reads
@@ -657,7 +662,7 @@ class GraphedForward:
             self.outputs = self._body()
         # the graph's nodes hold raw device pointers into this batch shape's activation pool: keep the pool alive from here, whatever
         # Program._alloc evicts later (MAX_POOLS); a replay after an eviction would otherwise read and write freed memory
-        self._pool = prog._pools[(x.shape[0], str(x.device))]
+        self._pool = prog.pool_for(x.shape[0], x.device)
 
     def _body(self):
         # one stream inside the capture: hipStreamEndCapture of ROCm 7.2 crashed on the forked multi-stream HRNet schedule

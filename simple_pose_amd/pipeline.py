@@ -1,0 +1,336 @@
+"""Top-down pose estimation in one call: image in, poses out, nothing returns to the host in between.
+
+    est = TopDownPoseEstimator(detector, pose_model, decoder=GaussTaylorKeyPointDecoder(), capacity=32)
+    res = est.estimate(img)                       # uint8 BGR [H,W,3], numpy or CUDA -> PoseResult
+    res = est.estimate_batch(imgs)                # same-sized batch [B,H,W,3] -> list of PoseResult
+    res = est.estimate_boxes(imgs, det, counts)   # caller-supplied detections (the reference's predicts_by_pred path)
+
+The reference runs the three stages as three offline scripts joined by JSON files (eval.py: gen_data_by_detector, predicts_by_pred,
+temp_read_in_and_filter).  Here a frame is one stream of launches: letterbox + YOLOv5 + decode, sp_yolo_nms_device, sp_yolo_boxes_to_source,
+sp_topdown_plan (boxes -> crop geometry), sp_warp_affine_plan_u8c3 (the crops), the pose program on `capacity` crops, the key-point decode,
+sp_pose_rescore and sp_oks_nms.  The person count never reaches the host: the pose half always computes `capacity` slots (dead slots are
+zero crops that OKS-NMS never sees), which is what makes the frame capturable - at batch 1 it is ONE hipGraph.  One device-to-host
+transfer per call brings back the keep list, the counts, the status words and the rows.  There is no CPU fallback."""
+from __future__ import annotations
+
+from dataclasses import dataclass
+from typing import Dict, List, Sequence, Union
+
+import numpy as np
+import torch
+
+from . import _lib, engine
+from ._lib import HipLibraryError
+
+P = _lib.ptr
+MAX_CAPACITY = 2048                  # the OKS-NMS group limit (sp_oks_nms)
+
+
+@dataclass
+class PoseResult:
+    """The persons of one image that survive OKS-NMS, in pick order."""
+    keypoints: np.ndarray            # float64 [n, J, 3]: x, y (image px), max_val
+    score: np.ndarray                # float64 [n]: box score x mean of the visible joints' max_val (eval.py:166-174)
+    box: np.ndarray                  # float32 [n, 5]: x1, y1, x2, y2, detector confidence
+    dropped: int = 0                 # selected detections of this image that did not fit `capacity`
+
+    def __len__(self) -> int:
+        return int(self.score.shape[0])
+
+    def coco(self, image_id) -> List[dict]:
+        """The COCO result dicts `datasets.naive_data.filter_poses` returns for this image."""
+        return [{"image_id": image_id, "score": float(s), "category_id": 1, "keypoints": k.reshape(-1).tolist()}
+                for k, s in zip(self.keypoints, self.score)]
+
+
+def _run_program(prog: engine.Program, x: torch.Tensor, single_stream: bool) -> torch.Tensor:
+    """Program.run; `single_stream`: every launch on the caller's stream, as inside a capture (stream capture crashes on forked
+    schedules: engine.GraphedForward does the same)."""
+    keep = prog.multi_stream
+    if single_stream:
+        prog.multi_stream = False
+    try:
+        return prog.run(x)
+    finally:
+        prog.multi_stream = keep
+
+
+class _Frame:
+    """The device buffers of one (batch, source shape, max_det): the static source, the plan, the crops, and ONE packed result buffer
+    whose slices the kernels write directly, so that a call ends in a single device-to-host copy."""
+
+    def __init__(self, B: int, H: int, W: int, max_det: int, cap: int, J: int, in_hw, device):
+        self.B, self.H, self.W, self.max_det = B, H, W, max_det
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
+        self.src = z((B, H, W, 3), torch.uint8)
+        self.det = z((B, max_det, 6), torch.float32)
+        self.src_index = z((cap,), torch.int32)
+        self.m_inv = z((cap, 6), torch.float64)
+        self.trans_inv = z((cap, 2, 3), torch.float32)
+        self.center, self.scale = z((cap, 2), torch.float32), z((cap, 2), torch.float32)
+        self.area, self.box_score = z((cap,), torch.float64), z((cap,), torch.float64)
+        self.crops = z((cap, in_hw[0], in_hw[1], 3), torch.uint8)
+        fields = (("kps64", (cap, J, 3), torch.float64), ("score", (cap,), torch.float64), ("box", (cap, 5), torch.float32),
+                  ("keep", (cap,), torch.int32), ("keep_count", (B,), torch.int32), ("seg", (B + 1,), torch.int32),
+                  ("status", (B,), torch.int32), ("dropped", (B,), torch.int32), ("counts", (B,), torch.int32))
+        self.layout, off = {}, 0
+        for name, shape, dt in fields:
+            nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
+            self.layout[name] = (off, nbytes, shape, dt)
+            off += (nbytes + 255) // 256 * 256
+        self.pack = z((off,), torch.uint8)
+        self.host = torch.empty(off, dtype=torch.uint8, pin_memory=True)
+        for name, (o, nbytes, shape, dt) in self.layout.items():
+            setattr(self, name, self.pack[o:o + nbytes].view(dt).view(shape))
+        self.graph = None
+        self.params = None
+        self.keepalive = None
+
+    def fetch(self) -> Dict[str, np.ndarray]:
+        """The call's one device-to-host transfer (and its one synchronisation)."""
+        self.host.copy_(self.pack, non_blocking=True)
+        torch.cuda.current_stream(self.pack.device).synchronize()
+        h = self.host.numpy()
+        np_dt = {torch.float64: np.float64, torch.float32: np.float32, torch.int32: np.int32}
+        return {name: h[o:o + nbytes].view(np_dt[dt]).reshape(shape).copy() for name, (o, nbytes, shape, dt) in self.layout.items()}
+
+
+class TopDownPoseEstimator(object):
+    """Detector -> crops -> pose network -> decode -> rescoring + OKS-NMS, device resident.
+
+    `detector`: a `YOLOv5Detector`; its `conf_thresh` / `iou_thresh` are read per call.  `pose_model`: any model with `hip_program`
+    (ResNet-DConv / DUC, HRNet; fp32 or bf16 through `compute_dtype`), in eval mode.  `capacity`: person slots per call (1 .. 2048), shared
+    by the images of a batch; the pose network always runs on `capacity` crops, selected detections beyond it are dropped from the end of
+    the (image, detection) order and reported in `PoseResult.dropped`.  `person_cls`: the detector class kept (-1: every row, as the
+    reference's gen_data_by_detector does); `min_box_score`: detections below it are not cropped.
+    `use_graph`: `estimate` (batch 1) replays one captured graph per source shape (an LRU of MAX_GRAPHS shapes); False launches eagerly."""
+
+    MAX_GRAPHS = 8
+    MAX_DET = 300                    # non_max_suppression's default, what single_predict uses
+
+    def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
+                 in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64)):
+        from .detector.yolov5_detector import YOLOv5Detector
+        from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
+        if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
+            raise ValueError(f"capacity: expected an int in 1..{MAX_CAPACITY} (the OKS-NMS group limit), got {capacity!r}")
+        if not isinstance(detector, YOLOv5Detector):
+            raise TypeError(f"detector: expected a YOLOv5Detector, got {type(detector).__name__}")
+        if not callable(getattr(pose_model, "hip_program", None)):
+            raise TypeError(f"pose_model: {type(pose_model).__name__} has no hip_program (expected a simple_pose_amd.nets model)")
+        if getattr(pose_model, "training", False):
+            raise ValueError("pose_model is in train() mode; the estimator runs the eval-mode program (call .eval())")
+        if decoder is None:
+            decoder = GaussTaylorKeyPointDecoder()
+        if not isinstance(decoder, BasicKeyPointDecoder):
+            raise TypeError(f"decoder: expected a simple_pose_amd.metrics key-point decoder, got {type(decoder).__name__}")
+        if not isinstance(person_cls, int) or person_cls < -1:
+            raise ValueError(f"person_cls: a class index, or -1 for every detection; got {person_cls!r}")
+        if len(input_shape) != 2 or len(output_shape) != 2 or input_shape[0] % 32 or input_shape[1] % 32 or \
+                tuple(output_shape) != (input_shape[0] // 4, input_shape[1] // 4):
+            raise ValueError(f"input_shape (w, h) must be multiples of 32 and output_shape a quarter of it, got {input_shape} / {output_shape}")
+        self.detector, self.pose_model, self.decoder = detector, pose_model, decoder
+        self.capacity, self.person_cls, self.min_box_score = capacity, person_cls, float(min_box_score)
+        self.in_vis_thre, self.oks_thre = float(in_vis_thre), float(oks_thre)
+        self.input_shape, self.output_shape = tuple(int(v) for v in input_shape), tuple(int(v) for v in output_shape)
+        self.device = detector.device
+        self.use_graph = True
+        self._frames: Dict[tuple, _Frame] = {}
+
+    # -- programs and buffers ---------------------------------------------------------------------------------------------------------
+    def _pose_program(self) -> engine.Program:
+        iw, ih = self.input_shape
+        prog = self.pose_model.hip_program(torch.empty((0, 3, ih, iw), device=self.device))
+        if tuple(prog.out_shape[1:]) != (self.output_shape[1], self.output_shape[0]):
+            raise HipLibraryError(f"pose program produces heat maps {tuple(prog.out_shape)}, expected [J, {self.output_shape[1]}, {self.output_shape[0]}]")
+        if getattr(self.pose_model, "autotune", False) and self.capacity >= 16 and self.capacity >= 4 * prog.tuned_for_batch:
+            # as forward_crops does at this batch size: pins the fastest tile per layer (speed only, same bits); never inside a capture
+            prog.autotune(torch.zeros((self.capacity, ih, iw, 3), dtype=torch.uint8, device=self.device))
+        return prog
+
+    def _frame(self, B: int, H: int, W: int, max_det: int, J: int) -> _Frame:
+        key = (B, H, W, max_det, J)
+        fr = self._frames.get(key)
+        if fr is None:
+            if len(self._frames) >= self.MAX_GRAPHS:
+                self._frames.pop(next(iter(self._frames)))
+            fr = _Frame(B, H, W, max_det, self.capacity, J, (self.input_shape[1], self.input_shape[0]), self.device)
+        else:
+            self._frames.pop(key)                # most recently used last
+        self._frames[key] = fr
+        return fr
+
+    def _load(self, fr: _Frame, imgs) -> None:
+        """The images into the frame's static source buffer (host -> device, or a device copy)."""
+        if isinstance(imgs, np.ndarray):
+            if imgs.dtype != np.uint8:
+                raise TypeError(f"expected a uint8 BGR image, got {imgs.dtype}")
+            imgs = torch.from_numpy(np.ascontiguousarray(imgs))
+        elif not imgs.is_cuda:
+            raise HipLibraryError(f"image tensor is on {imgs.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
+        if imgs.dtype != torch.uint8:
+            raise TypeError(f"expected a uint8 BGR image, got {imgs.dtype}")
+        fr.src.copy_(imgs.reshape(fr.src.shape))
+
+    @staticmethod
+    def _shape_of(imgs, batched: bool):
+        if isinstance(imgs, (list, tuple)):
+            if not batched:
+                raise ValueError("estimate takes one image [H, W, 3]")
+            shapes = {tuple(np.shape(i)) for i in imgs}
+            if len(shapes) != 1:
+                raise ValueError("the images of one batch share one size")
+            if any(isinstance(i, torch.Tensor) for i in imgs):
+                imgs = torch.stack(list(imgs))
+            else:
+                imgs = np.stack([np.asarray(i) for i in imgs])
+        if not isinstance(imgs, (np.ndarray, torch.Tensor)):
+            raise TypeError(f"expected a uint8 BGR image (numpy or CUDA), got {type(imgs).__name__}")
+        if isinstance(imgs, torch.Tensor) and not imgs.is_cuda:
+            raise HipLibraryError(f"image tensor is on {imgs.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
+        want = 4 if batched else 3
+        if len(imgs.shape) != want or imgs.shape[-1] != 3 or 0 in tuple(imgs.shape):
+            raise ValueError(f"expected uint8 BGR {'[B, H, W, 3]' if batched else '[H, W, 3]'}, got {tuple(imgs.shape)}")
+        return imgs
+
+    # -- the frame: every launch between the source image and the packed result -------------------------------------------------------
+    def _params(self, det_prog, pose_prog) -> tuple:
+        d = self.detector
+        return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
+                id(det_prog), id(pose_prog), id(self.decoder))
+
+    def _detect(self, fr: _Frame, det_prog, single_stream: bool = False) -> None:
+        """letterbox + network + head decode, NMS and the un-letterbox, all on the device (what single_predict / predict compute)."""
+        lib, d = _lib.lib(), self.detector
+        from .detector.yolov5_detector import _workspace
+        g = d.transform.geometry(fr.H, fr.W)
+        engine.set_letterbox(det_prog, fr.H, fr.W, g["new_h"], g["new_w"], g["top"], g["left"])
+        pred = _run_program(det_prog, fr.src, single_stream)
+        B, N, no = pred.shape
+        ws = _workspace(B, pred.device)
+        stream = _lib.current_stream(self.device)
+        fr.det.zero_()
+        _lib.check(lib.sp_yolo_nms_device(P(pred), B, N, no, float(d.conf_thresh), float(d.iou_thresh), 1, 1, 0, fr.max_det, P(ws), ws.numel(),
+                                          P(fr.det), P(fr.counts), P(fr.status), stream), "sp_yolo_nms_device")
+        # every row: the rows past counts[b] are zeros, and the plan never reads them
+        _lib.check(lib.sp_yolo_boxes_to_source(P(fr.det), B * fr.max_det, float(g["out_h"]), float(g["out_w"]), float(g["left"]), float(g["top"]),
+                                               float(g["ratio"]), stream), "sp_yolo_boxes_to_source")
+        fr.ws = ws                                   # (a captured graph holds its pointer)
+
+    def _poses(self, fr: _Frame, pose_prog, single_stream: bool) -> None:
+        """plan -> crops -> pose forward -> decode -> rescore -> OKS-NMS over the frame's `det` / `counts`."""
+        lib, cap = _lib.lib(), self.capacity
+        stream = _lib.current_stream(self.device)
+        iw, ih = self.input_shape
+        ow, oh = self.output_shape
+        J = pose_prog.out_shape[0]
+        _lib.check(lib.sp_topdown_plan(P(fr.det), P(fr.counts), fr.B, fr.max_det, self.person_cls, self.min_box_score, cap, iw, ih, ow, oh,
+                                       P(fr.seg), P(fr.src_index), P(fr.m_inv), P(fr.trans_inv), P(fr.center), P(fr.scale), P(fr.area),
+                                       P(fr.box_score), P(fr.box), P(fr.dropped), stream), "sp_topdown_plan")
+        _lib.check(lib.sp_warp_affine_plan_u8c3(P(fr.src), fr.B, fr.H, fr.W, P(fr.m_inv), P(fr.src_index), P(fr.seg), cap, P(fr.crops), ih, iw,
+                                                stream), "sp_warp_affine_plan_u8c3")
+        hm = _run_program(pose_prog, fr.crops, single_stream)
+        kps, mv = self.decoder(hm, fr.trans_inv)
+        kps3 = torch.cat([kps, mv], -1)              # eval.py:138
+        _lib.check(lib.sp_pose_rescore(P(kps3), P(fr.box_score), cap, J, self.in_vis_thre, P(fr.kps64), P(fr.score), stream), "sp_pose_rescore")
+        _lib.check(lib.sp_oks_nms(P(fr.kps64), P(fr.score), P(fr.area), P(fr.seg), fr.B, cap, J, None, self.oks_thre, -1.0, P(fr.keep),
+                                  P(fr.keep_count), stream), "sp_oks_nms")
+
+    def _capture(self, fr: _Frame, det_prog, pose_prog) -> None:
+        dev = self.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                # warm-up outside the capture: activation pools and workspaces get allocated here
+            self._detect(fr, det_prog, True)
+            self._poses(fr, pose_prog, True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._detect(fr, det_prog, True)
+            self._poses(fr, pose_prog, True)
+        fr.graph, fr.params = graph, self._params(det_prog, pose_prog)
+        # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
+        fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self.capacity, dev), fr.ws)
+
+    def _results(self, fr: _Frame) -> List[PoseResult]:
+        h = fr.fetch()
+        if (h["status"] & 1).any():
+            b = int(np.nonzero(h["status"] & 1)[0][0])
+            raise HipLibraryError(f"image {b}: more than {_lib.SP_YOLO_NMS_MAX_CANDIDATES} detector candidates after the multi-label expansion "
+                                  "(raise the detector's conf_thresh)")
+        out = []
+        for b in range(fr.B):
+            lo, n = int(h["seg"][b]), int(h["keep_count"][b])
+            if n < 0:
+                raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
+            rows = h["keep"][lo:lo + n]
+            out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b])))
+        return out
+
+    # -- public surface -----------------------------------------------------------------------------------------------------------------
+    def _run(self, imgs, graph: bool) -> List[PoseResult]:
+        # Both program lookups validate their cache against every parameter's (data_ptr, version) - a walk over a few hundred tensors per
+        # call, replays included.  It is what notices in-place weight updates (and forces the re-capture); it is also host time that a
+        # replay does not get back, one reason the graphed frame is no faster than the eager one while the GPU is the longer side.
+        B, H, W = imgs.shape[0], imgs.shape[1], imgs.shape[2]
+        d = self.detector
+        g = d.transform.geometry(H, W)
+        det_prog = d.program(g["out_h"], g["out_w"])
+        pose_prog = self._pose_program()
+        fr = self._frame(B, H, W, self.MAX_DET, pose_prog.out_shape[0])
+        self._load(fr, imgs)
+        if graph:
+            if fr.graph is None or fr.params != self._params(det_prog, pose_prog):
+                self._capture(fr, det_prog, pose_prog)
+            fr.graph.replay()
+        else:
+            self._detect(fr, det_prog)
+            self._poses(fr, pose_prog, False)
+        return self._results(fr)
+
+    @torch.no_grad()
+    def estimate(self, img) -> PoseResult:
+        """One uint8 BGR image [H, W, 3] (numpy or CUDA) -> the persons in it."""
+        img = self._shape_of(img, batched=False)
+        return self._run(img[None], self.use_graph)[0]
+
+    @torch.no_grad()
+    def estimate_batch(self, imgs: Union[torch.Tensor, np.ndarray, Sequence]) -> List[PoseResult]:
+        """A batch of same-sized images ([B, H, W, 3], or a list of [H, W, 3]) -> one PoseResult per image.  One forward of the detector
+        on B images, one pose forward on the `capacity` slots the images share."""
+        return self._run(self._shape_of(imgs, batched=True), False)
+
+    @torch.no_grad()
+    def estimate_boxes(self, imgs, det, counts=None) -> List[PoseResult]:
+        """Caller-supplied detections instead of the detector (the reference's predicts_by_pred path): imgs [B, H, W, 3] (or one image
+        [H, W, 3]), det fp32 [B, M, 6] (or [M, 6]) rows (x1, y1, x2, y2, score, cls) in source pixels, counts int [B] valid rows per image
+        (default: all M).  Selection (`person_cls`, `min_box_score`, `capacity`) applies as in `estimate`."""
+        single = len(getattr(imgs, "shape", ())) == 3
+        imgs = self._shape_of(imgs[None] if single else imgs, batched=True)
+        B, H, W = imgs.shape[0], imgs.shape[1], imgs.shape[2]
+        if isinstance(det, np.ndarray):
+            det = torch.from_numpy(np.ascontiguousarray(det, dtype=np.float32)).to(self.device)
+        if not (isinstance(det, torch.Tensor) and det.is_cuda and det.dtype == torch.float32):
+            raise HipLibraryError("det: expected float32 detections [B, M, 6] (numpy or CUDA)")
+        if det.dim() == 2:
+            det = det[None]
+        if det.dim() != 3 or det.shape[0] != B or det.shape[2] != 6 or det.shape[1] == 0:
+            raise ValueError(f"det: expected [{B}, M, 6], got {tuple(det.shape)}")
+        M = det.shape[1]
+        if counts is None:
+            counts = [M] * B
+        if isinstance(counts, torch.Tensor):
+            cnt = counts.to(device=self.device, dtype=torch.int32).reshape(-1)
+        else:
+            cnt = torch.from_numpy(np.ascontiguousarray(np.asarray(counts, dtype=np.int32).reshape(-1))).to(self.device)
+        if cnt.numel() != B:
+            raise ValueError(f"counts: expected {B} values")
+        pose_prog = self._pose_program()
+        fr = self._frame(B, H, W, M, pose_prog.out_shape[0])
+        self._load(fr, imgs)
+        fr.det.copy_(det)
+        fr.counts.copy_(cnt)
+        fr.status.zero_()
+        self._poses(fr, pose_prog, False)
+        return self._results(fr)

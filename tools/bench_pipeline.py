@@ -1,0 +1,138 @@
+"""tools/bench_pipeline.py - the top-down frame (image -> poses) on one MI355X: staged chain vs the device-resident estimator.
+
+    python tools/bench_pipeline.py [--out profiles/pipeline_bench.json] [--quick]
+
+Per frame, median wall time ending in a device synchronise, warm, the variants ALTERNATED in one process (so that clock ramps and
+neighbours hit them alike):
+  staged   single_predict -> crop_boxes -> forward_crops -> decoder -> filter_poses (the public pieces, as a user assembles them)
+  staged2  the same chain again: the difference of the two medians is the measurement's own spread
+  eager    TopDownPoseEstimator.estimate with use_graph = False
+  graph    TopDownPoseEstimator.estimate, one graph replay per frame
+for the s detector on a 640x640 source, ResNet50-DConv fp32 and ResNet50-DUC bf16, capacity 32, at n = 1, 8 and 32 live persons (n is set
+through min_box_score from the detector's own scores and recorded).  Weights are the tests' conditioned ones (random), so the detections are
+not people - the work per frame is what is measured.  The kernel breakdown comes from a run of its own,
+`rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o pipe -- python tools/bench_pipeline.py --quick`; its pipe_kernel_stats.csv
+is kept as profiles/pipeline_kernel_stats.csv.  The pose models run with tile timing off (autotune = False): see pose_model.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+import time
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from oracle import nets_oracle  # noqa: E402
+from simple_pose_amd import synth  # noqa: E402
+from simple_pose_amd.datasets.naive_data import crop_boxes, filter_poses  # noqa: E402
+from simple_pose_amd.detector.nets.yolov5 import YOLOv5  # noqa: E402
+from simple_pose_amd.detector.yolov5_detector import YOLOv5Detector  # noqa: E402
+from simple_pose_amd.metrics import GaussTaylorKeyPointDecoder  # noqa: E402
+from simple_pose_amd.nets import pose_resnet_dconv, pose_resnet_duc  # noqa: E402
+from simple_pose_amd.pipeline import TopDownPoseEstimator  # noqa: E402
+from tests.detector_ref import detector_state_dict  # noqa: E402
+
+DEV = "cuda:0"
+CAPACITY = 32
+
+
+def pose_model(head, dtype):
+    m = (pose_resnet_dconv if head == "dconv" else pose_resnet_duc).resnet50(pretrained=False, num_classes=17)
+    sd = synth.conditioned_state_dict(nets_oracle.state_dict_shapes_resnet50(head), 0)
+    m.load_state_dict({k: torch.from_numpy(v) for k, v in sd.items()}, strict=True)
+    m = m.to(DEV).eval()
+    m.compute_dtype = dtype
+    # One Program serves every variant.  Tile timing is OFF: the first batch-32 forward would otherwise pin batch-32 tiles that the staged
+    # chain's batch-1 / batch-8 forwards then run on (forward_crops never retunes downwards), to the staged side's disadvantage.  Every
+    # variant runs the library's default tiles.
+    m.autotune = False
+    return m
+
+
+def staged_frame(detector, model, decoder, img, dev_img, min_score):
+    boxes = detector.single_predict(img)
+    if isinstance(boxes, list):
+        return [], 0
+    boxes = boxes[(boxes[:, 5] == 0) & (boxes[:, 4] >= min_score)][:CAPACITY]
+    if boxes.shape[0] == 0:
+        return [], 0
+    crops, tinv, _, _, area = crop_boxes(dev_img, boxes[:, :4].cpu().numpy())
+    with torch.no_grad():
+        hm = model.forward_crops(crops)
+        kps, mv = decoder(hm, tinv)
+    return filter_poses(torch.cat([kps, mv], -1), boxes[:, 4].double().cpu().numpy(), area, [0] * boxes.shape[0]), int(boxes.shape[0])
+
+
+def wall_ms(fn):
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    fn()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) * 1e3
+
+
+def summary(ts):
+    a = np.sort(np.asarray(ts))
+    return {"median_ms": float(np.median(a)), "p25_ms": float(a[len(a) // 4]), "p75_ms": float(a[(3 * len(a)) // 4]), "min_ms": float(a[0])}
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipeline_bench.json"))
+    ap.add_argument("--quick", action="store_true", help="DConv fp32 at n = 32 only, few repetitions (the kernel-trace run)")
+    args = ap.parse_args()
+    reps, warm = (5, 2) if args.quick else (40, 5)
+    det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
+    det.conf_thresh, det.iou_thresh = 0.02, 0.45
+    img = np.random.default_rng(0).integers(0, 256, (640, 640, 3), dtype=np.uint8)
+    dev_img = torch.from_numpy(img).to(DEV)
+    found = det.single_predict(img)
+    scores = np.zeros(0, np.float32) if isinstance(found, list) else found[found[:, 5] == 0][:, 4].cpu().numpy()
+    decoder = GaussTaylorKeyPointDecoder()
+    out = {"device": torch.cuda.get_device_name(0), "source": [640, 640], "detector": "s fp32", "capacity": CAPACITY, "detections": int(scores.size),
+           "reps": reps, "pose_autotune": False, "runs": []}
+    models = [("dconv", "fp32")] if args.quick else [("dconv", "fp32"), ("duc", "bf16")]
+    for head, dtype in models:
+        model = pose_model(head, dtype)
+        for n_want in ((32,) if args.quick else (1, 8, 32)):
+            if scores.size < n_want:
+                continue
+            # the detections come out in descending score order: a threshold between the n-th and the next keeps exactly n
+            min_score = 0.0 if n_want >= min(CAPACITY, scores.size) else float((np.float64(scores[n_want - 1]) + np.float64(scores[n_want])) / 2)
+            est = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY, min_box_score=min_score)
+            variants = {
+                "staged": lambda: staged_frame(det, model, decoder, img, dev_img, min_score),
+                "eager": lambda: (setattr(est, "use_graph", False), est.estimate(img))[1],
+                "graph": lambda: (setattr(est, "use_graph", True), est.estimate(img))[1],
+                "staged2": lambda: staged_frame(det, model, decoder, img, dev_img, min_score),
+            }
+            want, n_live = variants["staged"]()
+            same = all(variants[k]().coco(0) == want for k in ("eager", "graph"))
+            times = {k: [] for k in variants}
+            for r in range(warm + reps):
+                for k, fn in variants.items():
+                    t = wall_ms(fn)
+                    if r >= warm:
+                        times[k].append(t)
+            run = {"pose": f"resnet50-{head} {dtype}", "n_live": n_live, "min_box_score": min_score, "results_equal_staged": bool(same),
+                   "poses_kept": len(want)}
+            run.update({k: summary(v) for k, v in times.items()})
+            run["staged_self_spread_ms"] = abs(run["staged"]["median_ms"] - run["staged2"]["median_ms"])
+            run["graph_minus_staged_ms"] = run["graph"]["median_ms"] - run["staged"]["median_ms"]
+            out["runs"].append(run)
+            print(json.dumps(run), flush=True)
+    if not args.quick:
+        with open(args.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+        print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
