@@ -306,6 +306,49 @@ int sp_oks_nms(const double* kps, const double* scores, const double* areas, con
                int joints, const double* sigmas_host, double thresh, double vis_thresh, int32_t* keep, int32_t* keep_count,
                void* stream);
 
+/* ---- COCO keypoint AP / AR: what metrics/pose_metrics.py:182-209 (evaluate_map) and eval.py:13-27 (eval_kps) hand to
+ * pycocotools' COCOeval(gt, dt, "keypoints") - loadRes, evaluate() and accumulate() - in fp64 on the device.  (No new ABI version:
+ * these are additions.)  Capacities, enforced (SP_EINVAL from the host-known maxima, a negative dt_count from the kernel), never
+ * truncated to: */
+#define SP_COCO_MAX_JOINTS 64
+#define SP_COCO_MAX_GT_PER_IMAGE 128   /* ground truths of one image */
+#define SP_COCO_MAX_DT_PER_IMAGE 2048  /* detections of one image before the cut to max_dets */
+#define SP_COCO_MAX_DETS 32            /* max_dets (COCO keypoints: 20) */
+#define SP_COCO_MAX_THRS 16            /* iouThrs (COCO: 10) */
+#define SP_COCO_MAX_AREAS 4            /* areaRng (COCO keypoints: all, medium, large) */
+#define SP_COCO_MAX_REC_THRS 128       /* recThrs (COCO: 101) */
+#define SP_COCO_DT_XY_F64 1            /* dt_flags: dt_xy is float64 (else float32, widened as the JSON round trip does) */
+#define SP_COCO_DT_SCORE_F64 2         /* dt_flags: dt_score is float64 (else float32) */
+#define SP_COCO_GT_CROWD 1             /* gt_flag: iscrowd (may absorb several detections) */
+#define SP_COCO_GT_IGNORE 2            /* gt_flag: ignore or iscrowd or num_keypoints == 0 */
+/* loadRes + evaluate() (computeOks, evaluateImg) for `images` images in one launch, one workgroup per image.  Image i owns ground
+ * truths gt_seg[i]..gt_seg[i+1]-1 (annotation order) and detections dt_seg[i]..dt_seg[i+1]-1 (list order); device int32 [images+1].
+ * gt_kps [n_gt, J, 3] (x, y, v), gt_area [n_gt], gt_bbox [n_gt, 4] (x, y, w, h): float64; gt_flag [n_gt]: SP_COCO_GT_*.
+ * Detection p of the segment order is row dt_index[p] (device int32, or NULL: row p) of dt_xy [P, J, 2] and dt_score [P].
+ * max_gt / max_dt: the largest image's counts, known to the host.  sigmas_host: `joints` doubles in HOST memory or NULL (COCO's 17);
+ * iou_thrs_host [n_thrs], area_rng_host [n_areas][2]: HOST doubles.  With S = images * max_dets slots (slot i * max_dets + k = the
+ * k-th detection of image i in stable descending score order), the outputs are: dt_count [images] (kept detections; -1: more than
+ * SP_COCO_MAX_DT_PER_IMAGE detections, -2: more than SP_COCO_MAX_GT_PER_IMAGE ground truths - nothing of that image is evaluated),
+ * dt_keep [S] (row of dt_xy, -1 = empty slot), dt_kscore [S], dt_karea [S] (float64), oks [n_gt * max_dets] (image i: a
+ * [dt_count[i], G_i] row-major matrix at offset gt_seg[i] * max_dets, ground truths in annotation order), dtm int32 [n_areas, n_thrs, S]
+ * (matched ground-truth row, -1 = none), dt_ignore uint8 [n_areas, n_thrs, S], gt_ignore uint8 [n_areas, n_gt]. */
+int sp_coco_kp_eval_images(const int32_t* gt_seg, const double* gt_kps, const double* gt_area, const double* gt_bbox,
+                           const int32_t* gt_flag, const int32_t* dt_seg, const int32_t* dt_index, const void* dt_xy, const void* dt_score,
+                           int dt_flags, int images, int n_gt, int max_gt, int max_dt, int joints, const double* sigmas_host, int max_dets,
+                           const double* iou_thrs_host, int n_thrs, const double* area_rng_host, int n_areas, int32_t* dt_count,
+                           int32_t* dt_keep, double* dt_kscore, double* dt_karea, double* oks, int32_t* dtm, unsigned char* dt_ignore,
+                           unsigned char* gt_ignore, void* stream);
+/* accumulate(): a stable descending-score order of the kept detections of all images (tiled rank by counting: S^2 comparisons), then
+ * per (area range, threshold) the tp / fp scan over non-ignored detections, rc = tp / npig, pr = tp / (fp + tp + 2^-52), the
+ * envelope from the right and pr[searchsorted(rc, rec_thrs, 'left')].  precision float64 [n_thrs, n_rec, n_areas], recall float64
+ * [n_thrs, n_areas]; -1 where the range has no non-ignored ground truth.  rec_thrs_host: HOST doubles.  Two launches, no copy, no
+ * synchronisation.  workspace: sp_coco_kp_accumulate_workspace bytes of device memory. */
+int sp_coco_kp_accumulate_workspace(int images, int max_dets, int n_thrs, int n_areas, int64_t* bytes);
+int sp_coco_kp_accumulate(const int32_t* dt_count, const double* dt_kscore, const int32_t* dtm, const unsigned char* dt_ignore,
+                          const unsigned char* gt_ignore, int images, int n_gt, int max_dets, int n_thrs, int n_areas,
+                          const double* rec_thrs_host, int n_rec, void* workspace, int64_t workspace_bytes, double* precision,
+                          double* recall, void* stream);
+
 /* the same normalisation written directly in the network's input layout (the stem's loader format): NHWC4 fp32 [B,h,w,4] or,
  * out_bf16 == 1: NHWC8 bf16 [B,h,w,8]; out_bf16 == 2: NHWC4 bf16 [B,h,w,4] (what the bf16 inference stem reads); pad channels are zero.  Replaces sp_u8hwc_bgr_to_nchw_f32 + sp_nchw_to_nhwc4 when the crops
  * arrive as uint8 (1 byte per value over PCIe, one pass on the GPU). */

@@ -24,7 +24,9 @@ SP_CONV_HARDSWISH = 0x40      # y = hardswish(acc*scale + shift) (+ residual aft
 SP_CONV_OUT_SLICE = 0x80      # y = channel slice [c0, c0 + c_out) of an out_c-channel NHWC tensor (y pre-offset by c0)
 SP_LETTERBOX_FOCUS, SP_LETTERBOX_U8 = 0, 1
 SP_YOLO_NMS_MAX_CANDIDATES, SP_YOLO_NMS_MAX_DET = 32768, 1024
-CONV_TILES = ((128, 128), (64, 128), (128, 64), (64, 64), (256, 64), (128, 32))
+SP_COCO_MAX_JOINTS, SP_COCO_MAX_GT_PER_IMAGE, SP_COCO_MAX_DT_PER_IMAGE, SP_COCO_MAX_DETS = 64, 128, 2048, 32
+SP_COCO_DT_XY_F64, SP_COCO_DT_SCORE_F64, SP_COCO_GT_CROWD, SP_COCO_GT_IGNORE = 1, 2, 1, 2
+CONV_TILES =((128, 128), (64, 128), (128, 64), (64, 64), (256, 64), (128, 32))
 ABI_VERSION = 36
 SP_CONV_KERNEL_IGEMM, SP_CONV_KERNEL_RING, SP_CONV_KERNEL_PW, SP_CONV_KERNEL_RING_LW, SP_CONV_KERNEL_RING_LW4 = 0, 1, 2, 3, 4
 RING_LW4_TILES = ((192, 128), (128, 128), (96, 128), (256, 128), (128, 256), (96, 256), (64, 128))   # kernel = SP_CONV_KERNEL_RING_LW4 (four MFMA waves + four loader waves)
@@ -118,6 +120,10 @@ SYMBOLS = {
     "sp_pose_score": (c_int, [_P, c_int, c_int, _P, _P]),
     "sp_pose_rescore": (c_int, [_P, _P, c_int, c_int, c_double, _P, _P, _P]),
     "sp_oks_nms": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, _P, c_double, c_double, _P, _P, _P]),
+    "sp_coco_kp_eval_images": (c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int,
+                                       ctypes.POINTER(c_double), c_int, ctypes.POINTER(c_double), c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "sp_coco_kp_accumulate_workspace": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
+    "sp_coco_kp_accumulate": (c_int, [_P, _P, _P, _P, _P, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_double), c_int, _P, c_int64, _P, _P, _P]),
     "sp_pixel_unshuffle2_nhwc": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "sp_pixel_unshuffle2_nhwc_bf16": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "sp_maxpool3x3s2_idx_nhwc": (c_int, [_P, c_int, _P, _P, c_int, c_int, c_int, c_int, _P]),

@@ -4,6 +4,7 @@
 // trip; here the decoded key points never leave the device.  One workgroup per image; all arithmetic in fp64, operation by
 // operation as numpy evaluates it (contraction OFF; numpy's pairwise add.reduce order for the 17-term sums).
 #include "sp_common.h"
+#include "sp_oks.h"      // np_pairwise_sum, the COCO sigmas (shared with cocoeval.hip)
 
 #pragma clang fp contract(off)
 
@@ -13,27 +14,6 @@ constexpr int NMS_MAX_JOINTS = 64;
 constexpr int NMS_MAX_GROUP = 2048;
 
 struct NmsVar { double v[NMS_MAX_JOINTS]; };
-
-// numpy float64 add.reduce over a contiguous run: 8 interleaved accumulators over the multiple-of-8 prefix, combined as
-// ((r0+r1)+(r2+r3))+((r4+r5)+(r6+r7)), tail in order; n < 8: in order.
-__device__ double np_pairwise_sum(const double* a, int n) {
-    if (n < 8) {
-        double r = 0.0;
-        for (int i = 0; i < n; ++i) r += a[i];
-        return r;
-    }
-    double r[8];
-#pragma unroll
-    for (int j = 0; j < 8; ++j) r[j] = a[j];
-    int i = 8;
-    for (; i < n - (n % 8); i += 8) {
-#pragma unroll
-        for (int j = 0; j < 8; ++j) r[j] += a[i + j];
-    }
-    double res = ((r[0] + r[1]) + (r[2] + r[3])) + ((r[4] + r[5]) + (r[6] + r[7]));
-    for (; i < n; ++i) res += a[i];
-    return res;
-}
 
 // eval.py:166-174: score = box_score * mean(kpt_scores[kpt_scores > in_vis_thre]) (0 without a visible joint); also widens the
 // fp32 decoder output to the float64 the reference's JSON round trip produces.
@@ -153,14 +133,13 @@ extern "C" int sp_pose_rescore(const float* kps, const double* box_score, int pe
 extern "C" int sp_oks_nms(const double* kps, const double* scores, const double* areas, const int32_t* seg, int groups, int max_group,
                           int joints, const double* sigmas_host, double thresh, double vis_thresh, int32_t* keep, int32_t* keep_count,
                           void* stream) {
-    static const double coco[17] = {.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89};
     SP_REQUIRE(kps && scores && areas && seg && keep && keep_count, "sp_oks_nms: null pointer");
     SP_REQUIRE(groups > 0 && joints > 0 && joints <= NMS_MAX_JOINTS, "sp_oks_nms: groups=%d joints=%d", groups, joints);
     SP_REQUIRE(sigmas_host || joints == 17, "sp_oks_nms: the default sigmas are COCO's 17; pass sigmas for %d joints", joints);
     SP_REQUIRE(max_group >= 0 && max_group <= NMS_MAX_GROUP, "sp_oks_nms: %d persons in one image (limit %d)", max_group, NMS_MAX_GROUP);
     NmsVar var;
     for (int j = 0; j < joints; ++j) {
-        const double s = sigmas_host ? sigmas_host[j] : coco[j] / 10.0;   // naive_data.py:131-133
+        const double s = sigmas_host ? sigmas_host[j] : sp_coco_sigma10(j) / 10.0;   // naive_data.py:131-133
         var.v[j] = (s * 2) * (s * 2);
     }
     hipLaunchKernelGGL(oks_nms_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, kps, scores, areas, seg, joints, var, thresh, vis_thresh,

@@ -1,1 +1,3 @@
 from .pose_metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder  # noqa: F401
+from .pose_metrics import evaluate_map  # noqa: F401
+from .coco_eval import KeypointEvaluator, KeypointGroundTruth  # noqa: F401

@@ -117,3 +117,19 @@ def kps_to_dict_(predicts: torch.Tensor, scores: torch.Tensor, img_ids, set_in_l
     flat = torch.cat([predicts, scores.reshape(B, J, 1)], dim=-1).reshape(B, -1).cpu().tolist()    # output formatting only
     for kp, s, img_id in zip(flat, sc.cpu().tolist(), img_ids):
         set_in_list.append({"image_id": img_id, "score": float(s), "category_id": 1, "keypoints": kp})
+
+
+def evaluate_map(res_file, ann_file, ann_type='keypoints', silence=True):
+    """`metrics/pose_metrics.py:182-209`: COCO keypoint AP / AR of a result file against an annotation file, as the dict
+    {'AP', 'Ap .5', 'AP .75', 'AP (M)', 'AP (L)', 'AR', 'AR .5', 'AR .75', 'AR (M)', 'AR (L)'} the reference builds from COCOeval's
+    stats.  The evaluation runs on the device (metrics.coco_eval); `res_file` may also be the list of result dicts and `ann_file` the
+    annotation dict or a `KeypointGroundTruth`.  `silence=False` prints the ten lines summarize() would."""
+    from .coco_eval import STAT_NAMES, evaluate_keypoints
+    if ann_type != 'keypoints':
+        raise ValueError(f"ann_type {ann_type!r}: only 'keypoints' is evaluated (no box / segmentation evaluation)")
+    ev = evaluate_keypoints(res_file, ann_file)
+    info_str = {name: ev.stats[ind] for ind, name in enumerate(STAT_NAMES)}
+    if not silence:
+        for name, value in info_str.items():
+            print(" {:<8s} @[ OKS=0.50:0.95 | maxDets={:d} ] = {:0.3f}".format(name, ev.max_dets, value))
+    return info_str

@@ -2,13 +2,13 @@
 schema, one process per GPU (env:// rendezvous, `torch.distributed` backend nccl = RCCL), every per-iteration operation a
 HIP kernel behind `simple_pose_amd` (train step, HeatMapAcc, decoder).
 
-Out of scope by the survey's contract: COCO parsing / augmentation and COCOeval.  The loaders are
-therefore pluggable (`train_loader` / `val_loader`: iterables of the reference's collate tuples, tensors on any device), and
-`data.synthetic: N` builds deterministic synthetic ones on the GPU; `val()` reports loss / accuracy and writes the
-checkpoint in the reference's format, and computes AP only when pycocotools is importable and an annotation file is given."""
+Out of scope by the survey's contract: COCO parsing / augmentation.  The loaders are therefore pluggable
+(`train_loader` / `val_loader`: iterables of the reference's collate tuples, tensors on any device), and `data.synthetic: N` builds
+deterministic synthetic ones on the GPU; `val()` reports loss / accuracy and writes the checkpoint in the reference's format.  With
+ground truth (`data.val_ann_path` names an annotation file, or `val_gt` is passed) it also reports COCO keypoint AP from the device
+evaluator (metrics.coco_eval: the decoder's output goes to it without leaving the GPU), tracks `best_map` and writes `_best.pth`."""
 from __future__ import annotations
 
-import json
 import os
 from typing import Iterable, Optional
 
@@ -73,7 +73,9 @@ class SyntheticLoader:
 
 
 class DDPProcessor(object):
-    def __init__(self, cfg_path: str, train_loader: Optional[Iterable] = None, val_loader: Optional[Iterable] = None):
+    def __init__(self, cfg_path: str, train_loader: Optional[Iterable] = None, val_loader: Optional[Iterable] = None, val_gt=None):
+        """`val_gt`: the validation ground truth as a `KeypointGroundTruth` or an annotation dict (`images` / `annotations`); default: the
+        annotation file `data.val_ann_path` when it exists, else none (val() then reports `val_ap: None`)."""
         with open(cfg_path, "r") as rf:
             self.cfg = yaml.safe_load(rf)
         self.data_cfg, self.model_cfg = self.cfg["data"], self.cfg["model"]
@@ -114,6 +116,7 @@ class DDPProcessor(object):
         self.decoder = BasicKeyPointDecoder()
         self.best_map = 0.0
         self.history = []
+        self.val_gt = val_gt
 
     # ddp...:97-153
     def train(self, epoch: int):
@@ -152,6 +155,7 @@ class DDPProcessor(object):
         self.loss_logger.reset(); self.acc_logger.reset()
         self.model.eval()
         kps_dict_list = []
+        evaluator = self._evaluator()
         ws = torch.empty(4096, dtype=torch.uint8, device=self.device)
         for input_tensors, heat_maps, masks, trans_invs, img_ids in self.vloader:
             x, targets = input_tensors.to(self.device), heat_maps.to(self.device)
@@ -164,10 +168,12 @@ class DDPProcessor(object):
             acc = self.acc_func(predicts, targets, mask)
             pred_kps, scores = self.decoder(predicts, tinv)
             kps_to_dict_(pred_kps, scores, img_ids, kps_dict_list)
+            if evaluator is not None:
+                evaluator.add(pred_kps, scores, img_ids)      # the same persons and the same score rule, kept on the device
             self.loss_logger.update(loss[0]); self.acc_logger.update(acc)
         self.model.train()
         cpkt = {"ema": {k: v.detach().cpu().clone() for k, v in self.model.state_dict().items()}, "epoch": epoch}
-        val_ap = self._evaluate_map(kps_dict_list)
+        val_ap = self._evaluate_map(evaluator)
         out = {"epoch": epoch, "loss": self.loss_logger.avg(), "acc": self.acc_logger.avg(), "val_ap": val_ap, "results": len(kps_dict_list)}
         print("val epoch:{:d}|mean_loss:{:8.6f}|mean_acc:{:6.4f}|val_ap:{}".format(epoch + 1, out["loss"], out["acc"] * 100, val_ap))
         wdir = self.val_cfg["weight_path"]
@@ -178,21 +184,23 @@ class DDPProcessor(object):
         torch.save(cpkt, os.path.join(wdir, "{:s}_last.pth".format(self.cfg["model_name"])))
         return out
 
-    def _evaluate_map(self, kps_dict_list):
-        ann = self.data_cfg.get("val_ann_path")
-        if not ann or not os.path.isfile(ann):
-            return None                                       # synthetic data has no ground-truth annotation file
-        try:
-            from pycocotools.coco import COCO
-            from pycocotools.cocoeval import COCOeval
-        except ImportError:
+    def _evaluator(self):
+        """A fresh evaluator over the validation ground truth (parsed and uploaded once), or None without ground truth."""
+        from ..metrics.coco_eval import KeypointEvaluator, KeypointGroundTruth
+        if self.val_gt is None:
+            ann = self.data_cfg.get("val_ann_path")
+            if not ann or not os.path.isfile(ann):
+                return None                                   # synthetic data has no ground-truth annotation file
+            self.val_gt = ann
+        if not isinstance(self.val_gt, KeypointGroundTruth):
+            self.val_gt = KeypointGroundTruth(self.val_gt)
+        return KeypointEvaluator(self.val_gt, device=self.device)
+
+    def _evaluate_map(self, evaluator):
+        """ddp...:198-206 (evaluate_map over temp_test.json): COCOeval's stats[0], without the JSON file and on the device."""
+        if evaluator is None:
             return None
-        with open("temp_test.json", "w") as wf:
-            json.dump(kps_dict_list, wf)
-        gt = COCO(ann)
-        ev = COCOeval(gt, gt.loadRes("temp_test.json"), "keypoints")
-        ev.evaluate(); ev.accumulate(); ev.summarize()
-        return float(ev.stats[0])
+        return float(evaluator.evaluate()["AP"])
 
     def run(self):
         for epoch in range(self.optim_cfg["epochs"]):
