@@ -14,12 +14,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int TH = 8, TW = 16;                  // output tile
 constexpr int TTH = TH + 2, TTW = TW + 2;       // t tile: 10 x 18 = 180 pixels (6 MFMA row blocks of 32, 12 slots idle)
@@ -282,13 +276,6 @@ constexpr int WSTAGE = 36 * 512;                           // one filter in frag
 constexpr int LDS_BYTES = T_BYTES + 512 + 2 * X_BYTES;
 static_assert(LDS_BYTES <= 160 * 1024 && 2 * WSTAGE <= X_BYTES, "LDS");
 
-// one LDS-DMA piece (conv_ring.hip dma16: inline asm on purpose, see there): 64 lanes x 16 bytes, lane l's bytes from rsrc + voff (zeros when out
-// of range) to LDS at lds_addr + 16 l
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, __amdgpu_buffer_rsrc_t rsrc) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc)
-                 : "memory");
-}
-
 __global__ __launch_bounds__(512) void basic_block_c32_w8_kernel(const BlockArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     // LDS: t tile [0, 32 KB) and the scale / shift table first (their reads are base + 16-bit immediate), then the two halo buffers
@@ -343,7 +330,7 @@ __global__ __launch_bounds__(512) void basic_block_c32_w8_kernel(const BlockArgs
     };
     auto piece = [&](int i, int buf) __attribute__((always_inline)) {
         const int id = wave * PPW + i;
-        dma16(xs_lds + (unsigned)(buf * X_BYTES + (id / 10) * XPLANE + (id % 10) * 1024), hsrc[i], xr);
+        sp_dma16(xs_lds + (unsigned)(buf * X_BYTES + (id / 10) * XPLANE + (id % 10) * 1024), hsrc[i], xr);
     };
     addresses(tile0);
 #pragma unroll
@@ -600,11 +587,10 @@ extern "C" int sp_basic_block_c32(const sp_conv_desc* d, const void* x, const vo
         a.x_bytes = (int)(elems * 2); a.w_bytes = d->n_pad * d->k_pad * 2;
         const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
         SP_REQUIRE(tiles < (1ll << 31), "sp_basic_block_c32: too many tiles");
-        static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&s48::basic_block_c32_w8_kernel),
-                                                           hipFuncAttributeMaxDynamicSharedMemorySize, s48::LDS_BYTES);
-        SP_REQUIRE(attr == hipSuccess, "sp_basic_block_c32: cannot reserve %d bytes of LDS (%s)", s48::LDS_BYTES, hipGetErrorString(attr));
+        if (sp_reserve_lds<&s48::basic_block_c32_w8_kernel>(s48::LDS_BYTES, "sp_basic_block_c32")) return SP_ELAUNCH;
         // persistent, one workgroup per CU; consecutive strips per workgroup, and as many workgroups as keeps the longest share minimal
-        const long long per = (tiles + 255) / 256;
+        const int cus = sp_device_cus();
+        const long long per = (tiles + cus - 1) / cus;
         const long long grid = (tiles + per - 1) / per;
         hipLaunchKernelGGL(s48::basic_block_c32_w8_kernel, dim3((unsigned)grid), dim3(512), s48::LDS_BYTES, (hipStream_t)stream, a);
         return sp_check_launch("basic_block_c32_w8_kernel");
@@ -613,7 +599,8 @@ extern "C" int sp_basic_block_c32(const sp_conv_desc* d, const void* x, const vo
     a.x_bytes = (int)(elems * 2); a.w_bytes = d->n_pad * d->k_pad * 2;
     const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
     SP_REQUIRE(tiles < (1ll << 31), "sp_basic_block_c32: too many tiles");
-    const long long grid = tiles < 256 * 2 ? tiles : 256 * 2;     // persistent: two workgroups per CU, filters fetched once each
+    const int slots = 2 * sp_device_cus();
+    const long long grid = tiles < slots ? tiles : slots;         // persistent: two workgroups per CU, filters fetched once each
     hipLaunchKernelGGL(basic_block_c32_kernel, dim3((unsigned)grid), dim3(256), 0, (hipStream_t)stream, a);
     return sp_check_launch("basic_block_c32_kernel");
 }

@@ -23,12 +23,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef __bf16 bf16x2 __attribute__((ext_vector_type(2)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int C = 64, KP = 576;                             // channels; K = 9 taps x 64 (the packed rows' length: k_pad)
 constexpr int TH = 4, TW = 24;                              // output strip
@@ -52,13 +46,6 @@ struct Block64Args {
     int H, W, batch, tiles_x, tiles_y;
     int x_bytes, w_bytes;
 };
-
-// one LDS-DMA piece (conv_ring.hip dma16: inline asm on purpose, see there): 64 lanes x 16 bytes, lane l's bytes from rsrc + voff (zeros when out
-// of range) to LDS at lds_addr + 16 l
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, __amdgpu_buffer_rsrc_t rsrc) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc)
-                 : "memory");
-}
 
 __global__ __launch_bounds__(512) void basic_block_c64_kernel(const Block64Args p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -101,7 +88,7 @@ __global__ __launch_bounds__(512) void basic_block_c64_kernel(const Block64Args 
             const int hy = P / XW, hx = P - hy * XW;
             const int iy = y0 + hy, ix = x0 + hx;
             const bool ok = tile < tile_end && P < NX && (unsigned)iy < (unsigned)p.H && (unsigned)ix < (unsigned)p.W;
-            dma16(xs_lds + (unsigned)(buf * XSTRIDE + (id / 4) * XPLANE + (id % 4) * 1024),
+            sp_dma16(xs_lds + (unsigned)(buf * XSTRIDE + (id / 4) * XPLANE + (id % 4) * 1024),
                   ok ? (unsigned)(base + (hy * p.W + hx) * (C * 2) + (id / 4) * 16) : OOB, xr);
         }
     };
@@ -323,10 +310,10 @@ extern "C" int sp_basic_block_c64(const sp_conv_desc* d, const void* x, const vo
     a.x_bytes = (int)(elems * 2); a.w_bytes = d->n_pad * d->k_pad * 2;
     const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
     SP_REQUIRE(tiles < (1ll << 31), "sp_basic_block_c64: too many tiles");
-    static const hipError_t attr = hipFuncSetAttribute(reinterpret_cast<const void*>(&basic_block_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES);
-    SP_REQUIRE(attr == hipSuccess, "sp_basic_block_c64: cannot reserve %d bytes of LDS (%s)", LDS_BYTES, hipGetErrorString(attr));
+    if (sp_reserve_lds<&basic_block_c64_kernel>(LDS_BYTES, "sp_basic_block_c64")) return SP_ELAUNCH;
     // persistent, one workgroup per CU; consecutive strips per workgroup, and as many workgroups as keeps the longest share minimal
-    const long long per = (tiles + 255) / 256;
+    const int cus = sp_device_cus();
+    const long long per = (tiles + cus - 1) / cus;
     const long long grid = (tiles + per - 1) / per;
     hipLaunchKernelGGL(basic_block_c64_kernel, dim3((unsigned)grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
     return sp_check_launch("basic_block_c64_kernel");

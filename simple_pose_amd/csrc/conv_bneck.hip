@@ -43,7 +43,6 @@ extern "C" int sp_bneck_debug_read(unsigned long long* dst, int n) {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int BT_H = 16, BT_W = 8;                 // output tile: 16 rows x 8 columns; wave w = rows 4w..4w+3
 constexpr int BH_H = BT_H + 2, BH_W = BT_W + 2;    // halo tile 18 x 10 = 180 pixels
@@ -697,20 +696,14 @@ extern "C" int sp_bottleneck_c64(const sp_conv_desc* d, const void* x, const voi
     a.w1_bytes = CM * CIO * 2; a.w2_bytes = CM * 576 * 2; a.w3_bytes = CIO * CM * 2;
     const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
     SP_REQUIRE(tiles < (1ll << 31), "sp_bottleneck_c64: too many tiles");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&bottleneck_c64_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB);
-    if (e != hipSuccess) { sp_set_error("sp_bottleneck_c64: hipFuncSetAttribute(max dynamic LDS = %d) failed: %s", LDSB, hipGetErrorString(e)); return SP_ELAUNCH; }
+    const int cus = sp_device_cus();
     const long long grid = tiles < cus ? tiles : cus;
     if (w8) {
-        const hipError_t e8 = hipFuncSetAttribute(reinterpret_cast<const void*>(&bottleneck_c64_w8_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDSB8);
-        if (e8 != hipSuccess) { sp_set_error("sp_bottleneck_c64: hipFuncSetAttribute(max dynamic LDS = %d) failed: %s", LDSB8, hipGetErrorString(e8)); return SP_ELAUNCH; }
+        if (sp_reserve_lds<&bottleneck_c64_w8_kernel>(LDSB8, "sp_bottleneck_c64")) return SP_ELAUNCH;
         hipLaunchKernelGGL(bottleneck_c64_w8_kernel, dim3((unsigned)grid), dim3(512), LDSB8, (hipStream_t)stream, a);
         return sp_check_launch("bottleneck_c64_w8_kernel");
     }
+    if (sp_reserve_lds<&bottleneck_c64_kernel>(LDSB, "sp_bottleneck_c64")) return SP_ELAUNCH;
     hipLaunchKernelGGL(bottleneck_c64_kernel, dim3((unsigned)grid), dim3(256), LDSB, (hipStream_t)stream, a);
     return sp_check_launch("bottleneck_c64_kernel");
 }

@@ -11,7 +11,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int CI = 32, CO = 32;
 constexpr unsigned OOB = 0x80000000u;
@@ -386,13 +385,8 @@ extern "C" int sp_conv3x3_direct(const sp_conv_desc* d, const void* x, const voi
         a.tiles_x = (d->in_w + T7C - 1) / T7C; a.tiles_y = (d->in_h + T7R - 1) / T7R;
         const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
         SP_REQUIRE(tiles < (1ll << 31), "sp_conv3x3_direct: too many tiles");
-        int dev = 0, cus = 256;
-        if (hipGetDevice(&dev) == hipSuccess) {
-            int v = 0;
-            if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-        }
-        const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c64_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS7);
-        if (e != hipSuccess) { sp_set_error("sp_conv3x3_direct: hipFuncSetAttribute(max dynamic LDS = %d) failed: %s", LDS7, hipGetErrorString(e)); return SP_ELAUNCH; }
+        if (sp_reserve_lds<&conv3x3_c64_tile_kernel>(LDS7, "sp_conv3x3_direct")) return SP_ELAUNCH;
+        const int cus = sp_device_cus();
         const long long grid = tiles < cus ? tiles : cus;
         hipLaunchKernelGGL(conv3x3_c64_tile_kernel, dim3((unsigned)grid), dim3(512), LDS7, (hipStream_t)stream, a);
         return sp_check_launch("conv3x3_c64_tile_kernel");

@@ -20,8 +20,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 
 constexpr int DP_TM = 128;                         // pixels per tile
 constexpr int DP_K = 64, DP_N = 256;
@@ -42,23 +40,6 @@ struct DualArgs {
     int a_bytes, w_bytes, y_bytes;
 };
 
-__device__ __forceinline__ u32x4 dual_rsrc(const void* base, int bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    u32x4 r;
-    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);
-    r[2] = __builtin_amdgcn_readfirstlane((unsigned)bytes);
-    r[3] = 0x00020000u;
-    return r;
-}
-
-// one LDS-DMA piece (conv_ring.hip dma16: inline asm on purpose, see there): 64 lanes x 16 bytes, lane l's bytes from rsrc + voff (zeros when out
-// of range) to LDS at lds_addr + 16 l
-__device__ __forceinline__ void dual_dma16(unsigned lds_addr, unsigned voff, u32x4 rsrc) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff), "s"(rsrc)
-                 : "memory");
-}
-
 __global__ __launch_bounds__(512, 2) void dual_pw_bf16_kernel(const DualArgs p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smemd[];
     unsigned char* const Wl = smemd;                              // [2 products][DP_WB]
@@ -69,7 +50,7 @@ __global__ __launch_bounds__(512, 2) void dual_pw_bf16_kernel(const DualArgs p) 
     const int fr = lane & 31, fh = lane >> 5;
     const int G = gridDim.x;
 
-    const u32x4 ar0 = dual_rsrc(p.a_main, p.a_bytes), ar1 = dual_rsrc(p.a_short, p.a_bytes);
+    const u32x4 ar0 = sp_make_rsrc(p.a_main, p.a_bytes), ar1 = sp_make_rsrc(p.a_short, p.a_bytes);
     const __amdgpu_buffer_rsrc_t wr0 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_main), (short)0, p.w_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t wr1 = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.w_short), (short)0, p.w_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, p.y_bytes, 0x00020000);
@@ -97,8 +78,8 @@ __global__ __launch_bounds__(512, 2) void dual_pw_bf16_kernel(const DualArgs p) 
             const long long m = (long long)tile * DP_TM + row;
             const unsigned src = m < p.rows ? (unsigned)((m * DP_K + ((pc ^ ((row >> 1) & 7)) << 3)) * 2) : OOB;
             const unsigned dst = at_lds + (unsigned)(buf * 2 * DP_AB + piece * 1024);
-            dual_dma16(dst, src, ar0);
-            dual_dma16(dst + DP_AB, src, ar1);
+            sp_dma16(dst, src, ar0);
+            sp_dma16(dst + DP_AB, src, ar1);
         }
     };
 
@@ -194,13 +175,8 @@ extern "C" int sp_dual_pw_bf16(const void* a_main, const void* w_main_packed, co
     a.s_main = scale_main; a.h_main = shift_main; a.s_short = scale_short; a.h_short = shift_short; a.y = y;
     a.rows = (int)rows; a.tiles = (int)((rows + DP_TM - 1) / DP_TM); a.relu = relu ? 1 : 0;
     a.a_bytes = (int)(rows * DP_K * 2); a.w_bytes = DP_N * DP_K * 2; a.y_bytes = (int)(rows * DP_N * 2);
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&dual_pw_bf16_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, DP_LDS);
-    if (e != hipSuccess) { sp_set_error("sp_dual_pw_bf16: hipFuncSetAttribute(max dynamic LDS = %d) failed: %s", DP_LDS, hipGetErrorString(e)); return SP_ELAUNCH; }
+    if (sp_reserve_lds<&dual_pw_bf16_kernel>(DP_LDS, "sp_dual_pw_bf16")) return SP_ELAUNCH;
+    const int cus = sp_device_cus();
     const int grid = a.tiles < cus ? a.tiles : cus;
     hipLaunchKernelGGL(dual_pw_bf16_kernel, dim3(grid), dim3(512), DP_LDS, (hipStream_t)stream, a);
     return sp_check_launch("dual_pw_bf16_kernel");

@@ -168,9 +168,10 @@ extern "C" int sp_conv2d_wgrad_grouped(const void* x, const void* dz, int bf16, 
     a.kh = kh; a.kw = kw; a.stride = stride; a.pad = pad;
     const size_t lds = ((size_t)kh * (in_w + 2 * pad) * a.ci + (size_t)out_w * a.ob) * sizeof(float);
     SP_REQUIRE(lds <= 160 * 1024, "sp_conv2d_wgrad_grouped: a row of %d pixels x %d channels does not fit the staging tile (%zu bytes of LDS)", in_w, a.ci, lds);
-    const void* fn = bf16 ? reinterpret_cast<const void*>(&gwgrad_partial_kernel<true>) : reinterpret_cast<const void*>(&gwgrad_partial_kernel<false>);
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    if (e != hipSuccess) { sp_set_error("sp_conv2d_wgrad_grouped: hipFuncSetAttribute(max dynamic LDS = %zu) failed: %s", lds, hipGetErrorString(e)); return SP_ELAUNCH; }
+    // the staging tile depends on the shape: the reservation grows to the largest row seen
+    if (bf16 ? sp_reserve_lds<&gwgrad_partial_kernel<true>>((int)lds, "sp_conv2d_wgrad_grouped")
+             : sp_reserve_lds<&gwgrad_partial_kernel<false>>((int)lds, "sp_conv2d_wgrad_grouped"))
+        return SP_ELAUNCH;
     const dim3 grid(a.chunks, c / a.ob);
     if (bf16) hipLaunchKernelGGL(gwgrad_partial_kernel<true>, grid, dim3(GW_THREADS), lds, (hipStream_t)stream, a);
     else hipLaunchKernelGGL(gwgrad_partial_kernel<false>, grid, dim3(GW_THREADS), lds, (hipStream_t)stream, a);

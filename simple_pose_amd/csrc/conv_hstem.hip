@@ -21,9 +21,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct HStemArgs {
     const float* x;                 // [B][3][H][W]
@@ -245,20 +242,8 @@ extern "C" int sp_hrnet_stem(const float* x, const void* w1_packed, int k1_pad, 
         sp_name_query_set("hrnet_stem_kernel");
         return SP_OK;
     }
-    static bool opted[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&hrnet_stem_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-            sp_set_error("hrnet stem: hipFuncSetAttribute(max dynamic LDS = %d) failed on device %d", LDS_BYTES, dev);
-            return SP_ELAUNCH;
-        }
-        hipDeviceProp_t prop;
-        cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        opted[dev] = true;
-    }
-    const int slots = cus[dev];                            // one workgroup per CU (398 registers per lane: one wave per SIMD)
+    if (sp_reserve_lds<&hrnet_stem_kernel>(LDS_BYTES, "hrnet stem")) return SP_ELAUNCH;
+    const int slots = sp_device_cus();                           // one workgroup per CU (398 registers per lane: one wave per SIMD)
     const int rounds = (a.n_tiles + slots - 1) / slots;
     const int grid = (a.n_tiles + rounds - 1) / rounds;
     hipLaunchKernelGGL(hrnet_stem_kernel, dim3(grid), dim3(256), LDS_BYTES, (hipStream_t)stream, a);

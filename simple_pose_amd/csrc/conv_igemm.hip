@@ -126,7 +126,6 @@ __device__ __forceinline__ float hardswish(float v) {
 
 __device__ __forceinline__ int swz(int row, int chunk) { return row * BK + ((chunk ^ ((row >> 1) & 7)) << 2); }
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 // (the BatchNorm element map of train.hip's bn_fwd_elem, operation by operation with contraction off: the ABN staging pass must give the bits
 // of the stand-alone pass it replaces)
@@ -930,22 +929,9 @@ int launch_t(const ConvArgs& a, int phases, bool uniform, hipStream_t stream) {
     const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int) +
                        ((STATS || BSTATS) ? (size_t)3 * WR * BN * sizeof(float) : 0);     // + the wave rows' column sums (statistics epilogue)
     dim3 grid(p.tiles_m * p.tiles_n, phases, 1), block(256, 1, 1);
-    // > 64 KiB of dynamic LDS needs an explicit opt-in, once per kernel instantiation AND per device (the attribute belongs to the
-    // function on the device that is current: a process driving several GPUs must not inherit device 0's opt-in)
-    static bool opted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        const hipError_t eu = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WR, WC, true, BF16, OUT16, STATS, DEEP, BSTATS>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        const hipError_t ec = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_kernel<BM, BN, WR, WC, false, BF16, OUT16, STATS, DEEP, BSTATS>),
-                                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-        if (eu != hipSuccess || ec != hipSuccess) {
-            sp_set_error("conv_igemm: hipFuncSetAttribute(max dynamic LDS = %zu) failed on device %d", lds, dev);
-            return SP_ELAUNCH;
-        }
-        opted[dev] = true;       // (a benign race: two threads may both set the same attribute to the same value)
-    }
+    if (sp_reserve_lds<&conv_igemm_kernel<BM, BN, WR, WC, true, BF16, OUT16, STATS, DEEP, BSTATS>>((int)lds, "conv_igemm") ||
+        sp_reserve_lds<&conv_igemm_kernel<BM, BN, WR, WC, false, BF16, OUT16, STATS, DEEP, BSTATS>>((int)lds, "conv_igemm"))
+        return SP_ELAUNCH;
     if (uniform)
         hipLaunchKernelGGL((conv_igemm_kernel<BM, BN, WR, WC, true, BF16, OUT16, STATS, DEEP, BSTATS>), grid, block, lds, stream, p);
     else
@@ -964,18 +950,8 @@ int launch_abn(const ConvArgs& a, hipStream_t stream) {
     p.tiles_n = a.n_pad / BN;
     const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int) + (size_t)3 * WR * BN * sizeof(float) +
                        (size_t)a.c_in * 4 * sizeof(float);                                   // + the [c_in][4] BatchNorm table
-    static bool opted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        const size_t lds_max = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int) + (size_t)3 * WR * BN * sizeof(float) + 512 * 16;
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_abn_kernel<BM, BN, WR, WC>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                                (int)lds_max) != hipSuccess) {
-            sp_set_error("conv_igemm_abn: hipFuncSetAttribute(max dynamic LDS = %zu) failed on device %d", lds_max, dev);
-            return SP_ELAUNCH;
-        }
-        opted[dev] = true;
-    }
+    const size_t lds_max = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int) + (size_t)3 * WR * BN * sizeof(float) + 512 * 16;
+    if (sp_reserve_lds<&conv_igemm_abn_kernel<BM, BN, WR, WC>>((int)lds_max, "conv_igemm_abn")) return SP_ELAUNCH;   // the largest table, once
     hipLaunchKernelGGL((conv_igemm_abn_kernel<BM, BN, WR, WC>), dim3(p.tiles_m * p.tiles_n, 1, 1), dim3(256, 1, 1), lds, stream, p);
     return sp_check_launch("conv_igemm_abn_kernel");
 }

@@ -299,16 +299,8 @@ __global__ __launch_bounds__(256, 1) void conv_pw_dual_kernel(const PwDualArgs p
 template <int K>
 int launch_pw_dual(const PwDualArgs& a, hipStream_t stream) {
     constexpr int lds = (4 * BM * K + 4 * BM * TRS) * 4;
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_dual_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-        sp_set_error("conv_pw_dual: hipFuncSetAttribute(max dynamic LDS = %d) failed", lds);
-        return SP_ELAUNCH;
-    }
-    int slots = cus / a.nchunks;
+    if (sp_reserve_lds<&conv_pw_dual_kernel<K>>(lds, "conv_pw_dual")) return SP_ELAUNCH;
+    int slots = sp_device_cus() / a.nchunks;
     if (slots < 1) slots = 1;
     if (slots > a.tiles_m) slots = a.tiles_m;
     const int rounds = (a.tiles_m + slots - 1) / slots;
@@ -320,21 +312,9 @@ int launch_pw_dual(const PwDualArgs& a, hipStream_t stream) {
 template <int K>
 int launch_pw(const PwArgs& a, hipStream_t stream) {
     constexpr int lds = (2 * BM * K + 4 * BM * TRS) * 4;
-    static bool opted[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_pw_kernel<K>), hipFuncAttributeMaxDynamicSharedMemorySize, lds) != hipSuccess) {
-            sp_set_error("conv_pw: hipFuncSetAttribute(max dynamic LDS = %d) failed on device %d", lds, dev);
-            return SP_ELAUNCH;
-        }
-        hipDeviceProp_t prop;
-        cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        opted[dev] = true;
-    }
+    if (sp_reserve_lds<&conv_pw_kernel<K>>(lds, "conv_pw")) return SP_ELAUNCH;
     // one workgroup per CU, a multiple of the channel-chunk count, whole rounds of row tiles per workgroup where possible
-    int slots = cus[dev] / a.nchunks;
+    int slots = sp_device_cus() / a.nchunks;
     if (slots < 1) slots = 1;
     if (slots > a.tiles_m) slots = a.tiles_m;
     const int rounds = (a.tiles_m + slots - 1) / slots;

@@ -39,9 +39,6 @@ extern "C" int sp_ring_debug_clear() {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
-
 struct RingArgs {
     const void* x;       // NHWC bf16 activations
     const void* w;       // packed weights [phases][n_pad][k_pad] bf16
@@ -64,29 +61,6 @@ struct RingArgs {
 };
 
 constexpr unsigned OOB = 0x80000000u;   // every tensor is < 2 GiB (host-checked): an offset the range check rejects
-
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, int bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    u32x4 r;                                   // (readfirstlane: an "s" asm operand must be provably wave-uniform)
-    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);      // stride 0: raw buffer
-    r[2] = __builtin_amdgcn_readfirstlane((unsigned)bytes);                    // num_records (bytes)
-    r[3] = 0x00020000u;
-    return r;
-}
-
-// One LDS-DMA piece: 64 lanes x 16 bytes, lane l's bytes from `rsrc` base + voff + soff (zeros when voff is out of range), written
-// to LDS at lds_addr + 16 * l (wave-uniform base in M0).  Inline asm on purpose: hipcc treats the builtin form as an LDS store it
-// must wait for (`s_waitcnt vmcnt(0)` in front of every later LDS access), which would drain the ring at every K tile; issued
-// from asm the transfers are invisible to its bookkeeping and ordered by this file's own counted `s_waitcnt vmcnt(N)` + s_barrier.
-// M0 is written in the statement that uses it (hipcc keeps nothing live in M0 across statements on gfx950, and it does not accept
-// "m0" in a clobber list - "inline asm clobber list contains reserved registers" - so the dependence cannot be declared); `s_nop 4` covers the
-// M0-write -> LDS-DMA and the VALU-written-SGPR -> VMEM wait states, which nothing pads inside an asm statement.
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, u32x4 rsrc, unsigned soff) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, %3 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff),
-                 "s"(rsrc), "s"(__builtin_amdgcn_readfirstlane(soff))
-                 : "memory");
-}
 
 // HAS_RES: a residual tensor is added in the epilogue (compile-time, so that its loads and their use sit on one path: with a run-time
 // test on both, hipcc has to assume a load may still be pending at the next K tile and drains the ring there)
@@ -153,8 +127,8 @@ __global__ __launch_bounds__(64 * (WR * WC + NLW), (WR * WC + NLW) / 4) void con
 
     // descriptors of the two DMA sources as plain SGPR quads: the LDS-DMA is issued from inline asm (below), built from kernel
     // arguments only, so provably wave-uniform
-    const u32x4 xr = make_rsrc(p.x, p.x_bytes);
-    const u32x4 wrs = make_rsrc(p.w, p.w_bytes);
+    const u32x4 xr = sp_make_rsrc(p.x, p.x_bytes);
+    const u32x4 wrs = sp_make_rsrc(p.w, p.w_bytes);
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, p.y_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(HAS_RES ? p.res : p.y), (short)0, p.y_bytes, 0x00020000);
 
@@ -229,10 +203,10 @@ __global__ __launch_bounds__(64 * (WR * WC + NLW), (WR * WC + NLW) / 4) void con
         const unsigned slot = ring_lds + (unsigned)(ld_slot * SB);
         if (o < LA) {
             const unsigned off = (a_mask[o] & t_bit) ? (unsigned)a_off0[o] + t_shift : OOB;
-            dma16(slot + (unsigned)((iw + NIW * o) * 1024), off, xr, 0u);
+            sp_dma16(slot + (unsigned)((iw + NIW * o) * 1024), off, xr, 0u);
         } else {
             const int j = o - LA;
-            dma16(slot + (unsigned)(BM * 128 + (iw + NIW * j) * 1024), b_voff[j], wrs, b_soff);
+            sp_dma16(slot + (unsigned)(BM * 128 + (iw + NIW * j) * 1024), b_voff[j], wrs, b_soff);
         }
     };
     auto loader_advance = [&]() __attribute__((always_inline)) {
@@ -509,17 +483,6 @@ __global__ __launch_bounds__(64 * (WR * WC + NLW), (WR * WC + NLW) / 4) void con
 #endif
 }
 
-int device_cus() {                       // CUs of the current device (cached per device index)
-    static int cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) return 256;
-    if (cache[dev] == 0) {
-        int v = 0;
-        cache[dev] = (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    return cache[dev];
-}
-
 template <int BM, int BN, int WR, int WC, int NS, bool HAS_RES, int NLW>
 int launch_ring_t(const RingArgs& a, hipStream_t stream) {
     if (sp_name_query_active()) {
@@ -531,15 +494,10 @@ int launch_ring_t(const RingArgs& a, hipStream_t stream) {
     p.tiles_n = a.n_pad / BN;
     const int phases = a.total_tiles;     // on entry: number of phases
     p.total_tiles = phases * p.tiles_m * p.tiles_n;
-    const int cus = device_cus();
+    const int cus = sp_device_cus();
     const int grid = p.total_tiles < cus ? p.total_tiles : cus;   // one workgroup per CU (its LDS ring takes the CU's whole LDS)
     const size_t lds = (size_t)NS * (BM + BN) * 128 + (size_t)2 * BM * sizeof(int4);
-    const void* fn = reinterpret_cast<const void*>(&conv_ring_kernel<BM, BN, WR, WC, NS, HAS_RES, NLW>);
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // per device: set before every launch
-    if (e != hipSuccess) {
-        sp_set_error("conv_ring: hipFuncSetAttribute(max dynamic LDS = %zu) failed: %s", lds, hipGetErrorString(e));
-        return SP_ELAUNCH;
-    }
+    if (sp_reserve_lds<&conv_ring_kernel<BM, BN, WR, WC, NS, HAS_RES, NLW>>((int)lds, "conv_ring")) return SP_ELAUNCH;
     hipLaunchKernelGGL((conv_ring_kernel<BM, BN, WR, WC, NS, HAS_RES, NLW>), dim3(grid, 1, 1), dim3(64 * (WR * WC + NLW), 1, 1), lds, stream, p);
     return sp_check_launch("conv_ring_kernel");
 }

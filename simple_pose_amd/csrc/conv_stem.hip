@@ -50,9 +50,6 @@ extern "C" int sp_stem_debug_read(unsigned long long* dst, int n) {
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 struct StemArgs {
     const void* x;             // fp32 [B][3][H][W], or (U8) BGR bytes [B][H][W][3] normalised on the fly: (v / 255 - mean) as datasets/coco.py:136
@@ -399,23 +396,11 @@ __global__ __launch_bounds__(256, BF16 ? 2 : 1) void stem_pool_kernel(const Stem
 template <bool BF16, int TPH, int TPW, bool U8 = false>
 int launch_stem(StemArgs a, hipStream_t stream) {
     using C = Cfg<BF16, TPH, TPW>;
-    static bool opted[64] = {};
-    static int cus[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&stem_pool_kernel<BF16, TPH, TPW, U8>), hipFuncAttributeMaxDynamicSharedMemorySize, C::LDS_BYTES) != hipSuccess) {
-            sp_set_error("stem: hipFuncSetAttribute(max dynamic LDS = %d) failed on device %d", C::LDS_BYTES, dev);
-            return SP_ELAUNCH;
-        }
-        hipDeviceProp_t prop;
-        cus[dev] = hipGetDeviceProperties(&prop, dev) == hipSuccess ? prop.multiProcessorCount : 256;
-        opted[dev] = true;
-    }
+    if (sp_reserve_lds<&stem_pool_kernel<BF16, TPH, TPW, U8>>(C::LDS_BYTES, "stem")) return SP_ELAUNCH;
     a.tiles_y = (a.Hp + TPH - 1) / TPH;
     a.tiles_x = (a.Wp + TPW - 1) / TPW;
     a.n_tiles = a.batch * a.tiles_y * a.tiles_x;
-    const int slots = cus[dev] * (BF16 ? 2 : 1);
+    const int slots = sp_device_cus() * (BF16 ? 2 : 1);
     // whole rounds: every persistent workgroup gets the same number of tiles (4,096 tiles at bs = 128 on 256 CUs: 8 / 16 each)
     const int rounds = (a.n_tiles + slots - 1) / slots;
     const int grid = (a.n_tiles + rounds - 1) / rounds;

@@ -12,7 +12,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int C9 = 128;
 constexpr int T9R = 16, T9C = 12;
@@ -213,13 +212,8 @@ int sp_tile128_launch(const sp_conv_desc* d, const void* x, const void* w_packed
     a.tiles_x = (d->in_w + T9C - 1) / T9C; a.tiles_y = (d->in_h + T9R - 1) / T9R;
     const long long tiles = (long long)d->batch * a.tiles_x * a.tiles_y;
     SP_REQUIRE(tiles < (1ll << 31), "sp_conv3x3_direct: too many tiles");
-    int dev = 0, cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess) {
-        int v = 0;
-        if (hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) cus = v;
-    }
-    const hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv3x3_c128_tile_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS9);
-    if (e != hipSuccess) { sp_set_error("sp_conv3x3_direct: hipFuncSetAttribute(max dynamic LDS = %d) failed: %s", LDS9, hipGetErrorString(e)); return SP_ELAUNCH; }
+    if (sp_reserve_lds<&conv3x3_c128_tile_kernel>(LDS9, "sp_conv3x3_direct")) return SP_ELAUNCH;
+    const int cus = sp_device_cus();
     const long long grid = tiles < cus ? tiles : cus;
     hipLaunchKernelGGL(conv3x3_c128_tile_kernel, dim3((unsigned)grid), dim3(512), LDS9, (hipStream_t)stream, a);
     return sp_check_launch("conv3x3_c128_tile_kernel");

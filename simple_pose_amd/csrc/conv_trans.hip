@@ -19,7 +19,6 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 
 constexpr int TR_ = 32, TC_ = 16;                 // tile: rows x columns of the stride-1 output
 constexpr int HR_ = TR_ + 2, HC_ = TC_ + 2;       // halo 34 x 18
@@ -220,17 +219,6 @@ __global__ __launch_bounds__(512, 2) void hrnet_transition1_kernel(const TransAr
     }
 }
 
-int trans_cus() {
-    static int cache[64];
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!cache[dev]) {
-        hipDeviceProp_t prop;
-        cache[dev] = (hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0) ? prop.multiProcessorCount : 256;
-    }
-    return cache[dev];
-}
-
 }  // namespace
 
 extern "C" int sp_hrnet_transition1_ok(int c_in, int h, int w) { return c_in == CIN && h > 0 && w > 0 && h % 2 == 0 && w % 2 == 0; }
@@ -249,18 +237,9 @@ extern "C" int sp_hrnet_transition1(const void* x, int batch, int h, int w, cons
     a.x_bytes = (int)(in_elems * 2); a.wa_bytes = NA * k_pad * 2; a.wb_bytes = NB * k_pad * 2;
     a.ya_bytes = (int)((long long)batch * h * w * NA * 2); a.yb_bytes = (int)((long long)batch * (h / 2) * (w / 2) * NB * 2);
     if (sp_name_query_active()) { sp_name_query_set("hrnet_transition1_kernel"); return SP_OK; }
-    static bool opted[64] = {};
-    int dev = 0;
-    if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 64) dev = 0;
-    if (!opted[dev]) {
-        if (hipFuncSetAttribute(reinterpret_cast<const void*>(&hrnet_transition1_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, LDS_BYTES) != hipSuccess) {
-            sp_set_error("sp_hrnet_transition1: hipFuncSetAttribute(max dynamic LDS = %d) failed", LDS_BYTES);
-            return SP_ELAUNCH;
-        }
-        opted[dev] = true;
-    }
-    const int tiles = batch * a.tiles_y * a.tiles_x;
-    const int grid = tiles < trans_cus() ? tiles : trans_cus();
+    if (sp_reserve_lds<&hrnet_transition1_kernel>(LDS_BYTES, "sp_hrnet_transition1")) return SP_ELAUNCH;
+    const int tiles = batch * a.tiles_y * a.tiles_x, cus = sp_device_cus();
+    const int grid = tiles < cus ? tiles : cus;
     hipLaunchKernelGGL(hrnet_transition1_kernel, dim3(grid), dim3(512), LDS_BYTES, (hipStream_t)stream, a);
     return sp_check_launch("hrnet_transition1_kernel");
 }

@@ -29,10 +29,8 @@
 
 namespace {
 
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef short s16x4 __attribute__((ext_vector_type(4)));
 typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __attribute__((address_space(3))) void lds_void_t;
 typedef __attribute__((address_space(3))) s16x4 lds_s16x4;
 
 constexpr int WG_MAXJ = 16;              // layers per launch (kernel-argument table)
@@ -62,25 +60,6 @@ struct WgArgs {
     int n_layers;
     int units;           // units of the launch (>= gridDim.x: a workgroup walks units blockIdx.x, blockIdx.x + gridDim.x, ...)
 };
-
-__device__ __forceinline__ u32x4 make_rsrc(const void* base, unsigned bytes) {
-    const unsigned long long a = reinterpret_cast<unsigned long long>(base);
-    u32x4 r;                                   // (readfirstlane: an "s" asm operand must be provably wave-uniform)
-    r[0] = __builtin_amdgcn_readfirstlane((unsigned)a);
-    r[1] = __builtin_amdgcn_readfirstlane((unsigned)(a >> 32) & 0xffffu);      // stride 0: raw buffer
-    r[2] = __builtin_amdgcn_readfirstlane(bytes);                              // num_records (bytes)
-    r[3] = 0x00020000u;
-    return r;
-}
-
-// One LDS-DMA piece (see csrc/conv_ring.hip): 64 lanes x 16 bytes, lane l's bytes from `rsrc` base + voff (zeros when voff is out of
-// range), written to LDS at lds_addr + 16 * l.  Issued from inline asm so that hipcc does not drain the ring in front of every LDS read;
-// ordered by this file's own counted `s_waitcnt vmcnt(N)` + s_barrier.
-__device__ __forceinline__ void dma16(unsigned lds_addr, unsigned voff, u32x4 rsrc) {
-    asm volatile("s_mov_b32 m0, %0\n\ts_nop 4\n\tbuffer_load_dwordx4 %1, %2, 0 offen lds" ::"s"(__builtin_amdgcn_readfirstlane(lds_addr)), "v"(voff),
-                 "s"(rsrc)
-                 : "memory");   // (hipcc rejects "m0" in a clobber list: reserved register; it keeps nothing live in M0 across statements)
-}
 
 __device__ __forceinline__ int fdiv(int n, unsigned magic, int sh) {
     const int q = (int)(__umulhi((unsigned)n, magic) >> sh);      // (computed either way: a select, not a branch, inside the stage loop)
@@ -121,9 +100,9 @@ __device__ __forceinline__ void wgrad_unit(const WgLayer& p, const int tg, const
 
     // the G descriptor ends at this unit's last pixel: rows beyond m_end read as zeros without a per-lane test (same for a plain A)
     const long long g_end = (long long)m_end * p.n_ld * EB;
-    const u32x4 gr = make_rsrc(p.g, (unsigned)(g_end < p.g_bytes ? g_end : p.g_bytes));
+    const u32x4 gr = sp_make_rsrc(p.g, (unsigned)(g_end < p.g_bytes ? g_end : p.g_bytes));
     const long long a_end = (long long)m_end * p.c_in * EB;
-    const u32x4 ar = make_rsrc(p.a, (unsigned)((p.plain_a && a_end < p.a_bytes) ? a_end : p.a_bytes));
+    const u32x4 ar = sp_make_rsrc(p.a, (unsigned)((p.plain_a && a_end < p.a_bytes) ? a_end : p.a_bytes));
 
     // chunk swizzle of a bf16 image: physical 64-byte segment s of row r holds logical segment s ^ f(r) (inside aligned groups of four
     // segments; rows of 128 bytes have two segments and flip on bit 1 of r): the four rows of a transposing read hit disjoint banks
@@ -162,7 +141,7 @@ __device__ __forceinline__ void wgrad_unit(const WgLayer& p, const int tg, const
     auto loader_piece = [&](int o) __attribute__((always_inline)) {   // o in [0, L): one 1-KiB piece of the stage at pixel ld_m0
         const unsigned slot = ring_lds + (unsigned)(ld_slot * SB);
         if (o < LG) {
-            dma16(slot + (unsigned)((wave + 8 * o) * 1024), g_voff[o] + (unsigned)(ld_m0 * n_ld * EB), gr);
+            sp_dma16(slot + (unsigned)((wave + 8 * o) * 1024), g_voff[o] + (unsigned)(ld_m0 * n_ld * EB), gr);
         } else {
             const int j = o - LG;
             unsigned off;
@@ -177,7 +156,7 @@ __device__ __forceinline__ void wgrad_unit(const WgLayer& p, const int tg, const
                 const unsigned addr = (unsigned)(((b * in_h + iy) * in_w + ix) * c_in * EB + a_coff[j]);
                 off = ok ? addr : OOB;
             }
-            dma16(slot + (unsigned)(SBG + (wave + 8 * j) * 1024), off, ar);
+            sp_dma16(slot + (unsigned)(SBG + (wave + 8 * j) * 1024), off, ar);
         }
     };
     auto loader_advance = [&]() __attribute__((always_inline)) {
@@ -523,12 +502,7 @@ int launch_group(const WgArgs& a, int units, hipStream_t s) {
         const size_t need = (size_t)t.ns * t.pix_bf16 * (t.tg + t.ta) * 2;     // (fp32: half the pixels of twice the bytes)
         if (need > lds) lds = need;
     }
-    const void* fn = reinterpret_cast<const void*>(&conv_wgrad_group_kernel<BF16>);
-    const hipError_t e = hipFuncSetAttribute(fn, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);   // per device: set before every launch
-    if (e != hipSuccess) {
-        sp_set_error("conv_wgrad: hipFuncSetAttribute(max dynamic LDS = %zu) failed: %s", lds, hipGetErrorString(e));
-        return SP_ELAUNCH;
-    }
+    if (sp_reserve_lds<&conv_wgrad_group_kernel<BF16>>((int)lds, "conv_wgrad")) return SP_ELAUNCH;     // (grows with the largest tile seen)
     static const int cap = getenv("SP_WGRAD_GRID_CAP") ? atoi(getenv("SP_WGRAD_GRID_CAP")) : 0;      // (env: development knob; 0 = one workgroup per unit)
     WgArgs b = a;
     b.units = units;

@@ -5,12 +5,7 @@
 #include <stdio.h>
 
 #include "simple_pose_hip.h"
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
-
-#define SP_WAVE 64
+#include "sp_device.h"
 
 // ---- error plumbing (thread-local message, never throws across the C boundary) ----------------
 void sp_set_error(const char* fmt, ...);
@@ -33,6 +28,24 @@ void sp_name_query_set(const char* fmt, ...);
     } while (0)
 
 static inline int sp_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- launch helpers (the ONE place these two rules live; every launcher goes through them) -------
+// CUs of the current device, cached per device index; 256 (the MI355X) when the query fails or the index is outside the cache.
+int sp_device_cus();
+
+// > 64 KiB of dynamic LDS needs an explicit opt-in, once per kernel instantiation AND per device (the attribute belongs to the
+// function on the device that is current: a process driving several GPUs must not inherit device 0's opt-in).  `reserved` holds
+// what the kernel has been granted per device index; the attribute is set only when `bytes` exceeds it, so a kernel whose LDS
+// size depends on the shape grows its reservation and a fixed-size one pays one hipGetDevice per launch.  A benign race: two
+// threads may both set the same attribute, and the larger request is simply made again by whoever finds the smaller one recorded.
+// On failure: sp_set_error (`what`, the bytes, the device, the runtime's message) and SP_ELAUNCH.
+int sp_reserve_lds_for(const void* kernel, int* reserved, int bytes, const char* what);
+
+template <auto Kernel>
+int sp_reserve_lds(int bytes, const char* what) {
+    static int reserved[64];
+    return sp_reserve_lds_for(reinterpret_cast<const void*>(Kernel), reserved, bytes, what);
+}
 
 // ---- device helpers ------------------------------------------------------------------------------
 // torch.max semantics: larger value wins, NaN beats everything, ties -> lower index.

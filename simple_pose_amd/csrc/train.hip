@@ -7,8 +7,6 @@
 namespace {
 
 
-typedef __bf16 bf16x4 __attribute__((ext_vector_type(4)));
-typedef unsigned int u32x2 __attribute__((ext_vector_type(2)));
 
 // 4 consecutive channels of an NHWC tensor, fp32 (16 B) or bf16 (8 B), as floats; i4 = index in units of 4 channels
 template <bool BF16>
@@ -58,11 +56,6 @@ static int red_blocks(long long rows, int c) {
     const long long cap = (262144 / c) < 1024 ? (262144 / c) : 1024;
     if (n > cap) n = cap;
     return (int)(n < 1 ? 1 : n);
-}
-
-inline int grid_for(long long total, int block) {
-    long long g = (total + block - 1) / block;
-    return (int)(g < 1 ? 1 : (g > 2048 ? 2048 : g));
 }
 
 // ---------------------------------------------------------------------------------------------------------------
@@ -1344,14 +1337,14 @@ extern "C" int sp_bn_apply_nhwc(const void* z, int bf16, const float* mean, cons
     SP_REQUIRE(rows > 0 && c > 0 && c % 4 == 0, "sp_bn_apply_nhwc: bad shape");
     if ((bf16 & 1) && c % 8 == 0) {
         const long long total = rows * (c / 8);
-        hipLaunchKernelGGL((bn_apply_kernel<true, 8>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, residual, y,
+        hipLaunchKernelGGL((bn_apply_kernel<true, 8>), dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, residual, y,
                            c / 8, relu, total, reinterpret_cast<unsigned char*>(relu_mask));
         return sp_check_launch("bn_apply_kernel");
     }
     const long long total = rows * (c / 4);
-    if (bf16 & 1) hipLaunchKernelGGL((bn_apply_kernel<true, 4>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta,
+    if (bf16 & 1) hipLaunchKernelGGL((bn_apply_kernel<true, 4>), dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta,
                                      residual, y, c / 4, relu, total, (unsigned char*)nullptr);
-    else hipLaunchKernelGGL((bn_apply_kernel<false, 4>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta,
+    else hipLaunchKernelGGL((bn_apply_kernel<false, 4>), dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta,
                             residual, y, c / 4, relu, total, (unsigned char*)nullptr);
     return sp_check_launch("bn_apply_kernel");
 }
@@ -1363,9 +1356,9 @@ extern "C" int sp_bn_apply_sums_nhwc(const void* z, int bf16, const double* sums
     SP_REQUIRE(rows > 0 && total_rows > 0 && c > 0 && c % 4 == 0, "sp_bn_apply_sums_nhwc: bad shape");
     SP_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "sp_bn_apply_sums_nhwc: running stats come in pairs");
     const long long total = rows * (c / 4);
-    if (bf16 & 1) hipLaunchKernelGGL(bn_apply_sums_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, sums, (double)total_rows, eps,
+    if (bf16 & 1) hipLaunchKernelGGL(bn_apply_sums_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, sums, (double)total_rows, eps,
                                      momentum, gamma, beta, residual, y, c / 4, relu, total, mean, invstd, running_mean, running_var);
-    else hipLaunchKernelGGL(bn_apply_sums_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, sums, (double)total_rows, eps,
+    else hipLaunchKernelGGL(bn_apply_sums_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, sums, (double)total_rows, eps,
                             momentum, gamma, beta, residual, y, c / 4, relu, total, mean, invstd, running_mean, running_var);
     return sp_check_launch("bn_apply_sums_kernel");
 }
@@ -1398,7 +1391,7 @@ extern "C" int sp_bn_train_bwd_apply_nhwc(const void* dy, int bf16, const void* 
     SP_REQUIRE(!src_is_mask || (vw == 8 && relu_src), "sp_bn_train_bwd_apply_nhwc: a ReLU bit mask goes with bf16 activations (c %% 8 == 0)");
     const long long total = rows * (c / vw);
 #define SP_BWD_APPLY(A, G, V)                                                                                                                \
-    hipLaunchKernelGGL((bn_bwd_apply_kernel<A, G, V>), dim3(grid_for(total, 256)), dim3(256), 0, s, dy, relu_src, z, mean, invstd, gamma, sum_dgamma, \
+    hipLaunchKernelGGL((bn_bwd_apply_kernel<A, G, V>), dim3(sp_grid_for(total, 256)), dim3(256), 0, s, dy, relu_src, z, mean, invstd, gamma, sum_dgamma, \
                        sum_dbeta, (float)(1.0 / (double)total_rows), dz, dres, dres_accumulate, c / V, total, src_is_mask)
     if (a16 && g16 && vw == 8) SP_BWD_APPLY(true, true, 8);
     else if (a16 && g16) SP_BWD_APPLY(true, true, 4);
@@ -1487,7 +1480,7 @@ extern "C" int sp_maxpool3x3s2_bwd_nhwc(const void* x, int bf16, const void* dy,
     SP_REQUIRE(total * 4 < (1ll << 31), "sp_maxpool3x3s2_bwd_nhwc: tensor too large");
     const bool a16 = bf16 & 1, g16 = bf16 & 2;
 #define SP_POOL_BWD(A, G) \
-    hipLaunchKernelGGL((maxpool3x3s2_bwd_kernel<A, G>), dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, h, w, c / 4, ho, wo, total)
+    hipLaunchKernelGGL((maxpool3x3s2_bwd_kernel<A, G>), dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, dy, dx, h, w, c / 4, ho, wo, total)
     if (a16 && g16) SP_POOL_BWD(true, true);
     else if (a16) SP_POOL_BWD(true, false);
     else SP_POOL_BWD(false, false);
@@ -1501,9 +1494,9 @@ extern "C" int sp_maxpool3x3s2_idx_nhwc(const void* x, int bf16, void* y, void* 
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
     const long long total = (long long)batch * ho * wo * (c / 4);
     SP_REQUIRE((long long)batch * h * w * c < (1ll << 31), "sp_maxpool3x3s2_idx_nhwc: tensor too large");
-    if (bf16 & 1) hipLaunchKernelGGL(maxpool3x3s2_idx_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y,
+    if (bf16 & 1) hipLaunchKernelGGL(maxpool3x3s2_idx_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y,
                                  reinterpret_cast<unsigned int*>(idx), h, w, c / 4, ho, wo, total);
-    else hipLaunchKernelGGL(maxpool3x3s2_idx_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y,
+    else hipLaunchKernelGGL(maxpool3x3s2_idx_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y,
                             reinterpret_cast<unsigned int*>(idx), h, w, c / 4, ho, wo, total);
     return sp_check_launch("maxpool3x3s2_idx_kernel");
 }
@@ -1514,9 +1507,9 @@ extern "C" int sp_maxpool3x3s2_bwd_idx_nhwc(const void* idx, const void* dy, int
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
     const long long total = (long long)batch * h * w * (c / 4);
     SP_REQUIRE(total * 4 < (1ll << 31), "sp_maxpool3x3s2_bwd_idx_nhwc: tensor too large");
-    if (bf16 & 2) hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    if (bf16 & 2) hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                                  reinterpret_cast<const unsigned int*>(idx), dy, dx, h, w, c / 4, ho, wo, total);
-    else hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    else hipLaunchKernelGGL(maxpool3x3s2_bwd_idx_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                             reinterpret_cast<const unsigned int*>(idx), dy, dx, h, w, c / 4, ho, wo, total);
     return sp_check_launch("maxpool3x3s2_bwd_idx_kernel");
 }
@@ -1528,9 +1521,9 @@ extern "C" int sp_bn_apply_maxpool_nhwc(const void* z, int bf16, const float* me
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
     const long long total = (long long)batch * ho * wo * (c / 4);
     SP_REQUIRE((long long)batch * h * w * c < (1ll << 31), "sp_bn_apply_maxpool_nhwc: tensor too large");
-    if (bf16 & 1) hipLaunchKernelGGL(bn_apply_maxpool_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, y,
+    if (bf16 & 1) hipLaunchKernelGGL(bn_apply_maxpool_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, y,
                                      reinterpret_cast<unsigned int*>(idx), h, w, c / 4, ho, wo, total);
-    else hipLaunchKernelGGL(bn_apply_maxpool_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, y,
+    else hipLaunchKernelGGL(bn_apply_maxpool_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, z, mean, invstd, gamma, beta, y,
                             reinterpret_cast<unsigned int*>(idx), h, w, c / 4, ho, wo, total);
     return sp_check_launch("bn_apply_maxpool_kernel");
 }
@@ -1558,7 +1551,7 @@ extern "C" int sp_bn_maxpool_bwd_nhwc(const void* dy_pooled, int bf16, const voi
 #undef SP_SPR
     hipLaunchKernelGGL(pair_sum_final_kernel, dim3((c + 3) / 4), dim3(256), 0, s, part, nblk, c, dbeta, dgamma);
     const float inv_m = (float)(1.0 / (double)rows);
-#define SP_SPA(A, G, V) hipLaunchKernelGGL((stem_pool_bwd_apply_kernel<A, G, V>), dim3(grid_for(total * 4 / V, 256)), dim3(256), 0, s, dy_pooled, ix, z, mean, invstd, gamma, beta, dgamma, dbeta, inv_m, dz, h, w, c / V, ho, wo, total * 4 / V)
+#define SP_SPA(A, G, V) hipLaunchKernelGGL((stem_pool_bwd_apply_kernel<A, G, V>), dim3(sp_grid_for(total * 4 / V, 256)), dim3(256), 0, s, dy_pooled, ix, z, mean, invstd, gamma, beta, dgamma, dbeta, inv_m, dz, h, w, c / V, ho, wo, total * 4 / V)
     if (a16 && g16 && c % 8 == 0 && wide) SP_SPA(true, true, 8); else if (a16 && g16) SP_SPA(true, true, 4); else if (a16) SP_SPA(true, false, 4); else SP_SPA(false, false, 4);
 #undef SP_SPA
     return sp_check_launch("sp_bn_maxpool_bwd_nhwc");
@@ -1570,9 +1563,9 @@ extern "C" int sp_nchw_to_nhwc_pad(const float* x, void* y, int y_bf16, int batc
                channels, c_pad);
     const long long total = (long long)batch * h * w * (c_pad / 4);
     SP_REQUIRE(total * 4 < (1ll << 31), "sp_nchw_to_nhwc_pad: tensor too large");
-    if (y_bf16) hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, channels, h * w,
+    if (y_bf16) hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, channels, h * w,
                                c_pad / 4, total);
-    else hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, channels, h * w,
+    else hipLaunchKernelGGL(nchw_to_nhwc_pad_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, x, y, channels, h * w,
                             c_pad / 4, total);
     return sp_check_launch("nchw_to_nhwc_pad_kernel");
 }
@@ -1589,7 +1582,7 @@ extern "C" int sp_adam_step(float* param, const float* grad, float* exp_avg, flo
                             double beta2, double eps, int step, float grad_scale, void* stream) {
     SP_REQUIRE(param && grad && exp_avg && exp_avg_sq, "sp_adam_step: null pointer");
     SP_REQUIRE(n > 0 && n % 4 == 0 && step >= 1, "sp_adam_step: n=%lld must be a positive multiple of 4 and step >= 1", (long long)n);
-    hipLaunchKernelGGL(adam_kernel<false>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<f32x4*>(param),
+    hipLaunchKernelGGL(adam_kernel<false>, dim3(sp_grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<f32x4*>(param),
                        reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(exp_avg), reinterpret_cast<f32x4*>(exp_avg_sq), n / 4,
                        adam_scalars(lr, beta1, beta2, eps, step, grad_scale), nullptr);
     return sp_check_launch("adam_kernel");
@@ -1607,7 +1600,7 @@ extern "C" int sp_adam_set_scalars(double lr, double beta1, double beta2, double
 extern "C" int sp_adam_step_dev(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, const float* scalars8, void* stream) {
     SP_REQUIRE(param && grad && exp_avg && exp_avg_sq && scalars8, "sp_adam_step_dev: null pointer");
     SP_REQUIRE(n > 0 && n % 4 == 0, "sp_adam_step_dev: n=%lld must be a positive multiple of 4", (long long)n);
-    hipLaunchKernelGGL(adam_kernel<true>, dim3(grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<f32x4*>(param),
+    hipLaunchKernelGGL(adam_kernel<true>, dim3(sp_grid_for(n / 4, 256)), dim3(256), 0, (hipStream_t)stream, reinterpret_cast<f32x4*>(param),
                        reinterpret_cast<const f32x4*>(grad), reinterpret_cast<f32x4*>(exp_avg), reinterpret_cast<f32x4*>(exp_avg_sq), n / 4,
                        AdamScalars{}, reinterpret_cast<const AdamScalars*>(scalars8));
     return sp_check_launch("adam_kernel");
@@ -1715,9 +1708,9 @@ extern "C" int sp_se_gate_bwd_apply(const float* dy, int bf16, const void* y, co
     SP_REQUIRE(dy && y && gate_logits && ds && du && dres && batch > 0 && hw > 0 && c > 0, "sp_se_gate_bwd_apply: bad argument");
     const long long total = (long long)batch * hw * c;
     SP_REQUIRE(total < (1ll << 31), "sp_se_gate_bwd_apply: tensor too large");
-    if (bf16) hipLaunchKernelGGL(se_gate_bwd_apply_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, y, gate_logits, ds, hw,
+    if (bf16) hipLaunchKernelGGL(se_gate_bwd_apply_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, y, gate_logits, ds, hw,
                                  c, 1.f / (float)hw, du, dres, dres_accumulate, total);
-    else hipLaunchKernelGGL(se_gate_bwd_apply_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, y, gate_logits, ds, hw, c,
+    else hipLaunchKernelGGL(se_gate_bwd_apply_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, dy, y, gate_logits, ds, hw, c,
                             1.f / (float)hw, du, dres, dres_accumulate, total);
     return sp_check_launch("se_gate_bwd_apply_kernel");
 }
@@ -1763,10 +1756,10 @@ extern "C" int sp_upsample_add_bwd_nhwc(const float* dy, int bf16, const void* y
     SP_REQUIRE(dbase != dx, "sp_upsample_add_bwd_nhwc: the two gradients must be different tensors");
     const long long total = (long long)batch * h * w * (c / 4);
     SP_REQUIRE(total * factor * factor * 4 < (1ll << 31), "sp_upsample_add_bwd_nhwc: tensor too large");
-    if (bf16) hipLaunchKernelGGL(upsample_add_bwd_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    if (bf16) hipLaunchKernelGGL(upsample_add_bwd_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                                  reinterpret_cast<const f32x4*>(dy), y_relu_src, h, w, c / 4, factor, reinterpret_cast<f32x4*>(dbase), dbase_accumulate,
                                  reinterpret_cast<f32x4*>(dx), dx_accumulate, total);
-    else hipLaunchKernelGGL(upsample_add_bwd_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
+    else hipLaunchKernelGGL(upsample_add_bwd_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream,
                             reinterpret_cast<const f32x4*>(dy), y_relu_src, h, w, c / 4, factor, reinterpret_cast<f32x4*>(dbase), dbase_accumulate,
                             reinterpret_cast<f32x4*>(dx), dx_accumulate, total);
     return sp_check_launch("upsample_add_bwd_kernel");
@@ -1795,7 +1788,7 @@ extern "C" int sp_permute4_f32(const float* src, void* dst, int dst_bf16, const 
         total *= dst_dims[i];
     }
     pm.base = src_base; pm.dst_off = dst_offset;
-    if (dst_bf16) hipLaunchKernelGGL(permute4_kernel<true>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, pm, total);
-    else hipLaunchKernelGGL(permute4_kernel<false>, dim3(grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, pm, total);
+    if (dst_bf16) hipLaunchKernelGGL(permute4_kernel<true>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, pm, total);
+    else hipLaunchKernelGGL(permute4_kernel<false>, dim3(sp_grid_for(total, 256)), dim3(256), 0, (hipStream_t)stream, src, dst, pm, total);
     return sp_check_launch("permute4_kernel");
 }

@@ -780,3 +780,27 @@ def test_grouped_conv_forward_dgrad_wgrad_against_float64(C, groups, stride, B, 
     layer.wgrad_grouped(xg, dzg, B)
     torch.cuda.synchronize()
     assert torch.equal(first, flat.view("g.weight", grad=True))
+
+
+def test_grouped_wgrad_staging_tile_grows_past_64k_within_one_process():
+    """The dynamic-LDS reservation of a kernel is raised when a later call needs more than any earlier one (sp_reserve_lds): two
+    sp_conv2d_wgrad_grouped calls on ONE kernel instantiation (fp32, 3x3, group width 16: a staging tile of 256 * in_w + 384 bytes), first a row
+    of 8 pixels (2,432 bytes), then one of 300 (77,184 bytes: above the 64 KiB a kernel gets without opting in, below the 160 KiB cap).  A
+    reservation remembered from the first call would make the second launch fail with SP_ELAUNCH.  Both against float64, as above."""
+    lib, st = _lib.lib(), _lib.current_stream()
+    C, groups, B, H = 64, 4, 1, 3
+    cpg = C // groups
+    for W in (8, 300):
+        assert (256 * W + 384 < 64 * 1024) == (W == 8) and 256 * W + 384 <= 160 * 1024
+        x = torch.from_numpy(synth.tensor_normal(7, f"gw{W}/x", (B, C, H, W)))
+        dz = torch.from_numpy(synth.tensor_normal(7, f"gw{W}/dz", (B, C, H, W)))
+        wd = torch.zeros(C, cpg, 3, 3, dtype=torch.float64, requires_grad=True)
+        F.conv2d(x.double(), wd, padding=1, groups=groups).backward(dz.double())
+        need = ctypes.c_int64(0)
+        _lib.check(lib.sp_conv2d_wgrad_grouped_workspace(B, H, C, groups, 3, 3, ctypes.byref(need)))
+        ws = torch.empty((need.value + 3) // 4, dtype=torch.float32, device=DEV)
+        dw = torch.full((C, cpg, 3, 3), float("nan"), device=DEV)
+        xg, dzg = (t.permute(0, 2, 3, 1).contiguous().to(DEV) for t in (x, dz))
+        _lib.check(lib.sp_conv2d_wgrad_grouped(P(xg), P(dzg), 0, B, H, W, H, W, C, groups, 3, 3, 1, 1, P(dw), P(ws), ws.numel() * 4, st), f"in_w={W}")
+        torch.cuda.synchronize()
+        assert float((dw.cpu().double() - wd.grad).abs().max() / wd.grad.abs().max()) < 2e-5

@@ -2183,3 +2183,79 @@ def test_kernels_kept_for_same_box_ab_still_match(knob, selector):
     r = subprocess.run([sys.executable, "-m", "pytest", os.path.join(root, "tests", "test_gpu_parity.py"), "-x", "-q", "-m", "gpu", "-k", selector],
                        env=env, capture_output=True, text=True, timeout=600, cwd=root)
     assert r.returncode == 0 and " passed" in r.stdout, r.stdout[-2000:] + r.stderr[-2000:]
+
+
+# ---------------------------------------------------------------------------------------------- pointwise pairs, straight through the C ABI
+@pytest.mark.parametrize("bf16", [False, True], ids=["fp32", "bf16"])
+def test_pointwise_pairs_through_the_c_abi(bf16):
+    """Every pointwise kernel that exists for both dtypes (one `template <bool BF16>` kernel each, csrc/pointwise.hip), called directly: B=2 on
+    ragged 5 x 7 maps, C=32 (the smallest C the bf16 pixel shuffle takes).  Expected values: torch on the CPU in fp32, rounded to bf16 once
+    where the output is bf16 - exact for maxpool (one NaN, one -inf among the inputs), pixel shuffle / unshuffle, upsample_add (x2, x4) and the
+    NCHW -> NHWC conversions; global_avg_pool and se_gate_add_relu against float64 within the bars of the SE net tests above (1e-4 fp32,
+    2e-2 bf16, of the largest value).  Bad arguments are refused by name."""
+    F = torch.nn.functional
+    lib, P, st = _lib.lib(), _lib.ptr, _lib.current_stream()
+    sfx, dt, V = ("_bf16", torch.bfloat16, 8) if bf16 else ("", torch.float32, 4)
+    fn = lambda name: getattr(lib, name + sfx)
+    B, H, W, C = 2, 5, 7, 32
+    g = torch.Generator().manual_seed(11)
+    rnd = lambda *s: torch.randn(*s, generator=g).to(dt)
+    out = lambda *s: torch.full(s, float("nan"), dtype=dt, device=DEV)
+
+    def refused(rc, prefix):
+        assert rc != 0 and lib.sp_last_error().decode().startswith(prefix), lib.sp_last_error()
+
+    # maxpool 3x3 / 2 / 1: NaN wins its windows, -inf loses
+    x = rnd(B, H, W, C)
+    x[0, 2, 3, 5], x[1, 0, 0, 9] = float("nan"), float("-inf")
+    y = out(B, 3, 4, C)
+    xg = x.to(DEV)                                     # (device copies are held in names: a temporary's block is reused by the next one)
+    _lib.check(fn("sp_maxpool3x3s2_nhwc")(P(xg), P(y), B, H, W, C, st))
+    ref = F.max_pool2d(x.float().permute(0, 3, 1, 2), 3, 2, 1).permute(0, 2, 3, 1).to(dt)
+    assert torch.isnan(ref).any() and torch.equal(torch.isnan(y.cpu()), torch.isnan(ref)) and torch.equal(y.cpu().nan_to_num(nan=77.), ref.nan_to_num(nan=77.))
+    refused(fn("sp_maxpool3x3s2_nhwc")(P(y), P(y), B, H, W, C + 2, st), f"sp_maxpool3x3s2_nhwc{sfx}: bad shape")
+    # pixel shuffle and its backward
+    x = rnd(B, H, W, C)
+    y = out(B, 2 * H, 2 * W, C // 4)
+    xg = x.to(DEV)
+    _lib.check(fn("sp_pixel_shuffle2_nhwc")(P(xg), P(y), B, H, W, C, st))
+    assert torch.equal(y.cpu(), F.pixel_shuffle(x.float().permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1).to(dt))
+    back = out(B, H, W, C)
+    _lib.check(fn("sp_pixel_unshuffle2_nhwc")(P(y), P(back), B, H, W, C, st))
+    assert torch.equal(back.cpu(), x)
+    refused(fn("sp_pixel_shuffle2_nhwc")(P(y), P(back), B, H, W, 2 * V, st), f"sp_pixel_shuffle2_nhwc{sfx}: c={2 * V} must be a multiple of {4 * V}")
+    refused(fn("sp_pixel_unshuffle2_nhwc")(P(y), P(back), B, H, W, 2 * V, st), f"sp_pixel_unshuffle2_nhwc{sfx}: c={2 * V} must be a multiple of {4 * V}")
+    # nearest upsample + add (+ relu)
+    for f, relu in ((2, 0), (4, 1)):
+        x, base = rnd(B, H, W, C), rnd(B, H * f, W * f, C)
+        y = out(B, H * f, W * f, C)
+        xg, bg = x.to(DEV), base.to(DEV)
+        _lib.check(fn("sp_upsample_add_nhwc")(P(xg), P(bg), P(y), B, H, W, C, f, relu, st))
+        ref = base.float() + x.float().repeat_interleave(f, 1).repeat_interleave(f, 2)
+        assert torch.equal(y.cpu(), (ref.clamp(min=0) if relu else ref).to(dt))
+    refused(fn("sp_upsample_add_nhwc")(P(y), P(y), P(y), B, H, W, C + 2, 2, 0, st), f"sp_upsample_add_nhwc{sfx}: bad shape")
+    # NCHW fp32 image -> NHWC with zero tail channels
+    img = torch.randn(B, 3, H, W + 1, generator=g)
+    for name, cv, odt, w in (("sp_nchw_to_nhwc4", 4, torch.float32, W), ("sp_nchw_to_nhwc4", 4, torch.float32, W + 1)) if not bf16 else \
+            (("sp_nchw_to_nhwc8_bf16", 8, dt, W), ("sp_nchw_to_nhwc4_bf16", 4, dt, W + 1)):
+        src = img[..., :w].contiguous()
+        y = torch.full((B, H, w, cv), float("nan"), dtype=odt, device=DEV)
+        xg = src.to(DEV)
+        _lib.check(getattr(lib, name)(P(xg), P(y), B, 3, H, w, st))
+        assert torch.equal(y.cpu(), F.pad(src.permute(0, 2, 3, 1), (0, cv - 3)).to(odt))
+        refused(getattr(lib, name)(P(xg), P(y), B, 9, H, w, st), name + ": bad shape")
+    if bf16:
+        refused(lib.sp_nchw_to_nhwc4_bf16(P(y), P(y), B, 3, H, W, st), "sp_nchw_to_nhwc4_bf16: bad shape")          # odd width
+    # SE squeeze and excite against float64
+    bar = 2e-2 if bf16 else 1e-4
+    x, gate, idn = rnd(B, H * W, C), rnd(B, C), rnd(B, H * W, C)
+    sq, y = out(B, C), out(B, H * W, C)
+    xg, gg, ig = x.to(DEV), gate.to(DEV), idn.to(DEV)
+    _lib.check(fn("sp_global_avg_pool_nhwc")(P(xg), P(sq), B, H * W, C, st))
+    _lib.check(fn("sp_se_gate_add_relu_nhwc")(P(xg), P(gg), P(ig), P(y), B, H * W, C, st))
+    ref = x.double().mean(1)
+    assert float((sq.cpu().double() - ref).abs().max() / ref.abs().max()) <= bar
+    ref = torch.relu(x.double() * torch.sigmoid(gate.double())[:, None, :] + idn.double())
+    assert float((y.cpu().double() - ref).abs().max() / ref.abs().max()) <= bar
+    refused(fn("sp_global_avg_pool_nhwc")(P(y), P(sq), B, H * W, C + 2, st), f"sp_global_avg_pool_nhwc{sfx}: bad shape")
+    refused(fn("sp_se_gate_add_relu_nhwc")(P(y), P(sq), P(y), P(y), B, H * W, C + 2, st), f"sp_se_gate_add_relu_nhwc{sfx}: bad shape")

@@ -24,7 +24,7 @@ def main():
     for r in rows:
         r["s"], r["e"] = int(r["Start_Timestamp"]), int(r["End_Timestamp"])
     rows.sort(key=lambda r: r["s"])
-    marks = [i for i, r in enumerate(rows) if "nchw_to_nhwc8_bf16_kernel" in r["Kernel_Name"] or "nchw_to_nhwc4_kernel" in r["Kernel_Name"]]
+    marks = [i for i, r in enumerate(rows) if "nchw_to_nhwc_kernel<true, 8>" in r["Kernel_Name"] or "nchw_to_nhwc_kernel<false, 4>" in r["Kernel_Name"]]
     lo, hi = marks[args.step], marks[args.step + 1]
     step = rows[lo:hi]
     t0, t1 = step[0]["s"], max(r["e"] for r in step)
