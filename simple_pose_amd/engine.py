@@ -21,8 +21,9 @@ from typing import Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, conv_geometry
 from ._lib import ConvDesc, SP_CONV_BF16, SP_CONV_HARDSWISH, SP_CONV_OUT_NCHW, SP_CONV_OUT_SLICE, SP_CONV_PIXEL_SHUFFLE, SP_CONV_RELU
+from .conv_geometry import n_pad_for, round_up as _round_up
 
 BN_EPS = 1e-5
 
@@ -30,19 +31,6 @@ BN_EPS = 1e-5
 # ------------------------------------------------------------------------------------------------
 # weight packing: device kernels behind the C ABI (csrc/pack.hip)
 # ------------------------------------------------------------------------------------------------
-def _round_up(v: int, m: int) -> int:
-    return (v + m - 1) // m * m
-
-
-def n_pad_for(c_out: int) -> int:
-    """Packed row count: the kernel's N tile must divide it (128 / 64 / 32 wide tiles)."""
-    if c_out >= 128:
-        return _round_up(c_out, 128)
-    if c_out > 32:
-        return _round_up(c_out, 64)
-    return 32
-
-
 class HipPacker:
     """Reference-layout parameters -> kernel layouts ON THE GPU through the C ABI (sp_pack_conv_weights, sp_pack_deconv_k4s2p1,
     sp_fold_bn, sp_conv_packed_dims): the same entry points a maintainer binding include/simple_pose_hip.h would call.  Tensors must
@@ -904,26 +892,21 @@ class ProgramBuilder:
         buffer made by `buffer()` (SP_CONV_OUT_SLICE: the producers of a concat fill their slices, nothing is copied)."""
         h, w, c_buf = self.p.shapes[src]
         O, I, kh, kw = weight.shape
-        paired = False
+        half: Optional[int] = None
         pk = self.packer
         panel = 0
         if groups > 1:
             # grouped convolution (ResNeXt's conv2, pose_resnet_dconv.py:101): block-diagonal panels of `panel` channels, one per N tile; K per
-            # tap is the panel, not c_in (sp_conv_desc.c_in_group).  64 = one bf16 K tile / two fp32 ones and a legal tile_n of the implicit GEMM.
+            # tap is the panel, not c_in (sp_conv_desc.c_in_group; conv_geometry.grouped_panel)
             if not (O == c_buf and c_buf % groups == 0 and I == c_buf // groups and not pixel_shuffle and not out_nchw):
                 raise NotImplementedError(f"{name}: grouped convolutions are lowered for c_out == c_in (got {tuple(weight.shape)} on {c_buf} channels)")
-            panel = 64
-            while panel % I:
-                panel *= 2
-            if O % panel or panel > 128:
-                raise NotImplementedError(f"{name}: no panel width for {groups} groups of {I} channels in {O}")
+            panel = conv_geometry.grouped_panel(name, groups, I, O)
             packed, th, tw, ci, k_pad = pk.grouped(weight, groups, panel, bf16=self.bf16), kh, kw, c_buf, kh * kw * panel
         elif self.bf16 and c_buf == 4 and I < 4:
             # bf16 stem on the NHWC4 image read as pixel pairs [h, w/2, 8]: pixel 2*ox - pad + kx = pair (ox - ceil(pad/2)) + pt, half
             # `sub`, with kx + s0 = 2*pt + sub.  A stride of 2 pixels is a stride of ONE pair: separate x / y strides (stride_x).
             if stride != 2 or w % 2:
                 raise NotImplementedError("bf16 stem: stride-2 convolution on an even-width image expected")
-            paired = True
             half = (pad + 1) // 2
             s0 = 2 * half - pad
             tpw = (kw - 1 + s0) // 2 + 1
@@ -935,42 +918,17 @@ class ProgramBuilder:
             assert I == c_buf, (name, I, c_buf)
             # pixel_shuffle: rows sub-pixel-major; `scale` / `shift` must come in the same order (fold_bn(..., pixel_shuffle=True))
             packed, th, tw, ci, k_pad = pk.conv(weight, pixel_shuffle=pixel_shuffle, bf16=self.bf16)
-        gh, gw = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-        d = ConvDesc()
-        d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, ci
-        d.grid_h, d.grid_w, d.c_out, d.n_pad = gh, gw, O, packed.shape[0]
-        d.taps_h, d.taps_w, d.k_pad, d.stride = th, tw, k_pad, stride
-        d.dy0, d.dy_step, d.dx0, d.dx_step = -pad, 1, -pad, 1
-        if paired:
-            d.in_w, d.stride_x, d.dx0 = w // 2, 1, -half
-        d.phases_y = d.phases_x = 1
-        flags = SP_CONV_RELU if relu else 0
-        if pixel_shuffle:
-            assert O % 4 == 0 and packed.shape[0] == O
-            d.out_h, d.out_w, d.out_c = gh * 2, gw * 2, O // 4
-            d.oy_mul = d.ox_mul = 2
-            flags |= SP_CONV_PIXEL_SHUFFLE
-        else:
-            d.out_h, d.out_w, d.out_c = gh, gw, O
-            d.oy_mul = d.ox_mul = 1
-        d.oy_add = d.ox_add = 0
-        if out_nchw:
-            flags |= SP_CONV_OUT_NCHW
-        if self.bf16:
-            flags |= SP_CONV_BF16
-        if hardswish:
-            flags |= SP_CONV_HARDSWISH
-        c0 = 0
+        flags = (SP_CONV_RELU if relu else 0) | (SP_CONV_OUT_NCHW if out_nchw else 0) | (SP_CONV_BF16 if self.bf16 else 0) | \
+                (SP_CONV_HARDSWISH if hardswish else 0)
+        c0, slice_of = 0, None
         if out_slice is not None:
             dst, c0 = out_slice
-            sh_, sw_, sc_ = self.p.shapes[dst]
-            if (sh_, sw_) != (gh, gw) or c0 % 4 or c0 + O > sc_ or pixel_shuffle or out_nchw or res is not None:
-                raise ValueError(f"{name}: cannot write channels [{c0}, {c0 + O}) of {dst} {self.p.shapes[dst]} from a {gh}x{gw} launch")
-            d.out_c = sc_
-            flags |= SP_CONV_OUT_SLICE
-        d.flags = flags
-        if panel:
-            d.c_in_group, d.tile_m, d.tile_n = panel, 128, panel
+            slice_of = self.p.shapes[dst][2]
+        d = conv_geometry.conv_fwd(h, w, ci, O, packed.shape[0], kh, kw, th, tw, k_pad, stride, pad, flags, pixel_shuffle=pixel_shuffle, pair_half=half,
+                                   slice_of=slice_of, panel=panel)
+        gh, gw = d.grid_h, d.grid_w
+        if out_slice is not None and (self.p.shapes[dst][:2] != (gh, gw) or c0 % 4 or c0 + O > slice_of or pixel_shuffle or out_nchw or res is not None):
+            raise ValueError(f"{name}: cannot write channels [{c0}, {c0 + O}) of {dst} {self.p.shapes[dst]} from a {gh}x{gw} launch")
         dst = dst or self._fresh(name)
         if out_slice is None:
             self.p.shapes[dst] = (d.out_h, d.out_w, d.out_c)
@@ -990,16 +948,7 @@ class ProgramBuilder:
             return None
         p1, th, tw, ci, k_pad = self.packer.conv(w1, bf16=True)
         p2 = self.packer.conv(w2, bf16=True)[0]
-        d = ConvDesc()
-        d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, ci
-        d.grid_h, d.grid_w, d.c_out, d.n_pad = h, w, c, p1.shape[0]
-        d.taps_h, d.taps_w, d.k_pad, d.stride = th, tw, k_pad, 1
-        d.dy0, d.dy_step, d.dx0, d.dx_step = -1, 1, -1, 1
-        d.phases_y = d.phases_x = 1
-        d.out_h, d.out_w, d.out_c = h, w, c
-        d.oy_mul = d.ox_mul = 1
-        d.oy_add = d.ox_add = 0
-        d.flags = SP_CONV_RELU | SP_CONV_BF16
+        d = conv_geometry.conv_fwd(h, w, ci, c, p1.shape[0], 3, 3, th, tw, k_pad, 1, 1, SP_CONV_RELU | SP_CONV_BF16)
         if not (_lib.lib().sp_basic_block_c32_ok(d) if c == 32 else _lib.lib().sp_basic_block_c64_ok(d)):
             return None
         dst = self._fresh(name)
@@ -1018,16 +967,7 @@ class ProgramBuilder:
         p1 = self.packer.conv(w1, bf16=True)[0]
         p2, th, tw, ci, k_pad = self.packer.conv(w2, bf16=True)
         p3 = self.packer.conv(w3, bf16=True)[0]
-        d = ConvDesc()
-        d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, ci
-        d.grid_h, d.grid_w, d.c_out, d.n_pad = h, w, 64, p2.shape[0]
-        d.taps_h, d.taps_w, d.k_pad, d.stride = th, tw, k_pad, 1
-        d.dy0, d.dy_step, d.dx0, d.dx_step = -1, 1, -1, 1
-        d.phases_y = d.phases_x = 1
-        d.out_h, d.out_w, d.out_c = h, w, 64
-        d.oy_mul = d.ox_mul = 1
-        d.oy_add = d.ox_add = 0
-        d.flags = SP_CONV_RELU | SP_CONV_BF16
+        d = conv_geometry.conv_fwd(h, w, ci, 64, p2.shape[0], 3, 3, th, tw, k_pad, 1, 1, SP_CONV_RELU | SP_CONV_BF16)
         if not _lib.lib().sp_bottleneck_c64_ok(d) or p1.shape[1] != 256 or p3.shape != (256, 64):
             return None
         dst = self._fresh(name)
@@ -1059,15 +999,7 @@ class ProgramBuilder:
         I, O = weight.shape[:2]
         assert I == c
         packed, n_pad = self.packer.deconv(weight, bf16=self.bf16)
-        d = ConvDesc()
-        d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, I
-        d.grid_h, d.grid_w, d.c_out, d.n_pad = h, w, O, n_pad
-        d.taps_h, d.taps_w, d.k_pad, d.stride = 2, 2, 4 * I, 1
-        d.dy0, d.dy_step, d.dx0, d.dx_step = 0, -1, 0, -1       # + phase (py, px) inside the kernel
-        d.out_h, d.out_w, d.out_c = 2 * h, 2 * w, O
-        d.oy_mul, d.oy_add, d.ox_mul, d.ox_add = 2, 0, 2, 0    # + phase
-        d.phases_y = d.phases_x = 2
-        d.flags = (SP_CONV_RELU if relu else 0) | (SP_CONV_BF16 if self.bf16 else 0)
+        d = conv_geometry.deconv_k4s2p1_fwd(h, w, I, O, n_pad, (SP_CONV_RELU if relu else 0) | (SP_CONV_BF16 if self.bf16 else 0))
         dst = self._fresh(name)
         self.p.shapes[dst] = (2 * h, 2 * w, O)
         self._add(Op("conv", src, dst, desc=d, w=packed, scale=scale, shift=shift,
@@ -1190,13 +1122,6 @@ def _res_basic_block(b: ProgramBuilder, sd, x: str, p: str, stride: int) -> str:
     s1, h1 = _bn(b, sd, p + ".bn1")
     t = b.conv(x, sd[p + ".conv1.weight"], stride=stride, pad=1, scale=s1, shift=h1, relu=True, name=p + ".conv1")
     idn = x
-    if (p + ".downsample.0.weight") in sd and stride == 1 and (p + ".se.fc.0.weight") not in sd and w2.shape[0] == w2.shape[1]:
-        # layer1.0 (64 mid channels): conv3 + the projection shortcut as one launch - the 256-channel shortcut tensor is never written (same bits)
-        sdn, hdn = _bn(b, sd, p + ".downsample.1")
-        s3, h3 = _bn(b, sd, p + ".bn3")
-        y = b.dual_pointwise_tail(t, sd[p + ".conv3.weight"], s3, h3, x, sd[p + ".downsample.0.weight"], sdn, hdn, name=p + ".conv3+downsample")
-        if y is not None:
-            return y
     if (p + ".downsample.0.weight") in sd:
         sdn, hdn = _bn(b, sd, p + ".downsample.1")
         idn = b.conv(x, sd[p + ".downsample.0.weight"], stride=stride, scale=sdn, shift=hdn, name=p + ".downsample")
@@ -1296,9 +1221,7 @@ def _hr_module(b: ProgramBuilder, sd, xs: List[str], base: str, num_blocks: List
             if last and pending:   # (j < i never is the last j: the identity term j == i follows it)
                 y = b.upsample_add_n(y, pending, relu=True)
                 pending = []
-            if j >= i:
-                continue
-            else:                  # chain of 3x3 stride-2 convs (+bn, +relu except the last) (:205-233)
+            if j < i:              # chain of 3x3 stride-2 convs (+bn, +relu except the last) (:205-233)
                 t = xs[j]
                 for k in range(i - j):
                     s, h = _bn(b, sd, f"{f}.{k}.1")

@@ -22,9 +22,9 @@ from typing import Callable, Dict, List, Optional, Tuple
 
 import torch
 
-from . import _lib
+from . import _lib, conv_geometry
 from ._lib import ConvDesc, SP_CONV_BF16, SP_CONV_BN_Y_MASK, SP_CONV_OUT_F32, SP_CONV_OUT_NCHW, SP_CONV_RELU
-from .engine import _round_up, n_pad_for
+from .conv_geometry import n_pad_for, round_up as _round_up
 
 BN_EPS, BN_MOMENTUM = 1e-5, 0.1
 P = _lib.ptr
@@ -202,17 +202,7 @@ class ConvT:
             # fwd pack: dst [n_pad][khp][tw][ci] <- W[o][c][ty][tx]
             self.pack_jobs.append(PackJob(self.wname, self.w_fwd, (n_pad, khp, tw, ci), (I * kh * kw, kw, 1, kh * kw), (O, kh, kw, I), 0))
             self.oh, self.ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
-            d = ConvDesc()
-            d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, ci
-            d.grid_h, d.grid_w, d.c_out, d.n_pad = self.oh, self.ow, O, n_pad
-            d.taps_h, d.taps_w, d.k_pad, d.stride = kh, tw, k_pad, stride
-            d.dy0, d.dy_step, d.dx0, d.dx_step = -pad, 1, -pad, 1
-            d.out_h, d.out_w, d.out_c = self.oh, self.ow, O
-            d.oy_mul = d.ox_mul = 1
-            d.oy_add = d.ox_add = 0
-            d.phases_y = d.phases_x = 1
-            d.flags = (SP_CONV_OUT_NCHW if out_nchw else 0) | fbf
-            self.d_fwd = d
+            self.d_fwd = d = conv_geometry.conv_fwd(h, w, ci, O, n_pad, kh, kw, kh, tw, k_pad, stride, pad, (SP_CONV_OUT_NCHW if out_nchw else 0) | fbf)
             self.c_out_buf = O
             self.flops = 2 * self.oh * self.ow * O * I * kh * kw
             # wgrad: g = dz [M, O_buf], a = x gathered with the forward geometry
@@ -232,32 +222,14 @@ class ConvT:
                     self.pack_jobs.append(PackJob(self.wname, self.w_fwd, (n_pad, 2, 2, I), (16, 8, 2, O * 16), (O, 2, 2, I),
                                                   (1 - py) * 4 + (1 - px), ph * n_pad * 4 * I))
             self.oh, self.ow = 2 * h, 2 * w
-            d = ConvDesc()
-            d.batch, d.in_h, d.in_w, d.c_in = 1, h, w, I
-            d.grid_h, d.grid_w, d.c_out, d.n_pad = h, w, O, n_pad
-            d.taps_h, d.taps_w, d.k_pad, d.stride = 2, 2, 4 * I, 1
-            d.dy0, d.dy_step, d.dx0, d.dx_step = 0, -1, 0, -1
-            d.out_h, d.out_w, d.out_c = 2 * h, 2 * w, O
-            d.oy_mul, d.oy_add, d.ox_mul, d.ox_add = 2, 0, 2, 0
-            d.phases_y = d.phases_x = 2
-            d.flags = fbf
-            self.d_fwd = d
+            self.d_fwd = conv_geometry.deconv_k4s2p1_fwd(h, w, I, O, n_pad, fbf)
             self.c_out_buf = O
             self.flops = 2 * h * w * I * O * 16
             # dgrad = Conv2d(k=4, s=2, p=1) of dy with Wd[ci][(ky,kx,co)] = W[ci][co][ky][kx]
             nd = n_pad_for(I)
             self.w_dgrad = [torch.zeros((nd, 16 * O), dtype=wdt, device=dev)]
             self.pack_jobs.append(PackJob(self.wname, self.w_dgrad[0], (nd, 4, 4, O), (O * 16, 4, 1, 16), (I, 4, 4, O), 0))
-            g = ConvDesc()
-            g.batch, g.in_h, g.in_w, g.c_in = 1, 2 * h, 2 * w, O
-            g.grid_h, g.grid_w, g.c_out, g.n_pad = h, w, I, nd
-            g.taps_h, g.taps_w, g.k_pad, g.stride = 4, 4, 16 * O, 2
-            g.dy0, g.dy_step, g.dx0, g.dx_step = -1, 1, -1, 1
-            g.out_h, g.out_w, g.out_c = h, w, I
-            g.oy_mul = g.ox_mul = 1
-            g.oy_add = g.ox_add = 0
-            g.phases_y = g.phases_x = 1
-            g.flags = fbf | (SP_CONV_OUT_F32 if (self.bf16 and not tr.g16) else 0)   # activation gradients: fp32 unless grad_dtype is bf16
+            g = conv_geometry.deconv_k4s2p1_dgrad(h, w, I, O, nd, fbf | conv_geometry.dgrad_store_flag(self.bf16, tr.g16))
             self.d_dgrad = [g]
             self.dgrad_full_cover = True
             # wgrad: dW[ci][co][ky][kx] = sum_m x[m][ci] * dy[(2iy-1+ky, 2ix-1+kx)][co]: g = x, a = dy gathered like the dgrad conv
@@ -276,59 +248,35 @@ class ConvT:
         if C % self.groups or C // self.groups != cpg or kh * kw > 9 or 256 % cpg:
             raise NotImplementedError(f"{self.name}: grouped convolutions are lowered for c_out == c_in with a group width dividing 256 and at most 9 taps "
                                       f"(weight {tuple(weight.shape)}, groups {self.groups})")
-        panel = 64
-        while panel % cpg:
-            panel *= 2
-        if C % panel or panel > 128:
-            raise NotImplementedError(f"{self.name}: no panel width for {self.groups} groups of {cpg} channels in {C}")
+        panel = conv_geometry.grouped_panel(self.name, self.groups, cpg, C)
         self.O, self.I, self.kh, self.kw, self.ci, self.tw, self.panel = C, cpg, kh, kw, C, kw, panel
         self.oh, self.ow = (h + 2 * pad - kh) // stride + 1, (w + 2 * pad - kw) // stride + 1
         self.c_out_buf = C
         self.flops = 2 * self.oh * self.ow * C * cpg * kh * kw
         self.one_launch_phases = False                   # (sp_conv2d_dgrad_phases has no grouped form: one launch per output phase)
-
-        def desc(in_h, in_w, gh, gw, th, tw, st, dy0, dys, dx0, dxs, oh, ow, oym=1, oya=0, oxm=1, oxa=0, out_f32=False):
-            d = ConvDesc()
-            d.batch, d.in_h, d.in_w, d.c_in = 1, in_h, in_w, C
-            d.grid_h, d.grid_w, d.c_out, d.n_pad = gh, gw, C, C
-            d.taps_h, d.taps_w, d.k_pad, d.stride = th, tw, th * tw * panel, st
-            d.dy0, d.dy_step, d.dx0, d.dx_step = dy0, dys, dx0, dxs
-            d.out_h, d.out_w, d.out_c = oh, ow, C
-            d.oy_mul, d.oy_add, d.ox_mul, d.ox_add = oym, oya, oxm, oxa
-            d.phases_y = d.phases_x = 1
-            d.flags = fbf | (SP_CONV_OUT_F32 if out_f32 else 0)
-            d.c_in_group, d.tile_m, d.tile_n = panel, 128, panel
-            return d
-
         self.w_fwd = torch.zeros((C, kh * kw * panel), dtype=wdt, device=dev)
         self.gpacks.append((0, kh, kw, 0, 1, 0, 1, self.w_fwd))
-        self.d_fwd = desc(h, w, self.oh, self.ow, kh, kw, stride, -pad, 1, -pad, 1, self.oh, self.ow)
+        self.d_fwd = conv_geometry.conv_fwd(h, w, C, C, C, kh, kw, kh, kw, kh * kw * panel, stride, pad, fbf, panel=panel)
         self.d_wgrad = self.d_fwd
         self.w_dgrad, self.d_dgrad = [], []
         self.dgrad_full_cover = True
         if not need_dgrad:
             return
-        g32 = self.bf16 and not self.tr.g16                 # activation gradients: fp32 unless grad_dtype is bf16
+        flags = fbf | conv_geometry.dgrad_store_flag(self.bf16, self.tr.g16)
         if stride == 1:
             wd = torch.zeros((C, kh * kw * panel), dtype=wdt, device=dev)
             self.gpacks.append((1, kh, kw, kh - 1, -1, kw - 1, -1, wd))          # Wd[c][(ty, tx, o)] = W[o][c][kh-1-ty][kw-1-tx]
-            pp = kh - 1 - pad
             self.w_dgrad.append(wd)
-            self.d_dgrad.append(desc(self.oh, self.ow, h, w, kh, kw, 1, -pp, 1, -pp, 1, h, w, out_f32=g32))
+            self.d_dgrad.append(conv_geometry.conv_dgrad_s1(self.oh, self.ow, C, C, C, kh, kw, kh * kw * panel, pad, flags, panel=panel))
         else:
             assert stride == 2 and h % 2 == 0 and w % 2 == 0
-            for py in range(2):                             # one launch per output phase (ConvT._build_conv_dgrad's decomposition)
-                for px in range(2):
-                    ky0, kx0 = (py + pad) % 2, (px + pad) % 2
-                    th, tw = len(range(ky0, kh, 2)), len(range(kx0, kw, 2))
-                    if th == 0 or tw == 0:
-                        self.dgrad_full_cover = False
-                        continue
-                    wd = torch.zeros((C, th * tw * panel), dtype=wdt, device=dev)
-                    self.gpacks.append((1, th, tw, ky0, 2, kx0, 2, wd))
-                    self.w_dgrad.append(wd)
-                    self.d_dgrad.append(desc(self.oh, self.ow, h // 2, w // 2, th, tw, 1, (py + pad - ky0) // 2, -1, (px + pad - kx0) // 2, -1, h, w,
-                                             2, py, 2, px, out_f32=g32))
+            for ph in conv_geometry.stride2_dgrad_phases(kh, kw, pad):           # one launch per output phase that receives gradient
+                _, _, ky0, kx0, th, tw = ph[:6]
+                wd = torch.zeros((C, th * tw * panel), dtype=wdt, device=dev)
+                self.gpacks.append((1, th, tw, ky0, 2, kx0, 2, wd))
+                self.w_dgrad.append(wd)
+                self.d_dgrad.append(conv_geometry.conv_dgrad_s2(h, w, self.oh, self.ow, C, C, C, ph, th * tw * panel, flags, panel=panel))
+            self.dgrad_full_cover = len(self.d_dgrad) == 4
 
     def pack_grouped(self, stream) -> None:
         """Regenerate this grouped layer's block-diagonal panels (forward + input-gradient phases) from the flat parameter buffer."""
@@ -368,51 +316,26 @@ class ConvT:
         Ob = O if (O % kmul == 0 or O % epc == 0) else _round_up(O, kmul)
         self.c_out_buf = Ob
         self.w_dgrad, self.d_dgrad = [], []
+        flags = fbf | conv_geometry.dgrad_store_flag(self.bf16, self.tr.g16)
         if s == 1:
             khp = self._pad_rows(kh, kw * Ob)
             wd = torch.zeros((nd, khp * kw * Ob), dtype=wdt, device=dev)
             # Wd[c][(ty,tx,o)] = W[o][c][kh-1-ty][kw-1-tx]
             self.pack_jobs.append(PackJob(self.wname, wd, (nd, khp, kw, Ob), (kh * kw, -kw, -1, I * kh * kw), (I, kh, kw, O),
                                           (kh - 1) * kw + (kw - 1)))
-            g = ConvDesc()
-            g.batch, g.in_h, g.in_w, g.c_in = 1, self.oh, self.ow, Ob
-            g.grid_h, g.grid_w, g.c_out, g.n_pad = self.h, self.w, I, nd
-            g.taps_h, g.taps_w, g.k_pad, g.stride = kh, kw, khp * kw * Ob, 1
-            pp = kh - 1 - p
-            g.dy0, g.dy_step, g.dx0, g.dx_step = -pp, 1, -pp, 1
-            g.out_h, g.out_w, g.out_c = self.h, self.w, I
-            g.oy_mul = g.ox_mul = 1
-            g.oy_add = g.ox_add = 0
-            g.phases_y = g.phases_x = 1
-            g.flags = fbf | (SP_CONV_OUT_F32 if (self.bf16 and not self.tr.g16) else 0)
-            self.w_dgrad.append(wd); self.d_dgrad.append(g)
+            self.w_dgrad.append(wd)
+            self.d_dgrad.append(conv_geometry.conv_dgrad_s1(self.oh, self.ow, Ob, I, nd, kh, kw, khp * kw * Ob, p, flags))
             self.dgrad_full_cover = True
         else:
             assert s == 2 and self.h % 2 == 0 and self.w % 2 == 0
-            # dx[2g+py] = sum over ky with (2g+py+p-ky) even: oy = (2g+py+p-ky)/2.  Tap t of phase py: ky = ky0 + 2t (ky < kh),
-            # oy = g + (py+p-ky0)/2 - t  ->  dy0 = (py+p-ky0)/2, dy_step = -1
-            self.dgrad_full_cover = True
-            for py in range(2):
-                for px in range(2):
-                    ky0, kx0 = (py + p) % 2, (px + p) % 2
-                    th, tw = len(range(ky0, kh, 2)), len(range(kx0, kw, 2))
-                    if th == 0 or tw == 0:
-                        self.dgrad_full_cover = False             # 1x1 stride 2: only phase (0,0) receives gradient
-                        continue
-                    thp = self._pad_rows(th, tw * Ob)
-                    wd = torch.zeros((nd, thp * tw * Ob), dtype=wdt, device=dev)
-                    self.pack_jobs.append(PackJob(self.wname, wd, (nd, thp, tw, Ob), (kh * kw, 2 * kw, 2, I * kh * kw), (I, th, tw, O),
-                                                  ky0 * kw + kx0))
-                    g = ConvDesc()
-                    g.batch, g.in_h, g.in_w, g.c_in = 1, self.oh, self.ow, Ob
-                    g.grid_h, g.grid_w, g.c_out, g.n_pad = self.h // 2, self.w // 2, I, nd
-                    g.taps_h, g.taps_w, g.k_pad, g.stride = th, tw, thp * tw * Ob, 1
-                    g.dy0, g.dy_step, g.dx0, g.dx_step = (py + p - ky0) // 2, -1, (px + p - kx0) // 2, -1
-                    g.out_h, g.out_w, g.out_c = self.h, self.w, I
-                    g.oy_mul, g.oy_add, g.ox_mul, g.ox_add = 2, py, 2, px
-                    g.phases_y = g.phases_x = 1
-                    g.flags = fbf | (SP_CONV_OUT_F32 if (self.bf16 and not self.tr.g16) else 0)
-                    self.w_dgrad.append(wd); self.d_dgrad.append(g)
+            for ph in conv_geometry.stride2_dgrad_phases(kh, kw, p):
+                _, _, ky0, kx0, th, tw = ph[:6]
+                thp = self._pad_rows(th, tw * Ob)
+                wd = torch.zeros((nd, thp * tw * Ob), dtype=wdt, device=dev)
+                self.pack_jobs.append(PackJob(self.wname, wd, (nd, thp, tw, Ob), (kh * kw, 2 * kw, 2, I * kh * kw), (I, th, tw, O), ky0 * kw + kx0))
+                self.w_dgrad.append(wd)
+                self.d_dgrad.append(conv_geometry.conv_dgrad_s2(self.h, self.w, self.oh, self.ow, Ob, I, nd, ph, thp * tw * Ob, flags))
+            self.dgrad_full_cover = len(self.d_dgrad) == 4          # 1x1 stride 2: only phase (0,0) receives gradient
 
     # ---- launches ----
     def _stats_rows(self, d, B: int, what: str) -> int:
@@ -527,7 +450,6 @@ class ConvT:
             two = bn_src.bn2 is not None
             part = self._new((3 if two else 2, total, stride), torch.float32, dz.device)
             z, mean, invstd = bn_src.bn
-            row0 = 0
             ysrc, mflag = bn_src.data, 0
             if bn_src.mask is not None and self.tr.g16:
                 ysrc, mflag = bn_src.mask, SP_CONV_BN_Y_MASK        # the ReLU bit mask instead of y: 1/16 of the bytes
@@ -553,33 +475,32 @@ class ConvT:
         return self._dgrad_plain(lib, dz, B, acc)
 
     def _dgrad_bstats(self, lib, dz, B, acc, dx, bn_src, ysrc, z, mean, invstd, part, total, need, one, two):
-        if True:
-            row0 = 0
-            done = self._timed("dgrad")
-            if one:
-                # a stride-2 conv's output phases (different tap counts) as ONE launch: same rows, same bits, three launch boundaries less
-                descs, ws_ = self._phase_arrays()
-                z2, mean2, invstd2 = (bn_src.bn2[:3] if two else (None, None, None))
-                _lib.check(lib.sp_conv2d_dgrad_phases(descs, len(self.d_dgrad), P(dz), ws_, P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
-                                                      P(part[0]), P(part[1]), P(z2), P(mean2), P(invstd2), P(part[2]) if two else None, total,
-                                                      _lib.current_stream()), self.name + ".dgrad")
-                done()
-                bn_src.bstats = (part, total)
-                return dx
-            for d, w, n in zip(self.d_dgrad, self.w_dgrad, need):
-                if two:
-                    z2, mean2, invstd2, _ = bn_src.bn2
-                    _lib.check(lib.sp_conv2d_dgrad_bn_bwd_stats2(d, P(dz), P(w), P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
-                                                                 P(part[0, row0:]), P(part[1, row0:]), P(z2), P(mean2), P(invstd2),
-                                                                 P(part[2, row0:]), n, _lib.current_stream()), self.name + ".dgrad")
-                else:
-                    _lib.check(lib.sp_conv2d_dgrad_bn_bwd_stats(d, P(dz), P(w), P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
-                                                                P(part[0, row0:]), P(part[1, row0:]), n, _lib.current_stream()),
-                               self.name + ".dgrad")
-                row0 += n
+        row0 = 0
+        done = self._timed("dgrad")
+        if one:
+            # a stride-2 conv's output phases (different tap counts) as ONE launch: same rows, same bits, three launch boundaries less
+            descs, ws_ = self._phase_arrays()
+            z2, mean2, invstd2 = (bn_src.bn2[:3] if two else (None, None, None))
+            _lib.check(lib.sp_conv2d_dgrad_phases(descs, len(self.d_dgrad), P(dz), ws_, P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
+                                                  P(part[0]), P(part[1]), P(z2), P(mean2), P(invstd2), P(part[2]) if two else None, total,
+                                                  _lib.current_stream()), self.name + ".dgrad")
             done()
             bn_src.bstats = (part, total)
             return dx
+        for d, w, n in zip(self.d_dgrad, self.w_dgrad, need):
+            if two:
+                z2, mean2, invstd2, _ = bn_src.bn2
+                _lib.check(lib.sp_conv2d_dgrad_bn_bwd_stats2(d, P(dz), P(w), P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
+                                                             P(part[0, row0:]), P(part[1, row0:]), P(z2), P(mean2), P(invstd2),
+                                                             P(part[2, row0:]), n, _lib.current_stream()), self.name + ".dgrad")
+            else:
+                _lib.check(lib.sp_conv2d_dgrad_bn_bwd_stats(d, P(dz), P(w), P(acc), P(dx), P(ysrc), P(z), P(mean), P(invstd),
+                                                            P(part[0, row0:]), P(part[1, row0:]), n, _lib.current_stream()),
+                           self.name + ".dgrad")
+            row0 += n
+        done()
+        bn_src.bstats = (part, total)
+        return dx
 
     def _dgrad_plain(self, lib, dz, B, acc):
         if acc is None:
@@ -682,7 +603,6 @@ class PoseTrainer:
         # dgrad launches store bf16 and accumulate the residual share in bf16, the BatchNorm backward reads it rounded.
         has_se = any(".se." in k for k in model.state_dict())
         can16 = self.bf16 and self.head in ("dconv", "duc") and not has_se
-        import os
         if grad_dtype is None:
             grad_dtype = os.environ.get("SP_GRAD_DTYPE") or ("bf16" if can16 else "fp32")
             if grad_dtype == "bf16" and not can16:
@@ -753,7 +673,6 @@ class PoseTrainer:
         if want is None:
             # opt-in (native_comm=True, or SP_NATIVE_COMM=1 in the environment) until the two private communicators have met a peer on a
             # multi-GPU box: `tests/test_gpu_train.py::test_two_rank_rccl_*` is that test and skips on one GPU
-            import os
             want = usable and os.environ.get("SP_NATIVE_COMM", "0") == "1"
         if not want:
             return
@@ -1347,28 +1266,27 @@ class PoseTrainer:
         lib, stream = _lib.lib(), _lib.current_stream()
         dheat = _lib.require_cuda_f32(dheat, "d loss / d heat maps")
         dev, ws = dheat.device, self.red_ws
-        if True:   # (block kept for a minimal diff of the tape below)
-            Jb = fl.c_out_buf                              # heat-map channels padded to a K tile of the backward launches
-            # final_layer.bias.grad = sum over batch and pixels of d loss / d heat, straight from the NCHW gradient into the flat buffer
-            _lib.check(lib.sp_channel_sum_nchw(P(dheat), B, J, hh * ww, P(self.flat.view("final_layer.bias", True)), stream), "final_layer.bias.grad")
-            dh = new((B, hh, ww, Jb)) if self.bf16 else newf((B, hh, ww, Jb))
-            _lib.check(lib.sp_nchw_to_nhwc_pad(P(dheat), P(dh), int(self.bf16), B, J, hh, ww, Jb, stream), "dheat.nhwc")
-            wgrad_async(fl, a.data, dh)
-            a.grad = fl.dgrad(dh, B, None, bn_src=a if (self.fuse_bn_bwd and a.bn is not None and a.consumers == 1) else None)
-            a.contrib += 1
-            self._grads_ready("final_layer.bias", "final_layer.weight")
-            for fn in reversed(tape):
-                fn()
-            for xa in list(getattr(self, "_branch_open", [])):       # (a branch nobody downstream joined: its jobs still have to be queued)
-                self._join_grad(xa)
-            self._wgrad_flush()
-            if self._wgrad_tail is not None:
-                torch.cuda.current_stream(dev).wait_event(self._wgrad_tail)      # join: the optimizer reads every weight gradient
-            if self._opt_in_backward:
-                assert all(w is not None for w in self._works), "a gradient bucket never completed"
-                for w in self._works:
-                    torch.cuda.current_stream(dev).wait_event(w)                 # join: parameters and packed copies are updated
-                self._works = None
+        Jb = fl.c_out_buf                              # heat-map channels padded to a K tile of the backward launches
+        # final_layer.bias.grad = sum over batch and pixels of d loss / d heat, straight from the NCHW gradient into the flat buffer
+        _lib.check(lib.sp_channel_sum_nchw(P(dheat), B, J, hh * ww, P(self.flat.view("final_layer.bias", True)), stream), "final_layer.bias.grad")
+        dh = new((B, hh, ww, Jb)) if self.bf16 else newf((B, hh, ww, Jb))
+        _lib.check(lib.sp_nchw_to_nhwc_pad(P(dheat), P(dh), int(self.bf16), B, J, hh, ww, Jb, stream), "dheat.nhwc")
+        wgrad_async(fl, a.data, dh)
+        a.grad = fl.dgrad(dh, B, None, bn_src=a if (self.fuse_bn_bwd and a.bn is not None and a.consumers == 1) else None)
+        a.contrib += 1
+        self._grads_ready("final_layer.bias", "final_layer.weight")
+        for fn in reversed(tape):
+            fn()
+        for xa in list(getattr(self, "_branch_open", [])):       # (a branch nobody downstream joined: its jobs still have to be queued)
+            self._join_grad(xa)
+        self._wgrad_flush()
+        if self._wgrad_tail is not None:
+            torch.cuda.current_stream(dev).wait_event(self._wgrad_tail)      # join: the optimizer reads every weight gradient
+        if self._opt_in_backward:
+            assert all(w is not None for w in self._works), "a gradient bucket never completed"
+            for w in self._works:
+                torch.cuda.current_stream(dev).wait_event(w)                 # join: parameters and packed copies are updated
+            self._works = None
         self._mark("backward")
 
     def all_reduce_grads(self) -> float:

@@ -10,8 +10,11 @@ from simple_pose_amd._lib import SP_CONV_BF16, SP_CONV_OUT_NCHW, SP_CONV_PIXEL_S
 
 
 def conv_desc_cpu(d, x, w, scale, shift, res, y, B):
-    """x: [B,in_h,in_w,c_in]; w: [phases*n_pad, k_pad]; y: NHWC [B,out_h,out_w,out_c] or NCHW if flagged (in place)."""
+    """x: [B,in_h,in_w,c_in]; w: [phases*n_pad, k_pad]; y: NHWC [B,out_h,out_w,out_c] or NCHW if flagged (in place).  Results take the fp32
+    rounding of the kernel's accumulator on their way into `y`, except that a float64 `y` receives them unrounded (for checks of the geometry
+    alone, at float64 tolerances)."""
     phases = d.phases_y * d.phases_x
+    store = (lambda a: a) if y.dtype == torch.float64 else (lambda a: a.float().to(y.dtype))
     x = x.reshape(B, d.in_h, d.in_w, d.c_in)      # the bf16 stem reads the [h, w, 4] image as pixel pairs [h, w/2, 8]
     wp = w.reshape(phases, d.n_pad, d.k_pad)
     gy = torch.arange(d.grid_h).view(-1, 1)
@@ -54,16 +57,16 @@ def conv_desc_cpu(d, x, w, scale, shift, res, y, B):
                     part = part + res[:, yy][:, :, xx].double()
                 if d.flags & SP_CONV_RELU:
                     part = part.clamp(min=0)
-                y[:, yy.view(-1, 1), xx.view(1, -1), :] = part.float().to(y.dtype)
+                y[:, yy.view(-1, 1), xx.view(1, -1), :] = store(part)
             continue
         if res is not None:
             acc = acc + res[:, oy][:, :, ox].double()
         if d.flags & SP_CONV_RELU:
             acc = acc.clamp(min=0)
         if d.flags & SP_CONV_OUT_NCHW:
-            y[:, :, oy.view(-1, 1), ox.view(1, -1)] = acc.permute(0, 3, 1, 2).float()
+            y[:, :, oy.view(-1, 1), ox.view(1, -1)] = store(acc.permute(0, 3, 1, 2))
         else:
-            y[:, oy.view(-1, 1), ox.view(1, -1), :] = acc.float().to(y.dtype)
+            y[:, oy.view(-1, 1), ox.view(1, -1), :] = store(acc)
 
 
 def run_program_cpu(prog, x):
@@ -129,6 +132,34 @@ def run_program_cpu(prog, x):
         else:
             raise ValueError(op.kind)
     return bufs[prog.out_name], bufs
+
+
+def pack_conv_t_cpu(layer, weight):
+    """TEST HELPER: fill the packed weights of a simple_pose_amd.train.ConvT from `weight` in plain torch, as the device does after every
+    optimizer step.  Its PackJobs by the rule of sp_permute4_f32 (include/simple_pose_hip.h):
+        dst[dst_off + ((i0*d1 + i1)*d2 + i2)*d3 + i3] = all(i_k < valid[k]) ? src[base + sum i_k * strides[k]] : 0
+    and a grouped layer's panels by the rule of sp_pack_conv_weights_grouped_taps: row n (an output channel; with `transpose` an input
+    channel) holds, for tap (ky0 + ky_step*ty, kx0 + kx_step*tx), its group's weights at the group's channels inside panel n // panel."""
+    src = weight.detach().float().reshape(-1)
+    for j in layer.pack_jobs:
+        idx = torch.meshgrid(*[torch.arange(n) for n in j.dims], indexing="ij")
+        ok = torch.stack([i < v for i, v in zip(idx, j.valid)]).all(0)
+        off = j.base + sum(i.clamp(max=v - 1) * s for i, v, s in zip(idx, j.valid, j.strides))
+        vals = torch.where(ok, src[off], torch.zeros(()))
+        j.dst.view(-1)[j.dst_off:j.dst_off + vals.numel()] = vals.reshape(-1).to(j.dst.dtype)
+    wf = weight.detach().float()
+    for transpose, th, tw, ky0, kys, kx0, kxs, dst in layer.gpacks:
+        C, cpg, kh, kw = wf.shape
+        out = torch.zeros((C, th * tw, layer.panel))
+        for n in range(C):
+            g0 = (n // cpg) * cpg                                  # first channel of row n's group
+            lo = g0 - (n // layer.panel) * layer.panel
+            for ty in range(th):
+                for tx in range(tw):
+                    ky, kx = ky0 + kys * ty, kx0 + kxs * tx
+                    if 0 <= ky < kh and 0 <= kx < kw:
+                        out[n, ty * tw + tx, lo:lo + cpg] = wf[g0:g0 + cpg, n - g0, ky, kx] if transpose else wf[n, :, ky, kx]
+        dst.copy_(out.reshape(C, -1).to(dst.dtype))
 
 
 class TorchPacker:

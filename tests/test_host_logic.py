@@ -509,3 +509,80 @@ def test_stream_pin_is_per_thread_and_per_device():
     finally:
         _lib.pin_stream(prev)
     assert getattr(_lib._pin, "value", None) is prev
+
+
+# (kind, weight shape, input h x w, ConvT keywords): the smallest shapes at which each mapping of conv_geometry can still go wrong
+CONV_T_CASES = {
+    "3x3_s1_8to8": ("conv", (8, 8, 3, 3), 6, 4, dict(stride=1, pad=1)),                       # K = 72: _pad_rows appends a zero tap row
+    "3x3_s2_8to16": ("conv", (16, 8, 3, 3), 8, 6, dict(stride=2, pad=1)),                     # four phases of 2x2, 2x1, 1x2, 1x1 taps
+    "1x1_s2_32to64": ("conv", (64, 32, 1, 1), 8, 6, dict(stride=2, pad=0)),                   # three empty phases
+    "1x1_s1_32to17_nchw_bias": ("conv", (17, 32, 1, 1), 6, 4, dict(out_nchw=True, bias_name="final_layer.bias")),
+    "7x7_s2_stem": ("conv", (64, 3, 7, 7), 16, 12, dict(stride=2, pad=3, c_in_buf=4, need_dgrad=False)),
+    "deconv_32to16": ("deconv", (32, 16, 4, 4), 4, 3, dict(stride=2, pad=1)),
+    "grouped_3x3_s1": ("conv", (64, 16, 3, 3), 8, 6, dict(stride=1, pad=1, groups=4)),
+    "grouped_3x3_s2": ("conv", (64, 16, 3, 3), 8, 6, dict(stride=2, pad=1, groups=4)),
+}
+
+
+@pytest.mark.parametrize("case", list(CONV_T_CASES))
+def test_train_layer_descriptors_reproduce_torch_forward_and_input_gradient(case):
+    """train.ConvT's forward and input-gradient descriptors (conv_geometry) and its pack jobs, interpreted on the CPU, against float64
+    torch.nn.functional.conv2d / conv_transpose2d and the autograd input gradient of the same layer; fp32 weights, batch 2.  Every launch
+    writes into NaN-filled outputs and runs without an accumulator: forward and full-cover gradients must leave no NaN, and a stride-2 1x1
+    family must leave exactly the pixels that receive no gradient (then taken as 0).
+    Tolerance: interpreter and reference multiply the same fp32 values in float64 and differ only in the order of a sum of at most
+    16 * 64 terms, so 1e-9 (relative and absolute) is ample."""
+    import types
+    import torch.nn.functional as F
+    from simple_pose_amd.train import ConvT
+    from tests.desc_interp import conv_desc_cpu, pack_conv_t_cpu
+
+    kind, wshape, h, w, kw = CONV_T_CASES[case]
+    gen = torch.Generator().manual_seed(11)
+    B, stride, pad, groups = 2, kw.get("stride", 1), kw.get("pad", 0), kw.get("groups", 1)
+    weight = torch.randn(wshape, generator=gen)
+    deconv = kind == "deconv"
+    c_in, c_out = (wshape[0], wshape[1]) if deconv else (wshape[1] * groups, wshape[0])
+    x = torch.randn((B, c_in, h, w), generator=gen)
+    bias = torch.randn(c_out, generator=gen) if kw.get("bias_name") else None
+    L = ConvT(types.SimpleNamespace(bf16=False, g16=False), "layer", kind, weight, h, w, **kw)
+    pack_conv_t_cpu(L, weight)
+    if groups > 1:
+        assert torch.equal(L.w_fwd, TorchPacker().grouped(weight, groups, L.panel))
+
+    xr = x.double().requires_grad_(True)
+    if deconv:
+        ref = F.conv_transpose2d(xr, weight.double(), stride=2, padding=1)
+    else:
+        ref = F.conv2d(xr, weight.double(), None if bias is None else bias.double(), stride=stride, padding=pad, groups=groups)
+    d = L.d_fwd
+    x_nhwc = torch.zeros((B, h, w, d.c_in))
+    x_nhwc[..., :c_in] = x.permute(0, 2, 3, 1)                       # (the stem reads the image as NHWC4)
+    nan = float("nan")
+    y = torch.full(tuple(ref.shape) if L.out_nchw else (B, d.out_h, d.out_w, d.out_c), nan, dtype=torch.float64)
+    conv_desc_cpu(d, x_nhwc, L.w_fwd, None, bias, None, y, B)
+    assert not torch.isnan(y).any()
+    torch.testing.assert_close(y if L.out_nchw else y.permute(0, 3, 1, 2), ref.detach(), rtol=1e-9, atol=1e-9)
+    if case == "1x1_s1_32to17_nchw_bias":
+        assert L.c_out_buf == 32                                     # 17 heat-map channels: the gradient buffer is padded to one K tile
+    if not L.need_dgrad:
+        return
+
+    dz = torch.randn(ref.shape, generator=gen)
+    ref.backward(dz.double())
+    dz_nhwc = torch.zeros((B,) + tuple(ref.shape[2:]) + (L.c_out_buf,))
+    dz_nhwc[..., :c_out] = dz.permute(0, 2, 3, 1)
+    d0 = L.d_dgrad[0]
+    dx = torch.full((B, d0.out_h, d0.out_w, d0.out_c), nan, dtype=torch.float64)
+    assert (d0.out_h, d0.out_w, d0.out_c) == (h, w, c_in)
+    for dd, wd in zip(L.d_dgrad, L.w_dgrad):
+        conv_desc_cpu(dd, dz_nhwc, wd, None, None, None, dx, B)
+    want = xr.grad.permute(0, 2, 3, 1)
+    # input row iy takes gradient through tap ky iff (iy + pad - ky) is a multiple of the stride
+    reach = lambda k: torch.tensor([any((r + pad - t) % stride == 0 for t in range(k)) for r in range(stride)])
+    rows, cols = (torch.ones(1, dtype=torch.bool),) * 2 if deconv else (reach(wshape[2]), reach(wshape[3]))
+    hit = rows[torch.arange(h) % len(rows)].view(-1, 1) & cols[torch.arange(w) % len(cols)].view(1, -1)
+    assert L.dgrad_full_cover == bool(hit.all())
+    assert torch.equal(torch.isnan(dx), ~hit.view(1, h, w, 1).expand_as(dx))
+    assert (want[~hit.view(1, h, w, 1).expand_as(want)] == 0).all()
+    torch.testing.assert_close(torch.nan_to_num(dx, nan=0.0), want, rtol=1e-9, atol=1e-9)
