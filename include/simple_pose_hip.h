@@ -738,6 +738,22 @@ int sp_topdown_plan(const float* det, const int32_t* counts, int batch, int max_
 int sp_warp_affine_plan_u8c3(const unsigned char* src, int batch, int src_h, int src_w, const double* m_inv, const int32_t* src_index,
                              const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream);
 
+/* ---- flip test: the mirrored network input and the merge of the two sets of heat maps ----------------------------------------------------
+ * sp_mirror_w: dst[r, x] = src[r, w-1-x] over `rows` rows of `w` elements of elem_bytes bytes: 3 = uint8 BGR NHWC crops (rows = N*H),
+ * 4 = fp32 NCHW inputs (rows = N*C*H).  Out of place only: dst may be the second half of the allocation that holds src, overlapping ranges
+ * are refused.  rows == 0 is a no-op.  One launch; 16-byte (fp32) / 12-byte (uint8x3) accesses when w % 4 == 0 and both pointers are
+ * aligned for them, one element per lane otherwise. */
+int sp_mirror_w(const void* src, void* dst, int64_t rows, int w, int elem_bytes, void* stream);
+/* The flip test's merge, fp32 NCHW [batch, joints, h, w] in and out; perm_host: `joints` (<= 64) ints in HOST memory, a permutation of
+ * 0..joints-1 (the left/right swap), copied into the kernel's arguments (no host-to-device copy: capturable):
+ *   f[b,j,y,x]   = hm_flipped[b, perm[j], y, w-1-x]
+ *   g[b,j,y,x]   = shift ? (x >= 1 ? f[b,j,y,x-1] : f[b,j,y,0]) : f[b,j,y,x]        (shift: Simple-Baselines' SHIFT_HEATMAP)
+ *   out[b,j,y,x] = (hm[b,j,y,x] + g[b,j,y,x]) * 0.5f                                 (one fp32 add, one fp32 multiply)
+ * out == hm (in place on the un-flipped maps) is allowed and gives the same bits; any other overlap of out with hm, and any overlap of out
+ * with hm_flipped, is refused.  batch == 0 is a no-op.  One launch; 16-byte accesses when w % 4 == 0 and the pointers are 16-byte aligned. */
+int sp_heat_map_flip_merge(const float* hm, const float* hm_flipped, const int32_t* perm_host, int batch, int joints, int h, int w, int shift,
+                           float* out, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

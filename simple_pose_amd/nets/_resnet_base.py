@@ -15,6 +15,7 @@ from torch import nn
 
 from .. import engine
 from .._lib import HipLibraryError, require_cuda_f32
+from ..metrics.flip import COCO_JOINT_PAIRS, merge_flipped, mirror_input, pairs_to_perm
 
 
 class _Bottleneck(nn.Module):
@@ -156,8 +157,8 @@ class PoseResNetBase(nn.Module):
     def _forward_train(self, x: torch.Tensor) -> torch.Tensor:
         return train_forward(self, x)
 
-    def forward_crops(self, crops: torch.Tensor) -> torch.Tensor:
-        return forward_uint8_crops(self, crops)
+    def forward_crops(self, crops: torch.Tensor, flip_test: bool = False, joint_pairs=COCO_JOINT_PAIRS, shift_heatmap: bool = False) -> torch.Tensor:
+        return forward_uint8_crops(self, crops, flip_test, joint_pairs, shift_heatmap)
 
 
 def train_forward(self, x: torch.Tensor) -> torch.Tensor:
@@ -204,10 +205,14 @@ class _TrainForward(torch.autograd.Function):
         return (None, None) + grads          # no gradient w.r.t. the input image (the stem's dgrad is not computed, as in the solver)
 
 
-def forward_uint8_crops(model, crops: torch.Tensor) -> torch.Tensor:
+def forward_uint8_crops(model, crops: torch.Tensor, flip_test: bool = False, joint_pairs=COCO_JOINT_PAIRS, shift_heatmap: bool = False) -> torch.Tensor:
     """uint8 BGR crops [B,H,W,3] on the GPU (what `cv.warpAffine` / `datasets.naive_data.crop_boxes` produce) -> heat maps.  The
     collate normalisation of datasets/coco.py:136 (`x/255 - mean`, BGR -> RGB) happens inside the first launch, which writes the
-    network's NHWC input directly; bit-identical to `model(normalize_crops(crops))`."""
+    network's NHWC input directly; bit-identical to `model(normalize_crops(crops))`.
+    `flip_test`: the crops and their mirror images go through ONE forward on 2B; the second half's heat maps are mirrored back, their
+    left/right joints (`joint_pairs`) swapped, and averaged into the first half (metrics.flip; `shift_heatmap`: SHIFT_HEATMAP).  The 2B
+    buffer is filled by one device-to-device copy of the crops (data movement, no arithmetic) and one sp_mirror_w launch; a caller that
+    can write its crops straight into the first half of such a buffer (as TopDownPoseEstimator does) saves the copy."""
     if not (isinstance(crops, torch.Tensor) and crops.is_cuda and crops.dtype == torch.uint8 and crops.dim() == 4 and crops.shape[-1] == 3):
         raise HipLibraryError("forward_crops: expected a CUDA uint8 tensor [B,H,W,3]")
     B, H, W, _ = crops.shape
@@ -216,10 +221,20 @@ def forward_uint8_crops(model, crops: torch.Tensor) -> torch.Tensor:
     if model.training:
         raise NotImplementedError("forward_crops is the eval-mode path; training goes through simple_pose_amd.train.PoseTrainer")
     prog = model.hip_program(torch.empty((0, 3, H, W), device=crops.device))
-    crops = crops.contiguous()
+    if flip_test:
+        pairs_to_perm(joint_pairs, prog.out_shape[0])            # refuse bad pairs before anything is launched
+        both = torch.empty((2 * B, H, W, 3), dtype=torch.uint8, device=crops.device)
+        both[:B].copy_(crops)
+        mirror_input(both[:B], out=both[B:])
+        crops, B = both, 2 * B                                   # the autotune rule applies to the batch the program runs on
+    else:
+        crops = crops.contiguous()
     if model.autotune and B >= 16 and B >= 4 * prog.tuned_for_batch:
         prog.autotune(crops)
-    return prog.run(crops)
+    hm = prog.run(crops)
+    if flip_test:
+        hm = merge_flipped(hm[:B // 2], hm[B // 2:], joint_pairs, shift_heatmap, out=hm[:B // 2])
+    return hm
 
 
 def load_pretrained_like_reference(model: nn.Module, arch: str):

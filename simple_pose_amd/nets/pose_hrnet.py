@@ -17,6 +17,7 @@ import yaml
 
 from .. import engine
 from .._lib import HipLibraryError, require_cuda_f32
+from ..metrics.flip import COCO_JOINT_PAIRS
 from ._param_tree import ParamTree
 
 Shape = Tuple[str, Tuple[int, ...], str]
@@ -144,9 +145,9 @@ class PoseHighResolutionNet(ParamTree):
             prog.autotune(x)
         return prog.run(x)
 
-    def forward_crops(self, crops: torch.Tensor) -> torch.Tensor:
+    def forward_crops(self, crops: torch.Tensor, flip_test: bool = False, joint_pairs=COCO_JOINT_PAIRS, shift_heatmap: bool = False) -> torch.Tensor:
         from ._resnet_base import forward_uint8_crops
-        return forward_uint8_crops(self, crops)
+        return forward_uint8_crops(self, crops, flip_test, joint_pairs, shift_heatmap)
 
 
 def load_cfg(cfg_path: str) -> dict:

@@ -10,9 +10,13 @@ temp_read_in_and_filter).  Here a frame is one stream of launches: letterbox + Y
 sp_topdown_plan (boxes -> crop geometry), sp_warp_affine_plan_u8c3 (the crops), the pose program on `capacity` crops, the key-point decode,
 sp_pose_rescore and sp_oks_nms.  The person count never reaches the host: the pose half always computes `capacity` slots (dead slots are
 zero crops that OKS-NMS never sees), which is what makes the frame capturable - at batch 1 it is ONE hipGraph.  One device-to-host
-transfer per call brings back the keep list, the counts, the status words and the rows.  There is no CPU fallback."""
+transfer per call brings back the keep list, the counts, the status words and the rows.  There is no CPU fallback.
+With `flip_test=True` the crops are mirrored into a second half of the crop buffer (sp_mirror_w), the pose program runs once on
+`2 * capacity` crops, and sp_heat_map_flip_merge averages the un-mirrored second half into the first before the decode: two more launches
+on the same stream, still one graph."""
 from __future__ import annotations
 
+import ctypes
 from dataclasses import dataclass
 from typing import Dict, List, Sequence, Union
 
@@ -21,6 +25,7 @@ import torch
 
 from . import _lib, engine
 from ._lib import HipLibraryError
+from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
 
 P = _lib.ptr
 MAX_CAPACITY = 2048                  # the OKS-NMS group limit (sp_oks_nms)
@@ -59,7 +64,7 @@ class _Frame:
     """The device buffers of one (batch, source shape, max_det): the static source, the plan, the crops, and ONE packed result buffer
     whose slices the kernels write directly, so that a call ends in a single device-to-host copy."""
 
-    def __init__(self, B: int, H: int, W: int, max_det: int, cap: int, J: int, in_hw, device):
+    def __init__(self, B: int, H: int, W: int, max_det: int, cap: int, J: int, in_hw, device, flip_test: bool = False):
         self.B, self.H, self.W, self.max_det = B, H, W, max_det
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
         self.src = z((B, H, W, 3), torch.uint8)
@@ -69,7 +74,7 @@ class _Frame:
         self.trans_inv = z((cap, 2, 3), torch.float32)
         self.center, self.scale = z((cap, 2), torch.float32), z((cap, 2), torch.float32)
         self.area, self.box_score = z((cap,), torch.float64), z((cap,), torch.float64)
-        self.crops = z((cap, in_hw[0], in_hw[1], 3), torch.uint8)
+        self.crops = z(((2 * cap if flip_test else cap), in_hw[0], in_hw[1], 3), torch.uint8)    # flip test: the crops, then their mirrors
         fields = (("kps64", (cap, J, 3), torch.float64), ("score", (cap,), torch.float64), ("box", (cap, 5), torch.float32),
                   ("keep", (cap,), torch.int32), ("keep_count", (B,), torch.int32), ("seg", (B + 1,), torch.int32),
                   ("status", (B,), torch.int32), ("dropped", (B,), torch.int32), ("counts", (B,), torch.int32))
@@ -103,13 +108,17 @@ class TopDownPoseEstimator(object):
     by the images of a batch; the pose network always runs on `capacity` crops, selected detections beyond it are dropped from the end of
     the (image, detection) order and reported in `PoseResult.dropped`.  `person_cls`: the detector class kept (-1: every row, as the
     reference's gen_data_by_detector does); `min_box_score`: detections below it are not cropped.
-    `use_graph`: `estimate` (batch 1) replays one captured graph per source shape (an LRU of MAX_GRAPHS shapes); False launches eagerly."""
+    `use_graph`: `estimate` (batch 1) replays one captured graph per source shape (an LRU of MAX_GRAPHS shapes); False launches eagerly.
+    `flip_test`: every crop also goes through the pose network mirrored (one forward on 2 x capacity crops) and the two sets of heat maps
+    are merged before the decode (metrics.flip); `joint_pairs`: the left/right joints that swap (default: COCO's eight pairs);
+    `shift_heatmap`: Simple-Baselines' SHIFT_HEATMAP on the un-mirrored maps.  `estimate`, `estimate_batch` and `estimate_boxes` honour it."""
 
     MAX_GRAPHS = 8
     MAX_DET = 300                    # non_max_suppression's default, what single_predict uses
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
-                 in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64)):
+                 in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
+                 joint_pairs=None, shift_heatmap: bool = False):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -129,6 +138,10 @@ class TopDownPoseEstimator(object):
         if len(input_shape) != 2 or len(output_shape) != 2 or input_shape[0] % 32 or input_shape[1] % 32 or \
                 tuple(output_shape) != (input_shape[0] // 4, input_shape[1] // 4):
             raise ValueError(f"input_shape (w, h) must be multiples of 32 and output_shape a quarter of it, got {input_shape} / {output_shape}")
+        # type and disjointness now; the range once the program's joint count is known (_pose_program)
+        self.joint_pairs = check_joint_pairs(COCO_JOINT_PAIRS if joint_pairs is None else joint_pairs)
+        self.flip_test, self.shift_heatmap = bool(flip_test), bool(shift_heatmap)
+        self._perm = None
         self.detector, self.pose_model, self.decoder = detector, pose_model, decoder
         self.capacity, self.person_cls, self.min_box_score = capacity, person_cls, float(min_box_score)
         self.in_vis_thre, self.oks_thre = float(in_vis_thre), float(oks_thre)
@@ -143,18 +156,26 @@ class TopDownPoseEstimator(object):
         prog = self.pose_model.hip_program(torch.empty((0, 3, ih, iw), device=self.device))
         if tuple(prog.out_shape[1:]) != (self.output_shape[1], self.output_shape[0]):
             raise HipLibraryError(f"pose program produces heat maps {tuple(prog.out_shape)}, expected [J, {self.output_shape[1]}, {self.output_shape[0]}]")
-        if getattr(self.pose_model, "autotune", False) and self.capacity >= 16 and self.capacity >= 4 * prog.tuned_for_batch:
+        n = self._pose_batch()
+        if getattr(self.pose_model, "autotune", False) and n >= 16 and n >= 4 * prog.tuned_for_batch:
             # as forward_crops does at this batch size: pins the fastest tile per layer (speed only, same bits); never inside a capture
-            prog.autotune(torch.zeros((self.capacity, ih, iw, 3), dtype=torch.uint8, device=self.device))
+            prog.autotune(torch.zeros((n, ih, iw, 3), dtype=torch.uint8, device=self.device))
+        if self.flip_test:                           # per call (a few ints): `joint_pairs` may have been reassigned; the range check happens here
+            J = prog.out_shape[0]
+            self._perm = (ctypes.c_int32 * J)(*pairs_to_perm(self.joint_pairs, J))
         return prog
 
+    def _pose_batch(self) -> int:
+        """Crops per run of the pose program: the slots, and with the flip test their mirrors."""
+        return 2 * self.capacity if self.flip_test else self.capacity
+
     def _frame(self, B: int, H: int, W: int, max_det: int, J: int) -> _Frame:
-        key = (B, H, W, max_det, J)
+        key = (B, H, W, max_det, J, self.flip_test)
         fr = self._frames.get(key)
         if fr is None:
             if len(self._frames) >= self.MAX_GRAPHS:
                 self._frames.pop(next(iter(self._frames)))
-            fr = _Frame(B, H, W, max_det, self.capacity, J, (self.input_shape[1], self.input_shape[0]), self.device)
+            fr = _Frame(B, H, W, max_det, self.capacity, J, (self.input_shape[1], self.input_shape[0]), self.device, self.flip_test)
         else:
             self._frames.pop(key)                # most recently used last
         self._frames[key] = fr
@@ -197,7 +218,7 @@ class TopDownPoseEstimator(object):
     def _params(self, det_prog, pose_prog) -> tuple:
         d = self.detector
         return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
-                id(det_prog), id(pose_prog), id(self.decoder))
+                id(det_prog), id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap)
 
     def _detect(self, fr: _Frame, det_prog, single_stream: bool = False) -> None:
         """letterbox + network + head decode, NMS and the un-letterbox, all on the device (what single_predict / predict compute)."""
@@ -229,7 +250,14 @@ class TopDownPoseEstimator(object):
                                        P(fr.box_score), P(fr.box), P(fr.dropped), stream), "sp_topdown_plan")
         _lib.check(lib.sp_warp_affine_plan_u8c3(P(fr.src), fr.B, fr.H, fr.W, P(fr.m_inv), P(fr.src_index), P(fr.seg), cap, P(fr.crops), ih, iw,
                                                 stream), "sp_warp_affine_plan_u8c3")
+        if self.flip_test:
+            half = fr.crops[:cap]
+            _lib.check(lib.sp_mirror_w(P(half), P(fr.crops[cap:]), cap * ih, iw, 3, stream), "sp_mirror_w")     # dead slots: zeros mirror to zeros
         hm = _run_program(pose_prog, fr.crops, single_stream)
+        if self.flip_test:
+            hm = hm[:cap]                            # merged in place; the decode sees the first `capacity` maps only
+            _lib.check(lib.sp_heat_map_flip_merge(P(hm), P(hm) + hm.numel() * 4, self._perm, cap, J, oh, ow, int(self.shift_heatmap), P(hm),
+                                                  stream), "sp_heat_map_flip_merge")
         kps, mv = self.decoder(hm, fr.trans_inv)
         kps3 = torch.cat([kps, mv], -1)              # eval.py:138
         _lib.check(lib.sp_pose_rescore(P(kps3), P(fr.box_score), cap, J, self.in_vis_thre, P(fr.kps64), P(fr.score), stream), "sp_pose_rescore")
@@ -251,7 +279,7 @@ class TopDownPoseEstimator(object):
             self._poses(fr, pose_prog, True)
         fr.graph, fr.params = graph, self._params(det_prog, pose_prog)
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
-        fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self.capacity, dev), fr.ws)
+        fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self._pose_batch(), dev), fr.ws)
 
     def _results(self, fr: _Frame) -> List[PoseResult]:
         h = fr.fetch()

@@ -6,7 +6,10 @@ Out of scope by the survey's contract: COCO parsing / augm
 (`train_loader` / `val_loader`: iterables of the reference's collate tuples, tensors on any device), and `data.synthetic: N` builds
 deterministic synthetic ones on the GPU; `val()` reports loss / accuracy and writes the checkpoint in the reference's format.  With
 ground truth (`data.val_ann_path` names an annotation file, or `val_gt` is passed) it also reports COCO keypoint AP from the device
-evaluator (metrics.coco_eval: the decoder's output goes to it without leaving the GPU), tracks `best_map` and writes `_best.pth`."""
+evaluator (metrics.coco_eval: the decoder's output goes to it without leaving the GPU), tracks `best_map` and writes `_best.pth`.
+Optional `val.flip_test: true` validates with the flip test (metrics.flip: the batch and its mirror image through one forward on 2B, the
+merged heat maps go to the loss, the accuracy and the decoder); `val.shift_heatmap: true` adds Simple-Baselines' SHIFT_HEATMAP and
+`val.joint_pairs` replaces COCO's eight left/right pairs."""
 from __future__ import annotations
 
 import os
@@ -152,6 +155,9 @@ class DDPProcessor(object):
         if self.rank != 0 or self.vloader is None:
             return None
         from .. import _lib
+        from ..metrics.flip import COCO_JOINT_PAIRS, merge_flipped, mirror_input
+        flip_test, shift_heatmap = bool(self.val_cfg.get("flip_test", False)), bool(self.val_cfg.get("shift_heatmap", False))
+        joint_pairs = self.val_cfg.get("joint_pairs", COCO_JOINT_PAIRS)      # optional: [[left, right], ...] for a non-COCO joint set
         self.loss_logger.reset(); self.acc_logger.reset()
         self.model.eval()
         kps_dict_list = []
@@ -160,7 +166,15 @@ class DDPProcessor(object):
         for input_tensors, heat_maps, masks, trans_invs, img_ids in self.vloader:
             x, targets = input_tensors.to(self.device), heat_maps.to(self.device)
             tinv, mask = trans_invs.to(self.device).float(), masks.to(self.device)
-            predicts = self.model(x)
+            if flip_test:                                     # val.flip_test: the batch and its mirror image through ONE forward on 2B
+                nb = x.shape[0]
+                both = torch.empty((2 * nb,) + tuple(x.shape[1:]), dtype=torch.float32, device=self.device)
+                both[:nb].copy_(x)
+                mirror_input(both[:nb], out=both[nb:])
+                predicts = self.model(both)
+                predicts = merge_flipped(predicts[:nb], predicts[nb:], joint_pairs, shift_heatmap, out=predicts[:nb])
+            else:
+                predicts = self.model(x)
             loss = torch.zeros(1, dtype=torch.float32, device=self.device)
             B, J, H, W = predicts.shape
             _lib.check(_lib.lib().sp_masked_mse(_lib.ptr(predicts), _lib.ptr(targets.contiguous()), _lib.ptr(mask.contiguous()), B, J, H * W,

@@ -1,6 +1,6 @@
 """tools/bench_pipeline.py - the top-down frame (image -> poses) on one MI355X: staged chain vs the device-resident estimator.
 
-    python tools/bench_pipeline.py [--out profiles/pipeline_bench.json] [--quick]
+    python tools/bench_pipeline.py [--out profiles/pipeline_bench.json] [--quick] [--flip-test]
 
 Per frame, median wall time ending in a device synchronise, warm, the variants ALTERNATED in one process (so that clock ramps and
 neighbours hit them alike):
@@ -13,6 +13,11 @@ through min_box_score from the detector's own scores and recorded).  Weights are
 not people - the work per frame is what is measured.  The kernel breakdown comes from a run of its own,
 `rocprofv3 --kernel-trace --stats --output-format csv -d <dir> -o pipe -- python tools/bench_pipeline.py --quick`; its pipe_kernel_stats.csv
 is kept as profiles/pipeline_kernel_stats.csv.  The pose models run with tile timing off (autotune = False): see pose_model.
+
+--flip-test measures what the flip test costs instead: the frame at 32 live persons with `flip_test` off and on, eager and graphed (and
+the off / graphed frame a second time: the measurement's own spread), plus the two kernels it adds (sp_mirror_w on 32 crops,
+sp_heat_map_flip_merge on 32 x 17 heat maps) timed with device events over back-to-back launches.  The result is merged into --out under
+the key "flip_test"; the other keys of the file stay.
 """
 from __future__ import annotations
 
@@ -83,10 +88,70 @@ def summary(ts):
     return {"median_ms": float(np.median(a)), "p25_ms": float(a[len(a) // 4]), "p75_ms": float(a[(3 * len(a)) // 4]), "min_ms": float(a[0])}
 
 
+def kernel_us(fn, launches=200, rounds=5):
+    """Median over `rounds` of (device-event time of `launches` back-to-back launches) / launches, in microseconds."""
+    out = []
+    for _ in range(rounds + 1):                                   # the first round warms up
+        t0, t1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        t0.record()
+        for _ in range(launches):
+            fn()
+        t1.record()
+        t1.synchronize()
+        out.append(t0.elapsed_time(t1) * 1e3 / launches)
+    return float(np.median(out[1:]))
+
+
+def flip_test_bench(args, det, img, decoder):
+    from simple_pose_amd.metrics import merge_flipped, mirror_input
+    reps, warm = (5, 2) if args.quick else (40, 5)
+    crops = torch.from_numpy(np.random.default_rng(1).integers(0, 256, (2 * CAPACITY, 256, 192, 3), dtype=np.uint8)).to(DEV)
+    hm = torch.from_numpy(np.random.default_rng(2).standard_normal((2 * CAPACITY, 17, 64, 48)).astype(np.float32)).to(DEV)
+    res = {"device": torch.cuda.get_device_name(0), "capacity": CAPACITY, "reps": reps, "pose_autotune": False, "kernels": {
+        "sp_mirror_w u8 [32,256,192,3] back_to_back_us": kernel_us(lambda: mirror_input(crops[:CAPACITY], out=crops[CAPACITY:])),
+        "sp_heat_map_flip_merge f32 [32,17,64,48] in place back_to_back_us": kernel_us(
+            lambda: merge_flipped(hm[:CAPACITY], hm[CAPACITY:], out=hm[:CAPACITY]))}, "runs": []}
+    print(json.dumps(res["kernels"]), flush=True)
+    for head, dtype in ([("dconv", "fp32")] if args.quick else [("dconv", "fp32"), ("duc", "bf16")]):
+        model = pose_model(head, dtype)
+        off = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY)
+        on = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY, flip_test=True)
+        frame = lambda est, graph: (setattr(est, "use_graph", graph), est.estimate(img))[1]
+        variants = {"off_eager": lambda: frame(off, False), "off_graph": lambda: frame(off, True), "on_eager": lambda: frame(on, False),
+                    "on_graph": lambda: frame(on, True), "off_graph2": lambda: frame(off, True)}
+        first = {k: fn() for k, fn in variants.items()}
+        times = {k: [] for k in variants}
+        for r in range(warm + reps):
+            for k, fn in variants.items():
+                t = wall_ms(fn)
+                if r >= warm:
+                    times[k].append(t)
+        graphs = [next(iter(e._frames.values())).graph is not None and len(e._frames) == 1 for e in (off, on)]
+        run = {"pose": f"resnet50-{head} {dtype}", "poses_kept_off": len(first["off_graph"]), "poses_kept_on": len(first["on_graph"]),
+               "graph_equals_eager": bool(first["off_graph"].coco(0) == first["off_eager"].coco(0) and first["on_graph"].coco(0) == first["on_eager"].coco(0)),
+               "one_graph_per_estimator": bool(all(graphs))}
+        run.update({k: summary(v) for k, v in times.items()})
+        run["off_graph_self_spread_ms"] = abs(run["off_graph"]["median_ms"] - run["off_graph2"]["median_ms"])
+        run["flip_cost_graph_ms"] = run["on_graph"]["median_ms"] - run["off_graph"]["median_ms"]
+        run["flip_cost_eager_ms"] = run["on_eager"]["median_ms"] - run["off_eager"]["median_ms"]
+        res["runs"].append(run)
+        print(json.dumps(run), flush=True)
+    if not args.quick:
+        doc = {}
+        if os.path.isfile(args.out):
+            with open(args.out) as fh:
+                doc = json.load(fh)
+        doc["flip_test"] = res
+        with open(args.out, "w") as fh:
+            json.dump(doc, fh, indent=1)
+        print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipeline_bench.json"))
     ap.add_argument("--quick", action="store_true", help="DConv fp32 at n = 32 only, few repetitions (the kernel-trace run)")
+    ap.add_argument("--flip-test", action="store_true", help="the frame at 32 persons with the flip test off / on, and its two kernels")
     args = ap.parse_args()
     reps, warm = (5, 2) if args.quick else (40, 5)
     det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
@@ -96,6 +161,8 @@ def main():
     found = det.single_predict(img)
     scores = np.zeros(0, np.float32) if isinstance(found, list) else found[found[:, 5] == 0][:, 4].cpu().numpy()
     decoder = GaussTaylorKeyPointDecoder()
+    if args.flip_test:
+        return flip_test_bench(args, det, img, decoder)
     out = {"device": torch.cuda.get_device_name(0), "source": [640, 640], "detector": "s fp32", "capacity": CAPACITY, "detections": int(scores.size),
            "reps": reps, "pose_autotune": False, "runs": []}
     models = [("dconv", "fp32")] if args.quick else [("dconv", "fp32"), ("duc", "bf16")]
@@ -129,6 +196,9 @@ def main():
             out["runs"].append(run)
             print(json.dumps(run), flush=True)
     if not args.quick:
+        if os.path.isfile(args.out):                             # a --flip-test run's results live in the same file
+            with open(args.out) as fh:
+                out.update({k: v for k, v in json.load(fh).items() if k == "flip_test"})
         with open(args.out, "w") as fh:
             json.dump(out, fh, indent=1)
         print("wrote", args.out)
