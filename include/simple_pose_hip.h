@@ -754,6 +754,36 @@ int sp_mirror_w(const void* src, void* dst, int64_t rows, int w, int elem_bytes,
 int sp_heat_map_flip_merge(const float* hm, const float* hm_flipped, const int32_t* perm_host, int batch, int joints, int h, int w, int shift,
                            float* out, void* stream);
 
+/* ---- tracking: persistent identities across video frames, and the next frame's boxes without the detector ---------------------------------
+ * (No new ABI version: these are additions.)  The track state is DEVICE memory the caller owns between frames, `slots` (1 .. 256) tracks:
+ *   t_id int32 [slots] (0 = free), t_age int32 [slots] (frames the track was seen in), t_miss int32 [slots] (frames since it was last seen),
+ *   t_kps double [slots, joints, 3], t_area double [slots], t_conf fp32 [slots] (the detector confidence carried along), next_id int32 [1]
+ *   (the id the next new track gets; ids start at 1 when the caller initialises it to 1, and are never reused).
+ * sp_track_associate: one image's kept poses - rows keep[seg[0] .. seg[0] + keep_count[0]) of kps [rows, joints, 3] / area [rows] /
+ * box fp32 [rows, 5] (column 4: confidence), exactly what sp_topdown_plan, sp_pose_rescore and sp_oks_nms leave behind, in pick order;
+ * n <= slots (more are ignored) - against the tracks:
+ *   1. similarity [slots, slots] double: S[t, p] = oks_iou(track t's last pose, pose p) as sp_oks_nms computes it (the same function, no
+ *      visibility threshold, sigmas_host: `joints` doubles in HOST memory or NULL = COCO's 17) for live t and p < n, -1 elsewhere;
+ *   2. greedy matching over the pairs in (S descending, slot ascending, pose ascending) order: a pair matches when both sides are free and
+ *      S >= match_thre (a NaN never matches);
+ *   3. a matched track takes the pose (kps, area, confidence), miss = 0, age += 1;
+ *   4. unmatched poses, in pick order, take the lowest free slot (free at the start of the call), and when none is left the unmatched track
+ *      with the largest miss (ties: lowest slot): id = next_id++, age = 1, miss = 0;
+ *   5. every other unmatched track: miss += 1, and freed (id = age = miss = 0) once miss > max_age;
+ *   6. track_id int32 [rows]: the id of every kept row, 0 for the rest.
+ * Two launches (a grid over the pairs, then one workgroup); no copy, no synchronisation, capturable.  Works with zero tracks and zero poses. */
+int sp_track_associate(const double* kps, const double* area, const float* box, const int32_t* keep, const int32_t* keep_count,
+                       const int32_t* seg, int rows, int joints, const double* sigmas_host, double match_thre, int max_age, int slots,
+                       int32_t* t_id, int32_t* t_age, int32_t* t_miss, double* t_kps, double* t_area, float* t_conf, int32_t* next_id,
+                       double* similarity, int32_t* track_id, void* stream);
+/* The boxes of the tracks seen in the last frame (id != 0 && miss == 0), in slot order, as detector rows: det fp32 [1, max_det, 6] rows
+ * (x1, y1, x2, y2, conf, cls), counts[0] = their number - the input sp_topdown_plan reads; max_det >= slots, rows counts[0] .. slots-1 are
+ * zeroed.  fp32 from the key points cast to fp32, contraction off: min / max of the joints with c > in_vis_thre (of all joints when fewer
+ * than two qualify; a NaN coordinate is skipped), scaled about its centre by box_expand, at least 1 px wide and high, clipped to
+ * [0, img_w] x [0, img_h] (a NaN edge becomes 0).  One launch of one workgroup. */
+int sp_track_boxes(const int32_t* t_id, const int32_t* t_miss, const double* t_kps, const float* t_conf, int slots, int joints,
+                   float in_vis_thre, float box_expand, float cls, int img_w, int img_h, int max_det, float* det, int32_t* counts, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -188,6 +188,9 @@ SYMBOLS = {
     "sp_warp_affine_plan_u8c3": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
     "sp_mirror_w": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
     "sp_heat_map_flip_merge": (c_int, [_P, _P, ctypes.POINTER(c_int32), c_int, c_int, c_int, c_int, c_int, _P, _P]),
+    "sp_track_associate": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
+                                   _P, _P]),
+    "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
 }
 
 _lib = None

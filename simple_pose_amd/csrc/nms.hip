@@ -4,16 +4,13 @@
 // trip; here the decoded key points never leave the device.  One workgroup per image; all arithmetic in fp64, operation by
 // operation as numpy evaluates it (contraction OFF; numpy's pairwise add.reduce order for the 17-term sums).
 #include "sp_common.h"
-#include "sp_oks.h"      // np_pairwise_sum, the COCO sigmas (shared with cocoeval.hip)
+#include "sp_oks.h"      // np_pairwise_sum, the COCO sigmas (shared with cocoeval.hip), oks_one / NmsVar (shared with track.hip)
 
 #pragma clang fp contract(off)
 
 namespace {
 
-constexpr int NMS_MAX_JOINTS = 64;
 constexpr int NMS_MAX_GROUP = 2048;
-
-struct NmsVar { double v[NMS_MAX_JOINTS]; };
 
 // eval.py:166-174: score = box_score * mean(kpt_scores[kpt_scores > in_vis_thre]) (0 without a visible joint); also widens the
 // fp32 decoder output to the float64 the reference's JSON round trip produces.
@@ -34,24 +31,6 @@ __global__ void pose_rescore_kernel(const float* __restrict__ kps, const double*
     }
     const double m = k > 0 ? np_pairwise_sum(buf, k) / (double)k : 0.0;
     score[p] = box_score[p] * m;
-}
-
-// oks_iou (naive_data.py:120-150) of the pick against one candidate
-__device__ double oks_one(const double* pick /* LDS [J][3] */, const double* __restrict__ cand, double pick_area, double cand_area,
-                          const NmsVar& var, int J, double vis_thresh) {
-    double term[NMS_MAX_JOINTS];
-    float vis_sum = 0.f;
-    const double denom = (pick_area + cand_area) / 2 + 1e-12;
-    for (int j = 0; j < J; ++j) {
-        const double dx = cand[j * 3] - pick[j * 3], dy = cand[j * 3 + 1] - pick[j * 3 + 1];
-        const double e = (dx * dx + dy * dy) / var.v[j] / denom / 2;
-        float vis = 1.f;
-        if (vis_thresh >= 0) vis = (cand[j * 3 + 2] > vis_thresh && pick[j * 3 + 2] > vis_thresh) ? 1.f : 0.f;
-        term[j] = exp(-e) * (double)vis;
-        vis_sum += vis;
-    }
-    const float den = vis_sum + (float)1e-12;            // float32 + weak python float stays float32
-    return np_pairwise_sum(term, J) / (double)den;
 }
 
 // oks_nms (naive_data.py:153-173), one workgroup per image: rank sort (descending score, ties: higher index first), then the
@@ -138,10 +117,7 @@ extern "C" int sp_oks_nms(const double* kps, const double* scores, const double*
     SP_REQUIRE(sigmas_host || joints == 17, "sp_oks_nms: the default sigmas are COCO's 17; pass sigmas for %d joints", joints);
     SP_REQUIRE(max_group >= 0 && max_group <= NMS_MAX_GROUP, "sp_oks_nms: %d persons in one image (limit %d)", max_group, NMS_MAX_GROUP);
     NmsVar var;
-    for (int j = 0; j < joints; ++j) {
-        const double s = sigmas_host ? sigmas_host[j] : sp_coco_sigma10(j) / 10.0;   // naive_data.py:131-133
-        var.v[j] = (s * 2) * (s * 2);
-    }
+    sp_oks_fill_var(var, sigmas_host, joints);
     hipLaunchKernelGGL(oks_nms_kernel, dim3(groups), dim3(256), 0, (hipStream_t)stream, kps, scores, areas, seg, joints, var, thresh, vis_thresh,
                        keep, keep_count);
     return sp_check_launch("oks_nms_kernel");

@@ -1,5 +1,6 @@
-// sp_oks.h - what the two OKS users (nms.hip: oks_nms; cocoeval.hip: the keypoint evaluator) share: numpy's summation order and
-// COCO's per-joint sigmas.  Both restate numpy float64 code operation by operation, so both sum the per-joint terms as numpy does.
+// sp_oks.h - what the OKS users (nms.hip: oks_nms; track.hip: the tracker's association; cocoeval.hip: the keypoint evaluator) share:
+// numpy's summation order, COCO's per-joint sigmas, and oks_iou of one pair (nms.hip and track.hip call the one oks_one below).  All
+// restate numpy float64 code operation by operation, so all sum the per-joint terms as numpy does.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,4 +30,36 @@ __device__ inline double np_pairwise_sum(const double* a, int n) {
 inline double sp_coco_sigma10(int j) {
     static const double coco[17] = {.26, .25, .25, .35, .35, .79, .79, .72, .72, .62, .62, 1.07, 1.07, .87, .87, .89, .89};
     return coco[j];
+}
+
+// ---- oks_iou of one pair (nms.hip's greedy loop, track.hip's similarity matrix) ------------------------------------------------------
+constexpr int NMS_MAX_JOINTS = 64;
+
+struct NmsVar { double v[NMS_MAX_JOINTS]; };             // (2 sigma_j)^2, travels as a kernel argument
+
+// naive_data.py:131-133: `sigmas_host` (`joints` doubles in HOST memory) or, when NULL, COCO's 17
+inline void sp_oks_fill_var(NmsVar& var, const double* sigmas_host, int joints) {
+    for (int j = 0; j < joints; ++j) {
+        const double s = sigmas_host ? sigmas_host[j] : sp_coco_sigma10(j) / 10.0;
+        var.v[j] = (s * 2) * (s * 2);
+    }
+}
+
+// oks_iou (naive_data.py:120-150) of the pick against one candidate; vis_thresh < 0: in_vis_thresh None (every joint counts)
+__device__ inline double oks_one(const double* pick /* [J][3] */, const double* __restrict__ cand, double pick_area, double cand_area,
+                                 const NmsVar& var, int J, double vis_thresh) {
+#pragma clang fp contract(off)
+    double term[NMS_MAX_JOINTS];
+    float vis_sum = 0.f;
+    const double denom = (pick_area + cand_area) / 2 + 1e-12;
+    for (int j = 0; j < J; ++j) {
+        const double dx = cand[j * 3] - pick[j * 3], dy = cand[j * 3 + 1] - pick[j * 3 + 1];
+        const double e = (dx * dx + dy * dy) / var.v[j] / denom / 2;
+        float vis = 1.f;
+        if (vis_thresh >= 0) vis = (cand[j * 3 + 2] > vis_thresh && pick[j * 3 + 2] > vis_thresh) ? 1.f : 0.f;
+        term[j] = exp(-e) * (double)vis;
+        vis_sum += vis;
+    }
+    const float den = vis_sum + (float)1e-12;            // float32 + weak python float stays float32
+    return np_pairwise_sum(term, J) / (double)den;
 }

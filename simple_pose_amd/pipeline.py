@@ -38,6 +38,7 @@ class PoseResult:
     score: np.ndarray                # float64 [n]: box score x mean of the visible joints' max_val (eval.py:166-174)
     box: np.ndarray                  # float32 [n, 5]: x1, y1, x2, y2, detector confidence
     dropped: int = 0                 # selected detections of this image that did not fit `capacity`
+    track_id: np.ndarray = None      # int32 [n]: the persons' identities (tracking.PoseTracker.update only; None from estimate*)
 
     def __len__(self) -> int:
         return int(self.score.shape[0])
@@ -77,7 +78,8 @@ class _Frame:
         self.crops = z(((2 * cap if flip_test else cap), in_hw[0], in_hw[1], 3), torch.uint8)    # flip test: the crops, then their mirrors
         fields = (("kps64", (cap, J, 3), torch.float64), ("score", (cap,), torch.float64), ("box", (cap, 5), torch.float32),
                   ("keep", (cap,), torch.int32), ("keep_count", (B,), torch.int32), ("seg", (B + 1,), torch.int32),
-                  ("status", (B,), torch.int32), ("dropped", (B,), torch.int32), ("counts", (B,), torch.int32))
+                  ("status", (B,), torch.int32), ("dropped", (B,), torch.int32), ("counts", (B,), torch.int32),
+                  ("track_id", (cap,), torch.int32))             # written by tracking.PoseTracker's frames only
         self.layout, off = {}, 0
         for name, shape, dt in fields:
             nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
@@ -281,9 +283,10 @@ class TopDownPoseEstimator(object):
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
         fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self._pose_batch(), dev), fr.ws)
 
-    def _results(self, fr: _Frame) -> List[PoseResult]:
+    def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
+        """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
         h = fr.fetch()
-        if (h["status"] & 1).any():
+        if detected and (h["status"] & 1).any():
             b = int(np.nonzero(h["status"] & 1)[0][0])
             raise HipLibraryError(f"image {b}: more than {_lib.SP_YOLO_NMS_MAX_CANDIDATES} detector candidates after the multi-label expansion "
                                   "(raise the detector's conf_thresh)")
@@ -293,7 +296,8 @@ class TopDownPoseEstimator(object):
             if n < 0:
                 raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
             rows = h["keep"][lo:lo + n]
-            out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b])))
+            out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b]),
+                                  h["track_id"][rows] if tracked else None))
         return out
 
     # -- public surface -----------------------------------------------------------------------------------------------------------------

@@ -1,0 +1,193 @@
+"""Persons across video frames: persistent identities on top of `TopDownPoseEstimator`, and frames that leave the detector out.
+
+    trk = PoseTracker(estimator, slots=None, match_thre=0.5, max_age=30, detect_every=1, box_expand=1.25, sigmas=None)
+    res = trk.update(img)      # PoseResult with track_id: int32 [n], aligned with keypoints / score / box
+    trk.reset()
+
+The association runs on the device, on the estimator's stream, right after sp_oks_nms: sp_track_associate matches the frame's kept poses
+with the tracks by OKS (the similarity OKS-NMS uses, the same device function), greedily, best pair first; unmatched poses start new
+tracks (ids 1, 2, ... never reused), tracks unseen for more than `max_age` frames are freed.  The track state is device memory owned by
+the tracker; the ids come back in the frame's packed buffer, so a tracked frame still ends in ONE device-to-host copy, and with
+`estimator.use_graph` it is ONE graph replay.  There is no CPU fallback.
+
+Two kinds of frame, chosen by the host alone (from its own counters and the previous result, no extra synchronisation):
+  detector frame    _detect -> _poses -> sp_track_associate: the first frame, the first after reset(), every `detect_every`-th frame (counted
+                    from the last detector frame), and whenever the previous frame returned no person;
+  propagated frame  sp_track_boxes -> _poses -> sp_track_associate: every other frame.  The boxes are derived from the poses the tracker
+                    just saw (the tracks with miss == 0); the detector program is NOT launched at all, so persons who enter the scene
+                    are only seen at the next detector frame.
+Tracks live in source-image pixels: call reset() when the stream (or its size) changes; propagated boxes are clipped to the image they
+are used on.
+
+`match_thre`, `max_age` and `box_expand` are design choices, not tuned values: there are no trained weights in this repository to tune
+them on."""
+from __future__ import annotations
+
+import ctypes
+from typing import Dict
+
+import numpy as np
+import torch
+
+from . import _lib
+from .pipeline import PoseResult, TopDownPoseEstimator, _Frame
+
+P = _lib.ptr
+MAX_SLOTS = 256                      # one thread per track in the match kernel (sp_track_associate)
+
+
+class PoseTracker(object):
+    """`estimator`: a TopDownPoseEstimator (its `flip_test`, `use_graph`, thresholds and capacity apply unchanged).  `slots`: tracks kept
+    at most (capacity .. 256; default: the estimator's capacity, so that every person of a frame finds a slot).  `match_thre`: the least OKS
+    at which a pose continues a track.  `max_age`: frames a track survives without being seen.  `detect_every`: a detector frame every
+    that many frames (1: every frame).  `box_expand`: the factor a propagated box grows about its centre, on top of the key points'
+    extent.  `sigmas`: per-joint OKS sigmas (default COCO's 17; required for any other joint count)."""
+
+    MAX_GRAPHS = 8
+
+    def __init__(self, estimator, slots=None, match_thre: float = 0.5, max_age: int = 30, detect_every: int = 1, box_expand: float = 1.25,
+                 sigmas=None):
+        if not isinstance(estimator, TopDownPoseEstimator):
+            raise TypeError(f"estimator: expected a TopDownPoseEstimator, got {type(estimator).__name__}")
+        if slots is None:
+            slots = estimator.capacity
+        if not isinstance(slots, int) or isinstance(slots, bool) or slots < 1:
+            raise ValueError(f"slots: expected an int in 1..{MAX_SLOTS}, got {slots!r}")
+        if slots > MAX_SLOTS:
+            raise ValueError(f"slots: {slots} exceeds the tracker's limit of {MAX_SLOTS} tracks (one thread per track in the match kernel); "
+                             f"use an estimator with capacity <= {MAX_SLOTS} or pass slots explicitly")
+        if slots < estimator.capacity:
+            raise ValueError(f"slots: {slots} is below the estimator's capacity {estimator.capacity}; every person of a frame needs a slot")
+        if not isinstance(match_thre, (int, float)) or isinstance(match_thre, bool) or not (0.0 < float(match_thre) <= 1.0):
+            raise ValueError(f"match_thre: an OKS in (0, 1], got {match_thre!r}")
+        if not isinstance(max_age, int) or isinstance(max_age, bool) or max_age < 0:
+            raise ValueError(f"max_age: a frame count >= 0, got {max_age!r}")
+        if not isinstance(detect_every, int) or isinstance(detect_every, bool) or detect_every < 1:
+            raise ValueError(f"detect_every: an int >= 1, got {detect_every!r}")
+        if not isinstance(box_expand, (int, float)) or isinstance(box_expand, bool) or not (0.0 < float(box_expand) < float("inf")):
+            raise ValueError(f"box_expand: a positive factor, got {box_expand!r}")
+        if sigmas is not None:
+            sigmas = np.asarray(sigmas, np.float64).reshape(-1)
+            if sigmas.size < 1 or sigmas.size > 64 or not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
+                raise ValueError("sigmas: expected 1..64 positive per-joint values")
+        self.estimator, self.slots = estimator, slots
+        self.match_thre, self.max_age, self.detect_every, self.box_expand = float(match_thre), max_age, detect_every, float(box_expand)
+        self.sigmas = sigmas
+        self.state: Dict[str, torch.Tensor] = {}       # device tensors: id, age, miss, kps, area, conf, next_id (allocated with the first frame)
+        self._sim = None
+        self._graphs: Dict[tuple, tuple] = {}
+        self._since_detect, self._prev_n = 0, 0
+        self.last_frame_kind = None                    # "detector" / "propagated": what the last update ran
+
+    # -- state --------------------------------------------------------------------------------------------------------------------------
+    def _ensure_state(self, J: int) -> None:
+        if self.sigmas is None and J != 17:
+            raise ValueError(f"sigmas: the default OKS sigmas are COCO's 17; the pose model has {J} joints, pass `sigmas`")
+        if self.sigmas is not None and self.sigmas.size != J:
+            raise ValueError(f"sigmas: {self.sigmas.size} values for a pose model with {J} joints")
+        if self.state and self.state["kps"].shape[1] == J:
+            return
+        dev, n = self.estimator.device, self.slots
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        self.state = {"id": z((n,), torch.int32), "age": z((n,), torch.int32), "miss": z((n,), torch.int32), "kps": z((n, J, 3), torch.float64),
+                      "area": z((n,), torch.float64), "conf": z((n,), torch.float32), "next_id": z((1,), torch.int32)}
+        self._sim = z((n, n), torch.float64)
+        self._sig = None if self.sigmas is None else (ctypes.c_double * J)(*self.sigmas.tolist())
+        self._graphs.clear()
+        self.reset()
+
+    def reset(self) -> None:
+        """Forget every track: the next frame is a detector frame and ids restart at 1."""
+        for k, t in self.state.items():
+            t.fill_(1) if k == "next_id" else t.zero_()
+        self._since_detect, self._prev_n = 0, 0
+
+    def tracks(self) -> Dict[str, np.ndarray]:
+        """A host copy of the live tracks (id, age, miss, keypoints, area, conf), in slot order.  For inspection: it synchronises."""
+        if not self.state:
+            return {k: np.zeros(0) for k in ("id", "age", "miss", "keypoints", "area", "conf")}
+        h = {k: v.cpu().numpy() for k, v in self.state.items()}
+        live = h["id"] != 0
+        return {"id": h["id"][live], "age": h["age"][live], "miss": h["miss"][live], "keypoints": h["kps"][live], "area": h["area"][live],
+                "conf": h["conf"][live]}
+
+    # -- the two frames -----------------------------------------------------------------------------------------------------------------
+    def _boxes(self, fr: _Frame, J: int) -> None:
+        est, st = self.estimator, self.state
+        _lib.check(_lib.lib().sp_track_boxes(P(st["id"]), P(st["miss"]), P(st["kps"]), P(st["conf"]), self.slots, J, est.in_vis_thre,
+                                             self.box_expand, float(max(est.person_cls, 0)), fr.W, fr.H, fr.max_det, P(fr.det), P(fr.counts),
+                                             _lib.current_stream(est.device)), "sp_track_boxes")
+
+    def _associate(self, fr: _Frame, J: int) -> None:
+        est, st = self.estimator, self.state
+        _lib.check(_lib.lib().sp_track_associate(P(fr.kps64), P(fr.area), P(fr.box), P(fr.keep), P(fr.keep_count), P(fr.seg), est.capacity, J,
+                                                 self._sig, self.match_thre, self.max_age, self.slots, P(st["id"]), P(st["age"]), P(st["miss"]),
+                                                 P(st["kps"]), P(st["area"]), P(st["conf"]), P(st["next_id"]), P(self._sim), P(fr.track_id),
+                                                 _lib.current_stream(est.device)), "sp_track_associate")
+
+    def _launch(self, fr: _Frame, detect: bool, det_prog, pose_prog, single_stream: bool) -> None:
+        J = pose_prog.out_shape[0]
+        if detect:
+            self.estimator._detect(fr, det_prog, single_stream)
+        else:
+            self._boxes(fr, J)
+        self.estimator._poses(fr, pose_prog, single_stream)
+        self._associate(fr, J)
+
+    def _params(self, det_prog, pose_prog) -> tuple:
+        return (self.estimator._params(det_prog, pose_prog), self.match_thre, self.max_age, self.box_expand, self.slots, id(self._sim))
+
+    def _graph(self, fr: _Frame, detect: bool, det_prog, pose_prog):
+        key = (fr.H, fr.W, detect)
+        entry = self._graphs.get(key)
+        params = self._params(det_prog, pose_prog)
+        if entry is not None and entry[0] is fr and entry[2] == params:
+            return entry[1]
+        est, dev = self.estimator, self.estimator.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                # warm-up outside the capture, as the estimator's: pools and workspaces get allocated here.
+            if detect:                               # Without the association: it allocates nothing, and the tracks must advance once per frame
+                est._detect(fr, det_prog, True)
+            est._poses(fr, pose_prog, True)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._launch(fr, detect, det_prog, pose_prog, True)
+        keepalive = (det_prog, pose_prog, None if det_prog is None else det_prog.pool_for(1, dev), pose_prog.pool_for(est._pose_batch(), dev),
+                     getattr(fr, "ws", None), self.state, self._sim)
+        self._graphs.pop(key, None)
+        if len(self._graphs) >= self.MAX_GRAPHS:
+            self._graphs.pop(next(iter(self._graphs)))
+        self._graphs[key] = (fr, graph, params, keepalive)
+        return graph
+
+    @torch.no_grad()
+    def update(self, img) -> PoseResult:
+        """One uint8 BGR image [H, W, 3] (numpy or CUDA), the next frame of the stream -> the persons in it with their `track_id`s.
+        A propagated frame (see the module docstring) does not run the detector: new persons appear at the next detector frame."""
+        est = self.estimator
+        img = est._shape_of(img, batched=False)
+        imgs = img[None]
+        H, W = imgs.shape[1], imgs.shape[2]
+        detect = self._prev_n == 0 or self._since_detect >= self.detect_every
+        det_prog = None
+        if detect:
+            g = est.detector.transform.geometry(H, W)
+            det_prog = est.detector.program(g["out_h"], g["out_w"])
+        pose_prog = est._pose_program()
+        J = pose_prog.out_shape[0]
+        self._ensure_state(J)
+        fr = est._frame(1, H, W, est.MAX_DET, J)
+        est._load(fr, imgs)
+        self._prev_n = 0                             # (a frame that raises below is followed by a detector frame)
+        if est.use_graph:
+            self._graph(fr, detect, det_prog, pose_prog).replay()
+        else:
+            self._launch(fr, detect, det_prog, pose_prog, False)
+        res = est._results(fr, tracked=True, detected=detect)[0]
+        self._since_detect = 1 if detect else self._since_detect + 1
+        self._prev_n = len(res)
+        self.last_frame_kind = "detector" if detect else "propagated"
+        return res

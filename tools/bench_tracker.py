@@ -1,0 +1,119 @@
+"""tools/bench_tracker.py - what tracking costs per frame, and what leaving the detector out of three frames in four gains, on one MI355X.
+
+    python tools/bench_tracker.py [--out profiles/tracker_bench.json] [--quick]
+
+Per frame, median wall time ending in a device synchronise, warm, the variants ALTERNATED in one process (so that clock ramps and
+neighbours hit them alike), all graphed (one replay per frame):
+  estimate   TopDownPoseEstimator.estimate, the untracked frame
+  track1     PoseTracker.update, detect_every = 1: every frame runs the detector; track1 - estimate is the cost of the association
+  track4     PoseTracker.update, detect_every = 4: one detector frame, then three frames whose boxes come from the tracks
+  estimate2  the untracked frame again: the difference of the two medians is the measurement's own spread
+The set-up is tools/bench_pipeline.py's: the s detector on a 640 x 640 source, capacity 32, ResNet50-DConv fp32 and ResNet50-DUC bf16, the
+tests' conditioned (random) weights - the detections are not people, the work per frame is what is measured.  track4's median is over
+all frames, detector frames included; its two kinds of frame are also reported apart.  The two new entry points are timed with device
+events over back-to-back launches on a full state (32 tracks, 32 poses): sp_track_associate is two kernels per launch.
+"""
+from __future__ import annotations
+
+import argparse
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+if ROOT not in sys.path:
+    sys.path.insert(0, ROOT)
+
+from simple_pose_amd import _lib  # noqa: E402
+from simple_pose_amd.detector.nets.yolov5 import YOLOv5  # noqa: E402
+from simple_pose_amd.detector.yolov5_detector import YOLOv5Detector  # noqa: E402
+from simple_pose_amd.metrics import GaussTaylorKeyPointDecoder  # noqa: E402
+from simple_pose_amd.pipeline import TopDownPoseEstimator  # noqa: E402
+from simple_pose_amd.tracking import PoseTracker  # noqa: E402
+from tests.detector_ref import detector_state_dict  # noqa: E402
+from tools.bench_pipeline import CAPACITY, DEV, kernel_us, pose_model, summary, wall_ms  # noqa: E402
+
+P = _lib.ptr
+
+
+def kernel_times():
+    """The two entry points alone, on a full state: 32 tracks that all find their pose again (the state stays full from launch to launch)."""
+    rng = np.random.default_rng(3)
+    slots, J = CAPACITY, 17
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    kps = d(np.concatenate([rng.uniform(0, 640, (slots, J, 2)), rng.uniform(0.3, 1, (slots, J, 1))], 2))
+    area, box = d(rng.uniform(8000, 40000, slots)), d(rng.uniform(0, 1, (slots, 5)).astype(np.float32))
+    keep, kc, seg = d(np.arange(slots, dtype=np.int32)), d(np.array([slots], np.int32)), d(np.array([0, slots], np.int32))
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)
+    st = {"id": z((slots,), torch.int32), "age": z((slots,), torch.int32), "miss": z((slots,), torch.int32), "kps": z((slots, J, 3), torch.float64),
+          "area": z((slots,), torch.float64), "conf": z((slots,), torch.float32), "next_id": torch.ones((1,), dtype=torch.int32, device=DEV)}
+    sim, ids = z((slots, slots), torch.float64), z((slots,), torch.int32)
+    det, counts = z((1, 300, 6), torch.float32), z((1,), torch.int32)
+    lib, stream = _lib.lib(), _lib.current_stream(torch.device(DEV))
+    assoc = lambda: _lib.check(lib.sp_track_associate(P(kps), P(area), P(box), P(keep), P(kc), P(seg), slots, J, None, 0.5, 30, slots, P(st["id"]),
+                                                      P(st["age"]), P(st["miss"]), P(st["kps"]), P(st["area"]), P(st["conf"]), P(st["next_id"]), P(sim),
+                                                      P(ids), stream), "sp_track_associate")
+    boxes = lambda: _lib.check(lib.sp_track_boxes(P(st["id"]), P(st["miss"]), P(st["kps"]), P(st["conf"]), slots, J, 0.2, 1.25, 0.0, 640, 640, 300,
+                                                  P(det), P(counts), stream), "sp_track_boxes")
+    assoc()
+    out = {"sp_track_associate 32 tracks x 32 poses (2 kernels) back_to_back_us": kernel_us(assoc),
+           "sp_track_boxes 32 tracks back_to_back_us": kernel_us(boxes)}
+    assert int(counts.item()) == slots and sorted(ids.cpu().tolist()) == list(range(1, slots + 1))      # every launch matched all 32 again
+    return out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tracker_bench.json"))
+    ap.add_argument("--quick", action="store_true", help="DConv fp32 only, few repetitions; nothing is written")
+    args = ap.parse_args()
+    reps, warm = (8, 4) if args.quick else (80, 8)                # multiples of 4: track4 sees whole detector / propagated cycles
+    det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
+    det.conf_thresh, det.iou_thresh = 0.02, 0.45
+    img = np.random.default_rng(0).integers(0, 256, (640, 640, 3), dtype=np.uint8)
+    decoder = GaussTaylorKeyPointDecoder()
+    out = {"device": torch.cuda.get_device_name(0), "source": [640, 640], "detector": "s fp32", "capacity": CAPACITY, "reps": reps,
+           "pose_autotune": False, "kernels": kernel_times(), "runs": []}
+    print(json.dumps(out["kernels"]), flush=True)
+    for head, dtype in ([("dconv", "fp32")] if args.quick else [("dconv", "fp32"), ("duc", "bf16")]):
+        model = pose_model(head, dtype)
+        est = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY)
+        trk1, trk4 = PoseTracker(est, detect_every=1), PoseTracker(est, detect_every=4)
+        variants = {"estimate": lambda: est.estimate(img), "track1": lambda: trk1.update(img), "track4": lambda: trk4.update(img),
+                    "estimate2": lambda: est.estimate(img)}
+        first = {k: fn() for k, fn in variants.items()}
+        times = {k: [] for k in variants}
+        kinds = []
+        for r in range(warm + reps):
+            for k, fn in variants.items():
+                t = wall_ms(fn)
+                if r >= warm:
+                    times[k].append(t)
+                    if k == "track4":
+                        kinds.append(trk4.last_frame_kind)
+        run = {"pose": f"resnet50-{head} {dtype}", "poses_kept": len(first["estimate"]), "tracks_live": int(trk1.tracks()["id"].size),
+               "track1_ids_stable": bool(trk1.update(img).track_id.tolist() == first["track1"].track_id.tolist()),
+               "track4_propagated_share": kinds.count("propagated") / max(1, len(kinds))}
+        run.update({k: summary(v) for k, v in times.items()})
+        t4 = np.asarray(times["track4"])
+        for kind in ("detector", "propagated"):
+            sel = t4[np.asarray(kinds) == kind]
+            if sel.size:
+                run[f"track4_{kind}_frames"] = summary(sel)
+        run["estimate_self_spread_ms"] = abs(run["estimate"]["median_ms"] - run["estimate2"]["median_ms"])
+        run["association_cost_ms"] = run["track1"]["median_ms"] - run["estimate"]["median_ms"]
+        run["track4_mean_ms"] = float(t4.mean())
+        run["detect_every_4_gain_ms"] = run["estimate"]["median_ms"] - run["track4_mean_ms"]
+        out["runs"].append(run)
+        print(json.dumps(run), flush=True)
+    if not args.quick:
+        with open(args.out, "w") as fh:
+            json.dump(out, fh, indent=1)
+        print("wrote", args.out)
+
+
+if __name__ == "__main__":
+    main()
