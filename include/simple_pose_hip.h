@@ -784,6 +784,87 @@ int sp_track_associate(const double* kps, const double* area, const float* box, 
 int sp_track_boxes(const int32_t* t_id, const int32_t* t_miss, const double* t_kps, const float* t_conf, int slots, int joints,
                    float in_vis_thre, float box_expand, float cls, int img_w, int img_h, int max_det, float* det, int32_t* counts, void* stream);
 
+/* ---- baseline JPEG decoding: file bytes in, uint8 BGR [H,W,3] images out ---------------------------------------------------------------------
+ * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
+ * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF
+ * orientation is not applied.  Accepted: SOF0, 8-bit samples, 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, one
+ * interleaved scan, 8-bit quantisation tables, APPn / COM segments skipped.  Anything else is refused by sp_jpeg_parse with its own code;
+ * there is no CPU decode path. */
+#define SP_JPEG_ETRUNCATED (-10)   /* a header segment runs past the end of the buffer (the message names the byte offset) */
+#define SP_JPEG_ENOT_JPEG (-11)    /* no SOI, or no marker where one has to be */
+#define SP_JPEG_EPROGRESSIVE (-12) /* SOF2 */
+#define SP_JPEG_EEXTENDED (-13)    /* SOF1, SOF3, SOF5 .. SOF7 (extended sequential, lossless, hierarchical) */
+#define SP_JPEG_EARITHMETIC (-14)  /* SOF9 .. SOF15, DAC */
+#define SP_JPEG_EPRECISION (-15)   /* sample precision other than 8 bits */
+#define SP_JPEG_ECOMPONENTS (-16)  /* neither 1 nor 3 components */
+#define SP_JPEG_ESAMPLING (-17)    /* sampling factors other than 1x1 / 2x1 / 2x2 luma with 1x1 chroma (4:4:0, 4:1:1, ...) */
+#define SP_JPEG_EADOBE (-18)       /* Adobe APP14 segment with a colour transform other than YCbCr on a 3-component file */
+#define SP_JPEG_ESCANS (-19)       /* more than one scan, a scan that does not interleave every component, no scan */
+#define SP_JPEG_ENO_TABLE (-20)    /* a component selects a quantisation or Huffman table the file does not define */
+#define SP_JPEG_EBAD_TABLE (-21)   /* malformed DQT / DHT (16-bit quantisation values, counts that are no prefix code, bad index) */
+#define SP_JPEG_ESIZE (-22)        /* zero or > 16384 width / height, or a file of 2 GiB and more */
+
+/* One file.  sp_jpeg_parse fills everything down to out_bytes; the caller fills the placement fields before sp_jpeg_decode_batch. */
+typedef struct sp_jpeg_desc {
+    int32_t width, height, components;                /* components: 1 (grayscale) or 3 (YCbCr) */
+    int32_t h_samp[3], v_samp[3];                     /* sampling factors (1,1 for a single component) */
+    int32_t quant_sel[3], dc_sel[3], ac_sel[3];       /* table selectors 0..3 per component */
+    int32_t restart_interval;                         /* MCUs per restart segment, 0 = no restart markers */
+    int32_t mcus_x, mcus_y;                           /* ceil(width / (8 hmax)), ceil(height / (8 vmax)) */
+    int32_t ecs_offset, ecs_end;                      /* the entropy-coded data is bytes [ecs_offset, ecs_end) of the file */
+    int32_t segments;                                 /* restart segments found by scanning for FF D0..D7 (1 without markers) */
+    int32_t file_bytes;
+    int32_t coef_count;                               /* int16 coefficients: 64 per block, MCU padding included */
+    int32_t plane_bytes;                              /* uint8 component planes: 64 per block */
+    int32_t out_bytes;                                /* height * width * 3 */
+    int32_t seg_index;                                /* caller: this file's first entry in `seg_offsets` */
+    int32_t reserved;
+    int64_t file_offset;                              /* caller: the file's first byte in `bytes` */
+    int64_t coef_offset;                              /* caller: in int16 elements into `coef` */
+    int64_t plane_offset;                             /* caller: in bytes into `planes`, a multiple of 8 */
+    int64_t out_offset;                               /* caller: in bytes into `out` */
+    uint16_t quant[4][64];                            /* de-zigzagged to natural (row-major) order */
+    uint8_t huff_counts[8][16];                       /* [4 * class + index]: codes of length 1..16 (class 0 = DC, 1 = AC) */
+    uint8_t huff_values[8][256];                      /* the symbols in code order */
+} sp_jpeg_desc;
+
+/* Host only, no GPU call: parse the headers of one file (`size` bytes at `data`, HOST memory) into *desc.  Every marker length is checked
+ * against the buffer.  seg_offsets (HOST, may be NULL with seg_capacity 0) receives the file offset of the first entropy byte of each
+ * restart segment, at most seg_capacity of them; desc->segments is the number found (call again with a larger array when it exceeds the
+ * capacity).  Segment s ends two bytes before segment s + 1 starts (at its FF Dn), the last one at ecs_end (the EOI marker, or the end
+ * of a file that has none).  Returns SP_OK or one of SP_JPEG_E* with the reason, and where relevant the byte offset, in sp_last_error. */
+int sp_jpeg_parse(const uint8_t* data, int64_t size, sp_jpeg_desc* desc, int32_t* seg_offsets, int32_t seg_capacity);
+
+/* status bits sp_jpeg_decode_batch writes per image (0 = decoded) */
+#define SP_JPEG_STATUS_TRUNCATED 1  /* entropy data of a segment ended before its last block */
+#define SP_JPEG_STATUS_BAD_CODE 2   /* bits that are no Huffman code */
+#define SP_JPEG_STATUS_BAD_RUN 4    /* AC run past coefficient 63 */
+#define SP_JPEG_STATUS_SEGMENTS 8   /* segments != ceil(MCUs / restart interval) */
+#define SP_JPEG_STATUS_BAD_TABLE 16 /* Huffman counts that are no prefix code */
+
+/* sp_jpeg_decode_batch `stages` */
+#define SP_JPEG_STAGE_ENTROPY 1
+#define SP_JPEG_STAGE_IDCT 2
+#define SP_JPEG_STAGE_COLOR 4
+#define SP_JPEG_STAGE_ALL 7
+
+/* Decode `count` files of mixed sizes and sampling.  descs_host / descs_dev: the same `count` descriptors in HOST and in DEVICE memory (the
+ * host copy sizes the launches and is checked against every arena size below before anything is launched).  bytes: all files packed in
+ * one DEVICE buffer of bytes_size bytes; seg_offsets int32 [seg_count] DEVICE: the arrays sp_jpeg_parse filled, file s at seg_index;
+ * coef int16 [coef_size], planes uint8 [planes_size], out uint8 [out_size]: DEVICE arenas, image i at its *_offset; the regions of
+ * different images must not overlap (not checked).  status int32 [count] DEVICE.  Image i: out + out_offset = uint8 [height, width, 3] BGR.
+ * `stages`: SP_JPEG_STAGE_ALL, or a subset (a bench / test runs them one at a time; later stages read what earlier ones left):
+ *   entropy  one launch that zeroes every image's coefficient region (and nothing between them), then jpeg_entropy_kernel: one wave per image builds the Huffman lookahead tables in
+ *            LDS, lane s decodes restart segments s, s + 64, ... (a file without restart markers: lane 0 alone) into int16 coefficients in
+ *            natural order, component after component, each a row-major grid of (mcus_x h) x (mcus_y v) blocks; writes status;
+ *   idct     jpeg_idct_kernel: dequantise + islow IDCT, 8 lanes per block -> uint8 component planes (pitch = 8 * blocks per row);
+ *   color    jpeg_color_kernel: fancy upsampling + YCbCr -> BGR.
+ * A damaged stream ends in a non-zero status, never in an access outside the image's own regions; its pixels are unspecified.
+ * Nothing synchronises; count == 0 is a no-op. */
+int sp_jpeg_decode_batch(const sp_jpeg_desc* descs_host, const sp_jpeg_desc* descs_dev, int count, const uint8_t* bytes, int64_t bytes_size,
+                         const int32_t* seg_offsets, int64_t seg_count, int16_t* coef, int64_t coef_size, uint8_t* planes, int64_t planes_size,
+                         uint8_t* out, int64_t out_size, int32_t* status, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -52,6 +52,22 @@ class WgradJob(ctypes.Structure):
                 ("g_channels", c_int32), ("n_valid", c_int32), ("c_valid", c_int32), ("kw_valid", c_int32)]
 
 
+class JpegDesc(ctypes.Structure):
+    """Mirror of `sp_jpeg_desc` (field order is ABI): sp_jpeg_parse fills it down to out_bytes, the caller places the file in the arenas."""
+    _fields_ = [("width", c_int32), ("height", c_int32), ("components", c_int32), ("h_samp", c_int32 * 3), ("v_samp", c_int32 * 3),
+                ("quant_sel", c_int32 * 3), ("dc_sel", c_int32 * 3), ("ac_sel", c_int32 * 3), ("restart_interval", c_int32),
+                ("mcus_x", c_int32), ("mcus_y", c_int32), ("ecs_offset", c_int32), ("ecs_end", c_int32), ("segments", c_int32),
+                ("file_bytes", c_int32), ("coef_count", c_int32), ("plane_bytes", c_int32), ("out_bytes", c_int32), ("seg_index", c_int32),
+                ("reserved", c_int32), ("file_offset", c_int64), ("coef_offset", c_int64), ("plane_offset", c_int64), ("out_offset", c_int64),
+                ("quant", (ctypes.c_uint16 * 64) * 4), ("huff_counts", (ctypes.c_uint8 * 16) * 8), ("huff_values", (ctypes.c_uint8 * 256) * 8)]
+
+
+SP_JPEG_ETRUNCATED, SP_JPEG_ENOT_JPEG, SP_JPEG_EPROGRESSIVE, SP_JPEG_EEXTENDED, SP_JPEG_EARITHMETIC, SP_JPEG_EPRECISION, SP_JPEG_ECOMPONENTS, \
+    SP_JPEG_ESAMPLING, SP_JPEG_EADOBE, SP_JPEG_ESCANS, SP_JPEG_ENO_TABLE, SP_JPEG_EBAD_TABLE, SP_JPEG_ESIZE = range(-10, -23, -1)
+SP_JPEG_STATUS = {1: "entropy data ended early", 2: "invalid Huffman code", 4: "AC run past coefficient 63", 8: "restart segment count mismatch",
+                  16: "invalid Huffman table"}
+SP_JPEG_STAGE_ENTROPY, SP_JPEG_STAGE_IDCT, SP_JPEG_STAGE_COLOR, SP_JPEG_STAGE_ALL = 1, 2, 4, 7
+
 # every symbol include/simple_pose_hip.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -191,6 +207,8 @@ SYMBOLS = {
     "sp_track_associate": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,
                                    _P, _P]),
     "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
+    "sp_jpeg_parse": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32]),
+    "sp_jpeg_decode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
 }
 
 _lib = None
