@@ -784,6 +784,56 @@ int sp_track_associate(const double* kps, const double* area, const float* box, 
 int sp_track_boxes(const int32_t* t_id, const int32_t* t_miss, const double* t_kps, const float* t_conf, int slots, int joints,
                    float in_vis_thre, float box_expand, float cls, int img_w, int img_h, int max_det, float* det, int32_t* counts, void* stream);
 
+/* ---- overlay: the kept poses of one image drawn into it - boxes, limbs, joints, coloured by person (track id) or by part ------------------
+ * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] in and out, 1 <= h, w <= 16384; it reads exactly what sp_oks_nms (and
+ * sp_track_associate) leave behind: rows keep[seg[image] .. seg[image] + keep_count[image]) of kps [rows, joints, 3] / box fp32 [rows, 5] /
+ * track_id int32 [rows] (or NULL), in pick order, the count clamped to `rows` and to the keep list's end as sp_track_associate clamps it.
+ * The pixel rules (simple_pose_amd/csrc/sp_render.h states them once for the device and the host; all integer but one comparison):
+ *   primitive    ONE kind, the capsule {ax, ay, bx, by, r}: every point within r of the segment A-B, int32 in 1/16 px, with a BGR colour.
+ *                q(v) = (int32) rint(v * 16.0) (double, ties to even); a coordinate that is not finite or has |v| > 32768 makes the
+ *                primitive empty (r = -1).  A joint is visible iff its c > in_vis_thre (a NaN c is not).
+ *   per person   4 + edges + joints slots, in this order: the 4 box edges (top, right, bottom, left; radius box_r, all empty when
+ *                box_r == 0), the limbs in skeleton order (A -> B of edge[e], radius limb_r, empty unless both joints are visible), the
+ *                joints in index order (A == B, radius joint_r, empty when not visible).  No compaction: empty slots stay in the array.
+ *   order        primitive index = p * (4 + edges + joints) + slot, applied in ascending order; person slot p holds the pose at pick
+ *                position n - 1 - p, so persons are painted in reverse pick order and the best pose lies on top.
+ *   coverage     of pixel (x, y): 16 samples S = (16x + 4i + 2, 16y + 4j + 2), i, j in 0..3.  In int64, exactly: t = AS.AB, L = AB.AB,
+ *                c = ASx * ABy - ASy * ABx.  A sample is inside by the first rule that applies:  L == 0 or t <= 0: |AS|^2 <= r^2;
+ *                t >= L: |BS|^2 <= r^2;  otherwise (double)c * (double)c <= (double)(r * r) * (double)L (two fp64 products, each rounded
+ *                once; every conversion is exact).  k = the number of inside samples, 0..16.
+ *   blend        a = k * opacity; per channel out = (in * (256 - a) + colour * a + 128) >> 8, primitive after primitive, each step on the
+ *                previous step's result.
+ *   colour       SP_RENDER_COLOUR_PERSON: palette[(track_id - 1) % palette_n] when track_id is given and > 0, else
+ *                palette[pick position % palette_n].  SP_RENDER_COLOUR_PART: limb e palette[e % palette_n], joint j
+ *                palette[j % palette_n], boxes the person colour.
+ * style_host is HOST memory, validated and copied into the kernel arguments (no host-to-device copy: capturable). */
+#define SP_RENDER_COLOUR_PERSON 0
+#define SP_RENDER_COLOUR_PART 1
+#define SP_RENDER_MAX_EDGES 64
+#define SP_RENDER_MAX_PALETTE 32
+#define SP_RENDER_MAX_RADIUS 1024 /* 1/16 px: 64 px */
+typedef struct sp_render_style {
+    int32_t edges;                          /* 0 .. 64 */
+    int32_t edge[SP_RENDER_MAX_EDGES][2];   /* joint indices, each < joints */
+    int32_t joint_r, limb_r, box_r;         /* radii in 1/16 px, 0 .. 1024; box_r == 0: no boxes */
+    int32_t opacity;                        /* 0 .. 16 (sixteenths) */
+    double in_vis_thre;
+    int32_t colour_by;                      /* SP_RENDER_COLOUR_* */
+    int32_t palette_n;                      /* 1 .. 32 */
+    unsigned char palette[SP_RENDER_MAX_PALETTE][3];   /* BGR */
+} sp_render_style;
+/* bytes of the primitive array for `rows` person slots (1 .. 2048) */
+int sp_render_workspace_bytes(int rows, int joints, int edges, int64_t* bytes);
+/* Two launches (one thread per primitive slot; one 256-thread workgroup per 64 x 16 pixel tile, which scans the primitive array in chunks
+ * of 256, lists the primitives whose box meets the tile in index order and applies them to pixels held in registers); no copy, no
+ * synchronisation, capturable.  dst == src (in place) is allowed, a tile nothing touches is then skipped; any other overlap of src and dst
+ * is refused; out of place, untouched tiles are copied.  4-byte accesses when w % 4 == 0 and both pointers are 4-byte aligned, bytes
+ * otherwise.  rows == 0 is a no-op (a copy when dst != src; kps .. workspace are not read).  workspace: sp_render_workspace_bytes, 8-byte
+ * aligned device memory, overwritten by every call. */
+int sp_render_poses_u8c3(const unsigned char* src, unsigned char* dst, int h, int w, const double* kps, const float* box,
+                         const int32_t* track_id /* may be NULL */, const int32_t* keep, const int32_t* keep_count, const int32_t* seg,
+                         int image, int rows, int joints, const sp_render_style* style_host, void* workspace, void* stream);
+
 /* ---- baseline JPEG decoding: file bytes in, uint8 BGR [H,W,3] images out ---------------------------------------------------------------------
  * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
  * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF

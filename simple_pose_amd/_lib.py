@@ -68,6 +68,17 @@ SP_JPEG_STATUS = {1: "entropy data ended early", 2: "invalid Huffman code", 4: "
                   16: "invalid Huffman table"}
 SP_JPEG_STAGE_ENTROPY, SP_JPEG_STAGE_IDCT, SP_JPEG_STAGE_COLOR, SP_JPEG_STAGE_ALL = 1, 2, 4, 7
 
+
+class RenderStyle(ctypes.Structure):
+    """Mirror of `sp_render_style` (field order is ABI): host memory, copied into the kernel arguments by sp_render_poses_u8c3."""
+    _fields_ = [("edges", c_int32), ("edge", (c_int32 * 2) * 64), ("joint_r", c_int32), ("limb_r", c_int32), ("box_r", c_int32),
+                ("opacity", c_int32), ("in_vis_thre", c_double), ("colour_by", c_int32), ("palette_n", c_int32),
+                ("palette", (ctypes.c_uint8 * 3) * 32)]
+
+
+SP_RENDER_COLOUR_PERSON, SP_RENDER_COLOUR_PART = 0, 1
+SP_RENDER_MAX_EDGES, SP_RENDER_MAX_PALETTE, SP_RENDER_MAX_RADIUS = 64, 32, 1024
+
 # every symbol include/simple_pose_hip.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -209,6 +220,8 @@ SYMBOLS = {
     "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
     "sp_jpeg_parse": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32]),
     "sp_jpeg_decode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
+    "sp_render_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
+    "sp_render_poses_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RenderStyle), _P, _P]),
 }
 
 _lib = None

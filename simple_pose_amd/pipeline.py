@@ -13,7 +13,9 @@ zero crops that OKS-NMS never sees), which is what makes the frame capturable - 
 transfer per call brings back the keep list, the counts, the status words and the rows.  There is no CPU fallback.
 With `flip_test=True` the crops are mirrored into a second half of the crop buffer (sp_mirror_w), the pose program runs once on
 `2 * capacity` crops, and sp_heat_map_flip_merge averages the un-mirrored second half into the first before the decode: two more launches
-on the same stream, still one graph."""
+on the same stream, still one graph.
+With `renderer=PoseRenderer(...)` (visualize.py) the kept poses are drawn into a copy of the source image, `PoseResult.image`, by two more
+launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched."""
 from __future__ import annotations
 
 import ctypes
@@ -26,6 +28,7 @@ import torch
 from . import _lib, engine
 from ._lib import HipLibraryError
 from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
+from .visualize import PoseRenderer
 
 P = _lib.ptr
 MAX_CAPACITY = 2048                  # the OKS-NMS group limit (sp_oks_nms)
@@ -39,6 +42,8 @@ class PoseResult:
     box: np.ndarray                  # float32 [n, 5]: x1, y1, x2, y2, detector confidence
     dropped: int = 0                 # selected detections of this image that did not fit `capacity`
     track_id: np.ndarray = None      # int32 [n]: the persons' identities (tracking.PoseTracker.update only; None from estimate*)
+    image: torch.Tensor = None       # uint8 BGR [H, W, 3] on the device, the poses drawn in (estimators with a `renderer` only): a VIEW of the
+                                     # frame's canvas, valid until the next call with the same source shape - .clone() it to keep it
 
     def __len__(self) -> int:
         return int(self.score.shape[0])
@@ -92,6 +97,8 @@ class _Frame:
         self.graph = None
         self.params = None
         self.keepalive = None
+        self.canvas = None               # [B, H, W, 3] and the primitive array: allocated with the first frame of an estimator that has a renderer
+        self.render_ws = None
 
     def fetch(self) -> Dict[str, np.ndarray]:
         """The call's one device-to-host transfer (and its one synchronisation)."""
@@ -120,7 +127,7 @@ class TopDownPoseEstimator(object):
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
                  in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
-                 joint_pairs=None, shift_heatmap: bool = False):
+                 joint_pairs=None, shift_heatmap: bool = False, renderer=None):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -143,6 +150,9 @@ class TopDownPoseEstimator(object):
         # type and disjointness now; the range once the program's joint count is known (_pose_program)
         self.joint_pairs = check_joint_pairs(COCO_JOINT_PAIRS if joint_pairs is None else joint_pairs)
         self.flip_test, self.shift_heatmap = bool(flip_test), bool(shift_heatmap)
+        if renderer is not None and not isinstance(renderer, PoseRenderer):
+            raise TypeError(f"renderer: expected a simple_pose_amd.visualize.PoseRenderer or None, got {type(renderer).__name__}")
+        self.renderer = renderer
         self._perm = None
         self.detector, self.pose_model, self.decoder = detector, pose_model, decoder
         self.capacity, self.person_cls, self.min_box_score = capacity, person_cls, float(min_box_score)
@@ -181,6 +191,9 @@ class TopDownPoseEstimator(object):
         else:
             self._frames.pop(key)                # most recently used last
         self._frames[key] = fr
+        if self.renderer is not None and fr.canvas is None:
+            fr.canvas = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=self.device)
+            fr.render_ws = PoseRenderer.workspace(self.capacity, J, self.device)
         return fr
 
     def _load(self, fr: _Frame, imgs) -> None:
@@ -220,7 +233,8 @@ class TopDownPoseEstimator(object):
     def _params(self, det_prog, pose_prog) -> tuple:
         d = self.detector
         return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
-                id(det_prog), id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap)
+                id(det_prog), id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap,
+                None if self.renderer is None else self.renderer.key())
 
     def _detect(self, fr: _Frame, det_prog, single_stream: bool = False) -> None:
         """letterbox + network + head decode, NMS and the un-letterbox, all on the device (what single_predict / predict compute)."""
@@ -266,6 +280,15 @@ class TopDownPoseEstimator(object):
         _lib.check(lib.sp_oks_nms(P(fr.kps64), P(fr.score), P(fr.area), P(fr.seg), fr.B, cap, J, None, self.oks_thre, -1.0, P(fr.keep),
                                   P(fr.keep_count), stream), "sp_oks_nms")
 
+    def _render(self, fr: _Frame, J: int, tracked: bool = False) -> None:
+        """The overlay of every image's kept poses into the frame's canvas: one sp_render_poses_u8c3 (two launches) per image index, reading
+        the buffers sp_oks_nms (and, `tracked`, sp_track_associate) just wrote.  Nothing without a renderer."""
+        if self.renderer is None:
+            return
+        for b in range(fr.B):
+            self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64, fr.box, fr.track_id if tracked else None, fr.keep, fr.keep_count, fr.seg, b,
+                                 self.capacity, J, fr.render_ws)
+
     def _capture(self, fr: _Frame, det_prog, pose_prog) -> None:
         dev = self.device
         side = torch.cuda.Stream(device=dev)
@@ -273,12 +296,14 @@ class TopDownPoseEstimator(object):
         with torch.cuda.stream(side):                # warm-up outside the capture: activation pools and workspaces get allocated here
             self._detect(fr, det_prog, True)
             self._poses(fr, pose_prog, True)
+            self._render(fr, pose_prog.out_shape[0])
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self._detect(fr, det_prog, True)
             self._poses(fr, pose_prog, True)
+            self._render(fr, pose_prog.out_shape[0])
         fr.graph, fr.params = graph, self._params(det_prog, pose_prog)
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
         fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self._pose_batch(), dev), fr.ws)
@@ -297,7 +322,7 @@ class TopDownPoseEstimator(object):
                 raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
             rows = h["keep"][lo:lo + n]
             out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b]),
-                                  h["track_id"][rows] if tracked else None))
+                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b]))
         return out
 
     # -- public surface -----------------------------------------------------------------------------------------------------------------
@@ -319,6 +344,7 @@ class TopDownPoseEstimator(object):
         else:
             self._detect(fr, det_prog)
             self._poses(fr, pose_prog, False)
+            self._render(fr, pose_prog.out_shape[0])
         return self._results(fr)
 
     @torch.no_grad()
@@ -365,4 +391,5 @@ class TopDownPoseEstimator(object):
         fr.counts.copy_(cnt)
         fr.status.zero_()
         self._poses(fr, pose_prog, False)
+        self._render(fr, pose_prog.out_shape[0])
         return self._results(fr)

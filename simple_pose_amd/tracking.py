@@ -8,7 +8,8 @@ The association runs on the device, on the estimator's stream, right after sp_ok
 with the tracks by OKS (the similarity OKS-NMS uses, the same device function), greedily, best pair first; unmatched poses start new
 tracks (ids 1, 2, ... never reused), tracks unseen for more than `max_age` frames are freed.  The track state is device memory owned by
 the tracker; the ids come back in the frame's packed buffer, so a tracked frame still ends in ONE device-to-host copy, and with
-`estimator.use_graph` it is ONE graph replay.  There is no CPU fallback.
+`estimator.use_graph` it is ONE graph replay.  There is no CPU fallback.  An estimator built with a `renderer` also draws the frame
+(`PoseResult.image`, the persons coloured by track id), inside the same replay.
 
 Two kinds of frame, chosen by the host alone (from its own counters and the previous result, no extra synchronisation):
   detector frame    _detect -> _poses -> sp_track_associate: the first frame, the first after reset(), every `detect_every`-th frame (counted
@@ -133,6 +134,7 @@ class PoseTracker(object):
             self._boxes(fr, J)
         self.estimator._poses(fr, pose_prog, single_stream)
         self._associate(fr, J)
+        self.estimator._render(fr, J, tracked=True)  # (nothing without estimator.renderer) the frame's ids colour the persons
 
     def _params(self, det_prog, pose_prog) -> tuple:
         return (self.estimator._params(det_prog, pose_prog), self.match_thre, self.max_age, self.box_expand, self.slots, id(self._sim))
@@ -150,6 +152,7 @@ class PoseTracker(object):
             if detect:                               # Without the association: it allocates nothing, and the tracks must advance once per frame
                 est._detect(fr, det_prog, True)
             est._poses(fr, pose_prog, True)
+            est._render(fr, pose_prog.out_shape[0], tracked=True)      # (changes no state: whatever ids the frame holds)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
