@@ -154,6 +154,15 @@ int sp_dual_pw_f32(const float* a_main, const float* w_main_packed, const float*
 int sp_dual_pw_bf16(const void* a_main, const void* w_main_packed, const float* scale_main, const float* shift_main, const void* a_short,
                     const void* w_short_packed, const float* scale_short, const float* shift_short, void* y, int64_t rows, int c_main, int c_short,
                     int c_out, int relu, void* stream);
+/* conv3 of an identity-shortcut Bottleneck with 64 mid channels and the NEXT block's conv1 as ONE launch (fp32 NHWC, stride 1; csrc/conv_pw.hip):
+ *     y = relu( bn3(conv1x1_{64->256}(t)) + residual ),   t_next = relu( bn1(conv1x1_{256->c_next}(y)) )      nets/pose_resnet_dconv.py:112-133
+ * t [rows][64], residual / y [rows][256], t_next [rows][c_next], c_next = 64 or 128; weights packed by sp_pack_conv_weights ([256][64], [c_next][256]), the
+ * folded BatchNorms as (scale, shift) or null.  The second product reads y from the workgroup's LDS tile instead of HBM (403 MB at bs=128); y is still
+ * stored.  Same bits as the two sp_conv2d_fwd launches.  Neither output may alias an input or the other output. */
+int sp_pw_chain_f32_ok(int64_t rows, int c_mid, int c_out, int c_next);
+int sp_pw_chain_f32(const float* t, const float* w3_packed, const float* scale3, const float* shift3, const float* residual, float* y,
+                    const float* w1_packed, const float* scale1, const float* shift1, float* t_next, int64_t rows, int c_mid, int c_out, int c_next,
+                    void* stream);
 /* One ResNet Bottleneck (nets/pose_resnet_dconv.py:112-133) with an identity shortcut, stride 1, 256 -> 64 -> 64 -> 256 channels, in ONE
  * launch, bf16: y = relu(bn3(conv1x1(relu(bn2(conv3x3(relu(bn1(conv1x1(x)))))))) + x).  `desc` describes the block's 3x3 convolution
  * (sp_bottleneck_c64_ok(desc) == 1: what sp_conv3x3_direct_ok accepts at 64 channels); w1 [>=64][256], w2 [>=64][576], w3 [256][64]

@@ -296,6 +296,228 @@ __global__ __launch_bounds__(256, 1) void conv_pw_dual_kernel(const PwDualArgs p
     }
 }
 
+// ---- conv3 of an identity Bottleneck and the NEXT block's conv1 as ONE launch (round 7):
+//          y = relu( bn3(conv1x1(t)) + x ),   t_next = relu( bn1'(conv1x1(y)) ),   t [M][64], x / y [M][256], t_next [M][NEXT]   (nets/pose_resnet_dconv.py:112-133)
+// conv_pw_kernel already holds all 256 channels of 64 pixels in one workgroup's LDS (the four waves' transpose slices) on their way to HBM.  Here the
+// post-ReLU values are written back into those slices in place, and after a barrier a second GEMM (K = 256) takes its A fragments from them: the next
+// conv1 never reads y from HBM (403 MB at bs=128).  y is still stored: it is the next block's residual.
+//   * W1 lives in REGISTERS: every wave owns one 32-column tile of t_next over all of K (NEXT = 64: one 32-row tile of it, waves 2n / 2n + 1 share
+//     columns; NEXT = 128: both row tiles), i.e. 32 groups x 4 floats = 128 VGPRs per lane beside conv3's 64 - one wave per SIMD has 512.
+//   * the y tile keeps conv_pw_kernel's row stride TRS = 68 floats: a fragment read is 16 bytes of pixel `fr` at k = 8g + 4fh, slot (17 fr + c) mod 16
+//     = (fr + c) mod 16 of the 256-byte bank row, and each of ds_read_b128's 16-lane groups ({0-3,12-15,20-27}, {4-11,16-19,28-31}, + 32) covers
+//     every residue mod 16 exactly once: conflict-free.  Slice bases are multiples of 256 bytes.
+//   * the residual of tile t + 1 is requested BEFORE the chained GEMM of tile t (its registers are free after the epilogue), so loads are in flight
+//     behind both GEMMs; the stores of y drain behind the chained one.
+// Bits: conv3 exactly as conv_pw_kernel; the chained product is the tiled kernel's MFMA chain (per 8-k group g ascending, s = 0..3, the pair
+// (8g+s, 8g+4+s), one accumulator from 0) on the fp32 values that the two-launch program reads back, epilogue acc * scale + shift, relu.
+struct PwChainArgs {
+    const float* x;          // t [M][64]
+    const float* w;          // packed [256][64]
+    const float* scale;      // [256] or null
+    const float* shift;
+    const float* res;        // [M][256]
+    float* y;                // [M][256]
+    const float* w1;         // packed [NEXT][256]
+    const float* scale1;     // [NEXT] or null
+    const float* shift1;
+    float* t;                // [M][NEXT]
+    int M, tiles_m;
+    unsigned x_bytes, y_bytes, t_bytes;
+};
+
+constexpr int T2S = 36;      // row stride of the chained result's per-wave transpose (32 columns + 4)
+
+template <int K, int NEXT>
+__global__ __launch_bounds__(256, 1) void conv_pw_chain_kernel(const PwChainArgs p) {
+    static_assert(K == 64 && (NEXT == 64 || NEXT == 128), "conv3 of a 64-channel Bottleneck into a 64- or 128-channel conv1");
+    constexpr int N = 256;                        // conv3's outputs = the chained reduction
+    constexpr int CH = K / 4;
+    constexpr int NG = K / 8;
+    constexpr int NG1 = N / 8;                    // 8-k groups of the chained GEMM
+    constexpr int APT = BM * CH / 256;
+    constexpr int RT = NEXT / 64;                 // 32-row tiles of t_next per wave
+    extern __shared__ __align__(16) float smem[];
+    float* const As = smem;                       // [2][BM * K]
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    float* const ys = smem + 2 * BM * K;          // [4 channel slices][BM][TRS]: the y tile
+    float* const tr = ys + wave * (BM * TRS);
+    float* const t2 = ys + 4 * BM * TRS + wave * (RT * 32 * T2S);
+    const int fr = lane & 31, fh = lane >> 5;
+    const int slot = blockIdx.x, nslots = gridDim.x;
+    const int nbase = wave * 64;                  // this wave's 64 channels of y
+    const int cn = NEXT == 64 ? wave >> 1 : wave; // ... and its 32-column tile of t_next,
+    const int ri0 = NEXT == 64 ? wave & 1 : 0;    //     first 32-row tile
+
+    const __amdgpu_buffer_rsrc_t xr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.x), (short)0, p.x_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<float*>(p.res), (short)0, p.y_bytes, 0x00020000);
+    const __amdgpu_buffer_rsrc_t tnr = __builtin_amdgcn_make_buffer_rsrc(p.t, (short)0, p.t_bytes, 0x00020000);
+
+    float fb[NG][2][4];
+#pragma unroll
+    for (int g = 0; g < NG; ++g)
+#pragma unroll
+        for (int n = 0; n < 2; ++n) {
+            const f32x4 t = *reinterpret_cast<const f32x4*>(p.w + (size_t)(nbase + n * 32 + fr) * K + 8 * g + 4 * fh);
+            fb[g][n][0] = t[0]; fb[g][n][1] = t[1]; fb[g][n][2] = t[2]; fb[g][n][3] = t[3];
+        }
+    float fw[NG1][4];                             // W1[32 cn + fr][8g + 4fh + s]
+#pragma unroll
+    for (int g = 0; g < NG1; ++g) {
+        const f32x4 t = *reinterpret_cast<const f32x4*>(p.w1 + (size_t)(cn * 32 + fr) * N + 8 * g + 4 * fh);
+        fw[g][0] = t[0]; fw[g][1] = t[1]; fw[g][2] = t[2]; fw[g][3] = t[3];
+    }
+    const int c4 = (lane & 15) * 4, rsub = lane >> 4;
+    f32x4 sc4 = {1.f, 1.f, 1.f, 1.f}, sh4 = {0.f, 0.f, 0.f, 0.f};
+    if (p.scale) sc4 = *reinterpret_cast<const f32x4*>(p.scale + nbase + c4);
+    if (p.shift) sh4 = *reinterpret_cast<const f32x4*>(p.shift + nbase + c4);
+    const float s1v = p.scale1 ? p.scale1[cn * 32 + fr] : 1.f, h1v = p.shift1 ? p.shift1[cn * 32 + fr] : 0.f;   // accumulator layout: this lane's channel
+
+    auto swz = [](int row, int chunk) { return row * K + ((chunk ^ (row & (CH - 1))) << 2); };
+    u32x4 sa[APT];
+    auto load_a = [&](int mt) {
+        const unsigned base = (unsigned)mt * (BM * K * 4);
+#pragma unroll
+        for (int i = 0; i < APT; ++i) sa[i] = __builtin_amdgcn_raw_buffer_load_b128(xr, base + (unsigned)((tid + 256 * i) * 16), 0, 0);
+    };
+    auto park_a = [&](int buf) {
+#pragma unroll
+        for (int i = 0; i < APT; ++i) {
+            const int q = tid + 256 * i;
+            *reinterpret_cast<u32x4*>(As + buf * (BM * K) + swz(q / CH, q % CH)) = sa[i];
+        }
+    };
+    unsigned off[16];
+    u32x4 rv[16];
+    auto load_res = [&](int mt) {
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            const int row = mt * BM + it * 4 + rsub;
+            off[it] = row < p.M ? (unsigned)(((size_t)row * N + nbase + c4) * 4) : OOB;
+        }
+#pragma unroll
+        for (int it = 0; it < 16; ++it) rv[it] = __builtin_amdgcn_raw_buffer_load_b128(rr, off[it], 0, 0);
+    };
+
+    int mt = slot;
+    if (mt >= p.tiles_m) return;
+    load_a(mt);
+    park_a(0);
+    load_res(mt);
+    __syncthreads();
+    int cur = 0;
+    for (; mt < p.tiles_m; mt += nslots, cur ^= 1) {
+        const int m0 = mt * BM;
+        const bool more = mt + nslots < p.tiles_m;
+        if (more) load_a(mt + nslots);
+
+        f32x16 acc[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) acc[i][n][r] = 0.f;
+        const float* a = As + cur * (BM * K);
+        f32x4 fa[2][2];
+#pragma unroll
+        for (int i = 0; i < 2; ++i) fa[0][i] = *reinterpret_cast<const f32x4*>(a + swz(i * 32 + fr, fh));
+#pragma unroll
+        for (int g = 0; g < NG; ++g) {
+            if (g + 1 < NG) {
+#pragma unroll
+                for (int i = 0; i < 2; ++i) fa[(g + 1) & 1][i] = *reinterpret_cast<const f32x4*>(a + swz(i * 32 + fr, 2 * (g + 1) + fh));
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int i = 0; i < 2; ++i)
+#pragma unroll
+                    for (int n = 0; n < 2; ++n)
+                        acc[i][n] = __builtin_amdgcn_mfma_f32_32x32x2f32(fa[g & 1][i][s], fb[g][n][s], acc[i][n], 0, 0, 0);
+        }
+
+        // ---- conv3's epilogue (conv_pw_kernel's); what is stored also goes back into the LDS tile, in place ----
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int n = 0; n < 2; ++n)
+#pragma unroll
+                for (int r = 0; r < 16; ++r) tr[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * TRS + n * 32 + fr] = acc[i][n][r];
+#pragma unroll
+        for (int it = 0; it < 16; ++it) {
+            f32x4* const slot4 = reinterpret_cast<f32x4*>(tr + (it * 4 + rsub) * TRS + c4);
+            f32x4 v = *slot4;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] * sc4[e] + sh4[e];
+            const f32x4 r4 = __builtin_bit_cast(f32x4, rv[it]);
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] += r4[e];
+#pragma unroll
+            for (int e = 0; e < 4; ++e) v[e] = v[e] > 0.f ? v[e] : 0.f;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), yr, off[it], 0, 0);
+            *slot4 = v;
+        }
+        if (more) park_a(cur ^ 1);
+        __syncthreads();                          // the y tile is complete (and tile t + 1 of A is in LDS)
+        if (more) load_res(mt + nslots);          // in flight behind the chained GEMM and the next tile's conv3
+
+        // ---- chained GEMM: t_next[64 px][NEXT] = y tile . W1^T over K = 256, A fragments from the y tile ----
+        f32x16 c[RT];
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) c[i][r] = 0.f;
+        // k = 8g + 4fh: channel slice k >> 6 = g >> 3, column 8 (g & 7) + 4fh of it
+        auto yfrag = [&](int i, int g) { return *reinterpret_cast<const f32x4*>(ys + (g >> 3) * (BM * TRS) + ((ri0 + i) * 32 + fr) * TRS + 8 * (g & 7) + 4 * fh); };
+        f32x4 fy[2][RT];
+#pragma unroll
+        for (int i = 0; i < RT; ++i) fy[0][i] = yfrag(i, 0);
+#pragma unroll
+        for (int g = 0; g < NG1; ++g) {
+            if (g + 1 < NG1) {
+#pragma unroll
+                for (int i = 0; i < RT; ++i) fy[(g + 1) & 1][i] = yfrag(i, g + 1);
+            }
+#pragma unroll
+            for (int s = 0; s < 4; ++s)
+#pragma unroll
+                for (int i = 0; i < RT; ++i) c[i] = __builtin_amdgcn_mfma_f32_32x32x2f32(fy[g & 1][i][s], fw[g][s], c[i], 0, 0, 0);
+        }
+        // ---- its epilogue in the accumulator layout, a wave-private transpose, 16 bytes of one pixel per lane ----
+#pragma unroll
+        for (int i = 0; i < RT; ++i)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) {
+                float v = c[i][r] * s1v + h1v;
+                v = v > 0.f ? v : 0.f;
+                t2[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * T2S + fr] = v;
+            }
+#pragma unroll
+        for (int it = 0; it < RT * 4; ++it) {
+            const int lr = it * 8 + (lane >> 3), cc = (lane & 7) * 4;
+            const int row = m0 + ri0 * 32 + lr;
+            const unsigned o = row < p.M ? (unsigned)(((size_t)row * NEXT + cn * 32 + cc) * 4) : OOB;
+            const f32x4 v = *reinterpret_cast<const f32x4*>(t2 + lr * T2S + cc);
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, v), tnr, o, 0, 0);
+        }
+        __syncthreads();                          // every wave has left the y tile and buffer `cur`
+    }
+}
+
+template <int NEXT>
+int launch_pw_chain(const PwChainArgs& a, hipStream_t stream) {
+    constexpr int lds = (2 * BM * 64 + 4 * BM * TRS + 4 * (NEXT / 64) * 32 * T2S) * 4;
+    if (sp_reserve_lds<&conv_pw_chain_kernel<64, NEXT>>(lds, "conv_pw_chain")) return SP_ELAUNCH;
+    int slots = sp_device_cus();
+    if (slots < 1) slots = 1;
+    if (slots > a.tiles_m) slots = a.tiles_m;
+    const int rounds = (a.tiles_m + slots - 1) / slots;
+    slots = (a.tiles_m + rounds - 1) / rounds;
+    hipLaunchKernelGGL((conv_pw_chain_kernel<64, NEXT>), dim3(slots), dim3(256), lds, stream, a);
+    return sp_check_launch("conv_pw_chain_kernel");
+}
+
 template <int K>
 int launch_pw_dual(const PwDualArgs& a, hipStream_t stream) {
     constexpr int lds = (4 * BM * K + 4 * BM * TRS) * 4;
@@ -375,4 +597,26 @@ extern "C" int sp_dual_pw_f32(const float* a_main, const float* w_main_packed, c
     a.M = (int)rows; a.N = c_out; a.nchunks = c_out / 256; a.tiles_m = (int)((rows + BM - 1) / BM); a.relu = relu ? 1 : 0;
     a.x_bytes = (unsigned)(rows * 64 * 4); a.y_bytes = (unsigned)(rows * c_out * 4);
     return launch_pw_dual<64>(a, (hipStream_t)stream);
+}
+
+// conv3 (+ bn3 + residual + relu) of an identity Bottleneck with 64 mid channels and the next block's conv1 (+ bn1 + relu) as one launch
+extern "C" int sp_pw_chain_f32_ok(int64_t rows, int c_mid, int c_out, int c_next) {
+    return rows > 0 && rows * (int64_t)c_out <= (1ll << 29) && c_mid == 64 && c_out == 256 && (c_next == 64 || c_next == 128);
+}
+
+extern "C" int sp_pw_chain_f32(const float* t, const float* w3_packed, const float* scale3, const float* shift3, const float* residual, float* y,
+                               const float* w1_packed, const float* scale1, const float* shift1, float* t_next, int64_t rows, int c_mid, int c_out,
+                               int c_next, void* stream) {
+    SP_REQUIRE(t && w3_packed && residual && y && w1_packed && t_next, "sp_pw_chain_f32: null pointer");
+    SP_REQUIRE(sp_pw_chain_f32_ok(rows, c_mid, c_out, c_next),
+               "sp_pw_chain_f32: an fp32 1x1 product 64 -> 256 chained into a 1x1 product 256 -> 64 or 128 (got %d -> %d -> %d, %lld rows)", c_mid, c_out,
+               c_next, (long long)rows);
+    SP_REQUIRE(y != t && y != residual && t_next != t && t_next != residual && t_next != y, "sp_pw_chain_f32: y and t_next must not alias an input or each other");
+    if (sp_name_query_active()) { sp_name_query_set("conv_pw_chain_kernel<64, %d>", c_next); return SP_OK; }
+    PwChainArgs a;
+    a.x = t; a.w = w3_packed; a.scale = scale3; a.shift = shift3; a.res = residual; a.y = y;
+    a.w1 = w1_packed; a.scale1 = scale1; a.shift1 = shift1; a.t = t_next;
+    a.M = (int)rows; a.tiles_m = (int)((rows + BM - 1) / BM);
+    a.x_bytes = (unsigned)(rows * 64 * 4); a.y_bytes = (unsigned)(rows * 256 * 4); a.t_bytes = (unsigned)(rows * c_next * 4);
+    return c_next == 64 ? launch_pw_chain<64>(a, (hipStream_t)stream) : launch_pw_chain<128>(a, (hipStream_t)stream);
 }

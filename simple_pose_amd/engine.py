@@ -95,7 +95,7 @@ class HipPacker:
 # ------------------------------------------------------------------------------------------------
 @dataclass
 class Op:
-    kind: str                    # "conv" | "bb32" / "bb64" (fused BasicBlock, 32 / 64 channels) | "bneck64" (fused Bottleneck) | "stem7" / "hstem" (fused ResNet / HRNet stem) | "htrans" (HRNet transition1) | "maxpool" | ...
+    kind: str                    # "conv" | "bb32" / "bb64" (fused BasicBlock, 32 / 64 channels) | "bneck64" (fused Bottleneck) | "dual1x1" / "pwchain" (fused 1x1 pairs) | "stem7" / "hstem" (fused ResNet / HRNet stem) | "htrans" (HRNet transition1) | "maxpool" | ...
     src: str
     dst: str
     res: Optional[str] = None
@@ -108,7 +108,7 @@ class Op:
     name: str = ""
     lane: int = 0                # HIP stream the op is issued on (0 = the caller's stream); independent branches get their own
     direct: bool = False         # conv: use sp_conv3x3_direct (bf16 3x3, 32 -> 32 channels) instead of the implicit GEMM; same bits
-    dst2: Optional[str] = None   # second output ("htrans": HRNet's transition1 writes the high- and the half-resolution branch in one launch)
+    dst2: Optional[str] = None   # second output ("htrans": HRNet's transition1 writes the high- and the half-resolution branch in one launch; "pwchain": the next block's conv1 output)
     c0: int = 0                  # conv with SP_CONV_OUT_SLICE: first channel of `dst` this launch writes (a producer of a concat buffer)
 
     def writes(self) -> Tuple[str, ...]:
@@ -249,6 +249,10 @@ class Program:
             fn = lib.sp_dual_pw_bf16 if op.w.element_size() == 2 else lib.sp_dual_pw_f32
             _lib.check(fn(P(bufs[op.src]), P(op.w), P(op.scale), P(op.shift), P(bufs[op.res]), P(w_s), P(s_s), P(h_s), P(bufs[op.dst]),
                                            B * rows_per_image, 64, 64, 256, relu, stream), op.name)
+        elif op.kind == "pwchain":
+            w1, s1, h1, rows_per_image, c_next, _ = op.args
+            _lib.check(lib.sp_pw_chain_f32(P(bufs[op.src]), P(op.w), P(op.scale), P(op.shift), P(bufs[op.res]), P(bufs[op.dst]), P(w1), P(s1), P(h1),
+                                           P(bufs[op.dst2]), B * rows_per_image, 64, 256, c_next, stream), op.name)
         elif op.kind == "stem7":
             h, w, k_pad, unfused = op.args
             src = bufs[op.src]
@@ -807,6 +811,9 @@ class ProgramBuilder:
         # bf16: conv3 + the projection shortcut of a stage-opening Bottleneck with 64 mid channels (layer1.0 of the ResNets and of HRNet) as one
         # launch (sp_dual_pw_bf16: same bits, the 256-channel shortcut tensor is neither written nor read: 703 -> 301 MB at bs=128)
         self.fuse_tail = os.environ.get("SP_FUSE_TAIL", "1") != "0"       # (env: development knob for same-box A/Bs)
+        # fp32: conv3 of an identity Bottleneck with 64 mid channels + the next block's conv1 as one launch (sp_pw_chain_f32: same bits, conv1 reads the
+        # 256-channel tensor from the producer's LDS tile instead of HBM: 403 MB per pair at bs=128).  resnet_program(fuse_chain=True) asks for it
+        self.fuse_chain = os.environ.get("SP_FUSE_CHAIN", "1") != "0"     # (env: development knob for same-box A/Bs)
         # the ResNet stem (conv1 7x7 s2 + bn1 + relu + maxpool) as one launch on the fp32 NCHW image (sp_stem7_pool: same bits, the
         # 128 x 96 x 64 map between conv and pooling never reaches HBM, K is not padded to a GEMM tile)
         self.fuse_stem = True
@@ -1135,10 +1142,50 @@ def _res_basic_block(b: ProgramBuilder, sd, x: str, p: str, stride: int) -> str:
     return b.conv(t, sd[p + ".conv2.weight"], pad=1, scale=s2, shift=h2, relu=True, res=idn, name=p + ".conv2")
 
 
+def _plain_pointwise(d) -> bool:
+    """A dense 1x1 stride-1 NHWC launch whose output grid is its input grid (what sp_conv2d_pw_ok asks of the geometry)."""
+    return (d.c_in_group == 0 and d.taps_h == 1 and d.taps_w == 1 and d.stride == 1 and d.stride_x in (0, 1) and d.phases_y == 1 and d.phases_x == 1 and
+            d.dy0 == 0 and d.dx0 == 0 and (d.grid_h, d.grid_w) == (d.in_h, d.in_w) == (d.out_h, d.out_w) and d.oy_mul == 1 and d.ox_mul == 1 and
+            d.oy_add == 0 and d.ox_add == 0 and d.k_pad == d.c_in and d.n_pad == d.c_out and d.out_c == d.c_out)
+
+
+def _fuse_pw_chains(b: "ProgramBuilder", sd) -> None:
+    """fp32: every `<block>.conv3` (+ bn3 + identity residual + relu) of a Bottleneck with 64 mid channels that is directly followed by the next
+    block's 1x1 stride-1 `conv1` (+ bn1 + relu, 64 or 128 outputs) on its result becomes one `pwchain` op (sp_pw_chain_f32) named
+    `<producer>+<consumer>`.  The producer must be an identity block's plain conv3: a stage-opening block's tail is a `dual1x1` op or a conv
+    depending on `fuse_tail`, and the per-conv program must lose the same ops.  The two conv ops stay inside the op as its definition."""
+    if b.bf16 or not b.fuse_chain:
+        return
+    ops, out, i = b.p.ops, [], 0
+    while i < len(ops):
+        a, c = ops[i], ops[i + 1] if i + 1 < len(ops) else None
+        ok = (c is not None and a.kind == "conv" and c.kind == "conv" and a.lane == c.lane and a.name.endswith(".conv3") and c.name.endswith(".conv1") and
+              a.res is not None and c.res is None and c.src == a.dst and not a.direct and not c.direct and a.c0 == 0 and c.c0 == 0 and
+              a.scale is not None and a.shift is not None and c.scale is not None and c.shift is not None)
+        if ok:
+            blk, da, dc = a.name[:-len(".conv3")], a.desc, c.desc
+            ok = ((blk + ".downsample.0.weight") not in sd and (blk + ".se.fc.0.weight") not in sd and _plain_pointwise(da) and _plain_pointwise(dc) and
+                  da.flags == SP_CONV_RELU and dc.flags == SP_CONV_RELU and da.c_in == 64 and da.c_out == 256 and dc.c_in == 256 and
+                  dc.c_out in (64, 128) and tuple(a.w.shape) == (256, 64) and tuple(c.w.shape) == (dc.c_out, 256) and
+                  _lib.lib().sp_pw_chain_f32_ok(da.grid_h * da.grid_w, 64, 256, dc.c_out))
+        if ok:
+            out.append(Op("pwchain", a.src, a.dst, res=a.res, dst2=c.dst, w=a.w, scale=a.scale, shift=a.shift,
+                          args=(c.w, c.scale, c.shift, da.grid_h * da.grid_w, dc.c_out, (a, c)), name=a.name + "+" + c.name, flops=a.flops + c.flops,
+                          lane=a.lane))
+            i += 2
+        else:
+            out.append(a)
+            i += 1
+    b.p.ops[:] = out
+
+
 def resnet_program(sd: Dict[str, torch.Tensor], head: str, in_h: int = 256, in_w: int = 192,
-                   blocks=(3, 4, 6, 3), dtype: str = "fp32", packer=None, fuse_bottlenecks: bool = False, fuse_stem: bool = True) -> Program:
+                   blocks=(3, 4, 6, 3), dtype: str = "fp32", packer=None, fuse_bottlenecks: bool = False, fuse_stem: bool = True,
+                   fuse_chain: bool = False) -> Program:
     """Lower a reference-layout state_dict into a Program.  `sd` tensors must be on the GPU.
-    `fuse_bottlenecks`: bf16 identity-shortcut Bottlenecks with 64 mid channels as one launch each (sp_bottleneck_c64; same bits)."""
+    `fuse_bottlenecks`: bf16 identity-shortcut Bottlenecks with 64 mid channels as one launch each (sp_bottleneck_c64; same bits).
+    `fuse_chain`: fp32 - an identity Bottleneck's conv3 and the next block's conv1 as one launch (sp_pw_chain_f32; same bits).  Independent of
+    `fuse_bottlenecks`; off by default here (the models turn it on: PoseResNetBase.fuse_chain)."""
     b = ProgramBuilder(in_h, in_w, dtype, packer)
     b.fuse_bottlenecks = fuse_bottlenecks
     b.fuse_tail = fuse_bottlenecks and b.fuse_tail      # (one switch for the Bottleneck fusions of the ResNet programs: the per-conv program is the bitwise reference)
@@ -1149,6 +1196,8 @@ def resnet_program(sd: Dict[str, torch.Tensor], head: str, in_h: int = 256, in_w
     for li, n in enumerate(blocks, start=1):
         for bi in range(n):
             x = (_res_basic_block if basic else _bottleneck)(b, sd, x, f"layer{li}.{bi}", 2 if (bi == 0 and li > 1) else 1)
+    if fuse_chain and not basic:
+        _fuse_pw_chains(b, sd)
     J = sd["final_layer.weight"].shape[0]
     if head == "dconv":
         for idx in (0, 3, 6):

@@ -124,10 +124,11 @@ class PoseResNetBase(nn.Module):
     # -- HIP dispatch ------------------------------------------------------------------------------------
     fuse_bottlenecks = True    # bf16: layer1.1 / layer1.2 as one launch each (sp_bottleneck_c64); same bits, +0.6 ... 0.8 % end to end
     fuse_stem = True           # conv1 + bn1 + relu + maxpool as one launch on the fp32 NCHW image (sp_stem7_pool); same bits
+    fuse_chain = True          # fp32: conv3 of layer1.1 / layer1.2 + the next block's conv1 as one launch each (sp_pw_chain_f32); same bits
 
     def _tensors_key(self, x):
         sd = self.state_dict(keep_vars=True)
-        return (tuple(x.shape[2:]), str(x.device), self.compute_dtype, self.fuse_bottlenecks, self.fuse_stem) + tuple((v.data_ptr(), v._version) for v in sd.values())
+        return (tuple(x.shape[2:]), str(x.device), self.compute_dtype, self.fuse_bottlenecks, self.fuse_stem, self.fuse_chain) + tuple((v.data_ptr(), v._version) for v in sd.values())
 
     def hip_program(self, x: torch.Tensor) -> engine.Program:
         key = self._tensors_key(x)
@@ -137,7 +138,8 @@ class PoseResNetBase(nn.Module):
                 if v.device != x.device:
                     raise HipLibraryError(f"parameter {k} is on {v.device} but the input is on {x.device}; call .to(device)")
             self._program = engine.resnet_program(sd, self.HEAD, in_h=x.shape[2], in_w=x.shape[3], blocks=self.BLOCKS,
-                                                   dtype=self.compute_dtype, fuse_bottlenecks=self.fuse_bottlenecks, fuse_stem=self.fuse_stem)
+                                                   dtype=self.compute_dtype, fuse_bottlenecks=self.fuse_bottlenecks, fuse_stem=self.fuse_stem,
+                                                   fuse_chain=self.fuse_chain)
             self._program_key = key
         return self._program
 
