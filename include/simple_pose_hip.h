@@ -115,6 +115,15 @@ int sp_nchw_to_nhwc4(const float* x_nchw, float* y_nhwc4, int batch, int channel
 int sp_conv2d_fwd(const sp_conv_desc* desc, const void* x, const void* w_packed, const float* scale,
                   const float* shift, const void* residual, void* y, void* stream);
 
+/* Tap skipping (an addition to ABI 36).  An fp32 inference launch of sp_conv2d_fwd on the implicit-GEMM kernel with more than one tap, whole
+ * K tiles per tap (c_in % 32 == 0), no groups, an NHWC store without pixel shuffle and batch >= tile_m / 2 orders its rows (output position,
+ * image) and does not multiply the K tiles whose tap lies outside the image for every row of a tile (conv_igemm_tapskip_kernel).  Same bits
+ * as the full K loop under one PRECONDITION: the packed weights are finite (a skipped product was +-0 * w; an inf / NaN weight made it NaN).
+ * Activations may hold inf / NaN: an in-image value is never skipped.  sp_conv_set_tap_skip(0) restores the (image, position) row order and
+ * the full K loop for every later launch of the process, sp_conv_set_tap_skip(1) turns the path back on; the environment variable
+ * SP_CONV_TAP_SKIP=0 is the same switch read once, at the first launch.  Default: on. */
+int sp_conv_set_tap_skip(int on);
+
 /* Direct (non-im2col) 3x3 stride-1 pad-1 convolution for 32 -> 32 and 64 -> 64 channels in bf16 (HRNet's two high-resolution branches,
  * nets/pose_hrnet.py BasicBlock; ResNet-50 layer1.*.conv2): the halo tile of an 8x16 / 16x8 output tile goes through LDS once instead of
  * once per tap; the filter stays in registers (32 channels) or in LDS in MFMA-fragment order (64 channels) for a persistent workgroup.  Same arguments and bit-identical results as sp_conv2d_fwd for

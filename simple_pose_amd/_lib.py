@@ -86,6 +86,7 @@ SYMBOLS = {
     "sp_last_error": (ctypes.c_char_p, []),
     "sp_nchw_to_nhwc4": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "sp_conv2d_fwd": (c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
+    "sp_conv_set_tap_skip": (c_int, [c_int]),
     "sp_conv2d_ring_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
     "sp_conv2d_kernel_name": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, ctypes.c_char_p, c_int]),
     "sp_conv2d_default_tile": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),

@@ -111,3 +111,61 @@ def conv_dgrad_s2(h: int, w: int, oh: int, ow: int, c_dy: int, c_in: int, n_pad:
     """The launch of one `stride2_dgrad_phases` phase: dy [oh, ow, c_dy] -> pixels (2g + py, 2g + px) of dx [h, w, c_in]."""
     py, px, _, _, th, tw, dy0, dx0 = phase
     return _desc((oh, ow, c_dy), (h // 2, w // 2), c_in, n_pad, (th, tw), k_pad, 1, (dy0, dx0), -1, (h, w, c_in), (2, py, 2, px), flags=flags, panel=panel)
+
+
+def _full_range(grid: int, size: int, stride: int, d0: int, taps: int, step: int) -> Tuple[int, int]:
+    """Grid points [lo, hi) of one axis whose every tap lies inside the image (the kernel's own arithmetic, conv_igemm.hip)."""
+    far = (taps - 1) * step
+    a, b = -(d0 + min(far, 0)), size - 1 - d0 - max(far, 0)
+    lo = 0 if a <= 0 else (a + stride - 1) // stride
+    hi = min(0 if b < 0 else b // stride + 1, grid)
+    return min(lo, hi), hi
+
+
+def tap_skip_positions(d: ConvDesc, py: int = 0, px: int = 0) -> list:
+    """Output positions (gy, gx) of phase (py, px) in the order the tap-skipping kernel hands them out: every tap inside the image on both axes
+    first, then partial on x only, partial on y only, partial on both (interior, edges, corners of a padded 3x3)."""
+    ylo, yhi = _full_range(d.grid_h, d.in_h, d.stride, d.dy0 + py, d.taps_h, d.dy_step)
+    xlo, xhi = _full_range(d.grid_w, d.in_w, d.stride_x or d.stride, d.dx0 + px, d.taps_w, d.dx_step)
+    fy, fx = list(range(ylo, yhi)), list(range(xlo, xhi))
+    qy = [g for g in range(d.grid_h) if not ylo <= g < yhi]
+    qx = [g for g in range(d.grid_w) if not xlo <= g < xhi]
+    return [(gy, gx) for ys, xs in ((fy, fx), (fy, qx), (qy, fx), (qy, qx)) for gy in ys for gx in xs]
+
+
+def tap_mask(d: ConvDesc, gy: int, gx: int, py: int = 0, px: int = 0) -> int:
+    """Bit (ty * taps_w + tx) set when that tap of output position (gy, gx) reads inside the image."""
+    m = 0
+    for ty in range(d.taps_h):
+        for tx in range(d.taps_w):
+            iy = gy * d.stride + d.dy0 + py + ty * d.dy_step
+            ix = gx * (d.stride_x or d.stride) + d.dx0 + px + tx * d.dx_step
+            if 0 <= iy < d.in_h and 0 <= ix < d.in_w:
+                m |= 1 << (ty * d.taps_w + tx)
+    return m
+
+
+def tap_skip_k_tiles(d: ConvDesc, batch: int, tile_m: int, k_tile: int = 32) -> Tuple[int, int]:
+    """K tiles one column of N tiles executes over the whole launch (every phase, every M tile): (with tap skipping, without).
+    With skipping, rows are ordered (position in `tap_skip_positions` order, image) and a tile of `tile_m` rows runs the K tiles of the taps
+    that lie inside the image for at least one of its rows, `c_in / k_tile` per tap.  A launch the kernel's launcher would not take
+    (one tap, batch < tile_m / 2, c_in not in whole K tiles) executes everything: both counts are equal.  The launcher's other conditions
+    (fp32 inference, NHWC store, no groups) are the caller's to know."""
+    taps = d.taps_h * d.taps_w
+    M = batch * d.grid_h * d.grid_w
+    tiles_m = (M + tile_m - 1) // tile_m
+    phases = d.phases_y * d.phases_x
+    full = phases * tiles_m * (d.k_pad // k_tile)
+    if taps <= 1 or taps > 32 or 2 * batch < tile_m or d.c_in % k_tile or d.k_pad != taps * d.c_in:
+        return full, full
+    per_tap, done = d.c_in // k_tile, 0
+    for ph in range(phases):
+        py, px = ph // d.phases_x, ph % d.phases_x
+        masks = [tap_mask(d, gy, gx, py, px) for gy, gx in tap_skip_positions(d, py, px)]
+        for t in range(tiles_m):
+            first, last = t * tile_m // batch, (min((t + 1) * tile_m, M) - 1) // batch
+            union = 0
+            for i in range(first, last + 1):
+                union |= masks[i]
+            done += max(bin(union).count("1"), 1) * per_tap
+    return done, full

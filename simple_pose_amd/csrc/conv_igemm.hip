@@ -114,6 +114,8 @@ struct ConvArgs {
     const float* abn_beta;
     void* abn_y;                 // NHWC bf16, layout of x
     unsigned char* abn_mask;     // one byte per 8 channels of abn_y (null: no mask)
+    // SKIP instantiation (conv_igemm_tapskip_kernel): images of the launch = M / (grid_h * grid_w); rows are ordered (position, image)
+    int batch;
 };
 
 constexpr int BK = 32;  // floats per K tile (8 chunks of 16 B)
@@ -134,9 +136,16 @@ __device__ __forceinline__ float abn_elem(float v, float mu, float is, float g, 
     return (v - mu) * is * g + b;
 }
 
-template <int BM, int BN, int WR, int WC, bool UNIFORM_TAP, bool BF16, bool OUT16, bool STATS, bool DEEP, bool BSTATS, bool ABN>
+// SKIP (conv_igemm_tapskip_kernel; the fp32 inference launches of multi-tap convolutions the launcher finds eligible): rows are ordered
+// m = (position, image) instead of (image, position), so a tile of BM rows is BM images of ONE output position (two when the batch is not a
+// multiple of BM) and all its rows share one tap mask.  The K loop then walks only the K tiles of taps that lie inside the image for some row
+// of the tile, in ascending k: a skipped tile only ever added fma(+-0, w, acc) terms (the out-of-image load returns +0), which leave every bit
+// of an accumulator that started at +0 unchanged as long as w is finite - the precondition of the path.  Tiles differ in length (9 / 6 / 4 of
+// 9 taps), so positions are handed out longest first: interior before edges before corners, dealt round-robin over the eight XCD chunks.
+template <int BM, int BN, int WR, int WC, bool UNIFORM_TAP, bool BF16, bool OUT16, bool STATS, bool DEEP, bool BSTATS, bool ABN, bool SKIP = false>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     static_assert(!ABN || (UNIFORM_TAP && BF16 && OUT16 && STATS && !DEEP && !BSTATS), "ABN: the bf16 train-mode forward of a 1x1 conv");
+    static_assert(!SKIP || (UNIFORM_TAP && !BF16 && !OUT16 && !STATS && !DEEP && !BSTATS && !ABN), "SKIP: the plain fp32 inference instantiation");
     constexpr int ES = BF16 ? 2 : 4;     // element size of activations / weights
     constexpr int EPC = 16 / ES;         // elements per 16-byte chunk
     constexpr int BKE = 128 / ES;        // elements per K tile (one 128-byte LDS row)
@@ -174,7 +183,18 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
         t = (xcd < r ? xcd * (q + 1) : r * (q + 1) + (xcd - r) * q) + (orig >> 3);
     }
     const int tn = t % p.tiles_n, tm = t / p.tiles_n;
-    const int m0 = tm * BM, n0 = tn * BN;
+    int tm_rows = tm;
+    if constexpr (SKIP) {
+        // XCD x owns the M tiles of chunk x and starts them in ascending order, so the i-th tile of chunk x takes rank 8 i + x of the
+        // longest-first row order: every XCD gets the same mix of interior / edge / corner tiles and starts its longest ones first.
+        // (a bijection on [0, tiles_m): chunks 0 .. R-1 hold Q + 1 tiles, the others Q)
+        const int Q = p.tiles_m >> 3, R = p.tiles_m & 7;
+        int x, i;
+        if (tm < R * (Q + 1)) { x = tm / (Q + 1); i = tm - x * (Q + 1); }
+        else { const int u = tm - R * (Q + 1); x = u / Q; i = u - x * Q; x += R; }
+        tm_rows = i * 8 + x;
+    }
+    const int m0 = tm_rows * BM, n0 = tn * BN;
 
     // ---- phase (transposed conv) ----
     const int phase = blockIdx.y;
@@ -195,13 +215,41 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     //   x: byte offset of tap (0,0), channel 0 of this output pixel's receptive field (only used through valid taps)
     //   y: UNIFORM_TAP: bit (ty*taps_w + tx) set when that tap lies inside the image (taps <= 32, host-checked)
     //   z: (iy0 << 16) | (ix0 & 0xffff)  (generic path)      w: output element offset of the pixel, -1 = row >= M
+    // SKIP: per axis, the grid points [lo, hi) whose every tap lies inside the image ("full"); the others are "partial" (wave-uniform)
+    int sk_ylo = 0, sk_yhi = 0, sk_xlo = 0, sk_xhi = 0;
+    if constexpr (SKIP) {
+        auto full_range = [](int grid, int in, int stride, int d0, int taps, int step, int& lo, int& hi) {
+            const int far = (taps - 1) * step, mn = far < 0 ? far : 0, mx = far > 0 ? far : 0;
+            const int a = -(d0 + mn), b = in - 1 - d0 - mx;          // g * stride >= a  and  g * stride <= b
+            lo = a <= 0 ? 0 : (a + stride - 1) / stride;
+            hi = b < 0 ? 0 : b / stride + 1;
+            hi = hi < grid ? hi : grid;
+            lo = lo < hi ? lo : hi;
+        };
+        full_range(p.grid_h, p.in_h, p.stride, dy0, taps_h, p.dy_step, sk_ylo, sk_yhi);
+        full_range(p.grid_w, p.in_w, p.stride_x, dx0, taps_w, p.dx_step, sk_xlo, sk_xhi);
+    }
     if (tid < BM) {
         const int m = m0 + tid;
         int4 e;
         if (m < p.M) {
             const int gw = p.grid_w, ghw = p.grid_h * gw;
-            const int b = m / ghw, rem = m - b * ghw;
-            const int gy = rem / gw, gx = rem - gy * gw;
+            int b, gy, gx;
+            if constexpr (SKIP) {
+                // m = (position rank, image); rank -> (gy, gx): full x full, then full-y x partial-x, partial-y x full-x, partial x partial
+                int idx = m / p.batch;
+                b = m - idx * p.batch;
+                const int fy = sk_yhi - sk_ylo, fx = sk_xhi - sk_xlo, qy = p.grid_h - fy, qx = gw - fx;
+                auto part = [](int j, int lo, int hi) { return j < lo ? j : j - lo + hi; };   // j-th partial grid point of an axis
+                if (idx < fy * fx) { gy = sk_ylo + idx / fx; gx = sk_xlo + idx % fx; }
+                else if ((idx -= fy * fx) < fy * qx) { gy = sk_ylo + idx / qx; gx = part(idx % qx, sk_xlo, sk_xhi); }
+                else if ((idx -= fy * qx) < qy * fx) { gy = part(idx / fx, sk_ylo, sk_yhi); gx = sk_xlo + idx % fx; }
+                else { idx -= qy * fx; gy = part(idx / qx, sk_ylo, sk_yhi); gx = part(idx % qx, sk_xlo, sk_xhi); }
+            } else {
+                b = m / ghw;
+                const int rem = m - b * ghw;
+                gy = rem / gw; gx = rem - gy * gw;
+            }
             const int iy0 = gy * p.stride + dy0, ix0 = gx * p.stride_x + dx0;
             e.x = ((b * p.in_h + iy0) * p.in_w + ix0) * p.c_in * ES;
             unsigned msk = 0;
@@ -269,7 +317,29 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     int t_shift = 0, t_ddy = 0, t_ddx = 0, t_coff = 0, t_k0 = 0;
     unsigned t_bit = 0;
     bool t_ok = true;
+    // SKIP: the taps still to walk (bit = tap, wave-uniform: the union of the tile's row masks) and the K tile inside the current tap
+    unsigned sk_rem = 0;
+    int sk_sub = 0;
+    const int sk_cpt = p.c_in / BKE;                           // K tiles per tap
+    if constexpr (SKIP) {
+        unsigned u = 0;
+        for (int r = lane; r < BM; r += 64) u |= (unsigned)rowtab[r * 4 + 1];      // rows >= M carry an empty mask
+#pragma unroll
+        for (int o = 32; o; o >>= 1) u |= (unsigned)__shfl_xor((int)u, o, 64);
+        sk_rem = (unsigned)__builtin_amdgcn_readfirstlane((int)u);
+        if (!sk_rem) sk_rem = 1u;                              // (no real geometry: a tile without any valid tap still runs one K tile of zeros)
+    }
     auto tile_taps = [&](int kt) {
+        if constexpr (SKIP) {                                  // called once per executed K tile, in order: `kt` counts compacted tiles
+            if (sk_sub == sk_cpt) { sk_sub = 0; sk_rem &= sk_rem - 1; }
+            const int tap = __builtin_ctz(sk_rem);
+            const int ty = tap / taps_w, tx = tap - ty * taps_w;
+            t_k0 = tap * p.c_in + sk_sub * BKE;
+            t_bit = 1u << tap;
+            t_shift = ((ty * p.dy_step * p.in_w + tx * p.dx_step) * p.c_in + sk_sub * BKE) * ES;
+            ++sk_sub;
+            return;
+        }
         const int k0 = kt * BKE;
         t_k0 = k0;
         if (UNIFORM_TAP) {  // c_in % 32 == 0: the whole K tile sits inside one tap (all scalar)
@@ -346,7 +416,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
             for (int r = 0; r < 16; ++r) acc[i][n][r] = 0.f;
 
     const int fr = lane & 31, fh = lane >> 5;
-    const int nk = k_pad / BKE;
+    const int nk = SKIP ? __builtin_popcount(sk_rem) * sk_cpt : k_pad / BKE;    // SKIP: the compacted count (>= 1)
 
     // Fragment registers are double-buffered by hand (slot = k-step parity): the ds_reads of k-step j+1 are issued
     // before the MFMAs of k-step j, so LDS latency hides behind ~1000 cycles of matrix work.
@@ -897,6 +967,12 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void conv_igemm
     conv_igemm_body<BM, BN, WR, WC, true, true, true, true, false, false, true>(p);
 }
 
+// the same body with rows grouped by output position and all-padding K tiles skipped (fp32 inference; again a kernel of its own name)
+template <int BM, int BN, int WR, int WC>
+__global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void conv_igemm_tapskip_kernel(const ConvArgs p) {
+    conv_igemm_body<BM, BN, WR, WC, true, false, false, false, false, false, false, true>(p);
+}
+
 template <int BM, int BN, int WR, int WC, bool BF16, bool OUT16, bool STATS, bool DEEP = false, bool BSTATS = false>
 int launch_t(const ConvArgs& a, int phases, bool uniform, hipStream_t stream) {
     if constexpr (!DEEP && BF16) {
@@ -957,7 +1033,25 @@ int launch_abn(const ConvArgs& a, hipStream_t stream) {
 }
 
 template <int BM, int BN, int WR, int WC>
-int launch(const ConvArgs& a, int phases, bool uniform, hipStream_t stream) {
+int launch_tapskip(const ConvArgs& a, int phases, hipStream_t stream) {
+    if (sp_name_query_active()) {
+        sp_name_query_set("conv_igemm_tapskip_kernel<%d, %d, %d, %d>", BM, BN, WR, WC);
+        return SP_OK;
+    }
+    ConvArgs p = a;
+    p.tiles_m = (a.M + BM - 1) / BM;
+    p.tiles_n = a.n_pad / BN;
+    const size_t lds = (size_t)2 * (BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int);
+    if (sp_reserve_lds<&conv_igemm_tapskip_kernel<BM, BN, WR, WC>>((int)lds, "conv_igemm_tapskip")) return SP_ELAUNCH;
+    hipLaunchKernelGGL((conv_igemm_tapskip_kernel<BM, BN, WR, WC>), dim3(p.tiles_m * p.tiles_n, phases, 1), dim3(256, 1, 1), lds, stream, p);
+    return sp_check_launch("conv_igemm_tapskip_kernel");
+}
+
+// tap_skip: the launch passed every tile-independent test of conv_fwd_impl (see there); what is left is the tile's own: at least half a
+// tile of images per output position, so that a tile spans at most three positions
+template <int BM, int BN, int WR, int WC>
+int launch(const ConvArgs& a, int phases, bool uniform, bool tap_skip, hipStream_t stream) {
+    if (tap_skip && a.batch >= BM / 2) return launch_tapskip<BM, BN, WR, WC>(a, phases, stream);
     if (a.abn_mean) return launch_abn<BM, BN, WR, WC>(a, stream);
     if (a.bz) {                                        // dgrad launch that also reduces the BN backward sums of the tensor it writes
         if ((a.flags & SP_CONV_BF16) && !(a.flags & SP_CONV_OUT_F32)) return launch_t<BM, BN, WR, WC, true, true, false, false, true>(a, phases, uniform, stream);
@@ -984,6 +1078,17 @@ int sp_conv_pw_launch(const sp_conv_desc* d, const void* x, const void* w_packed
                       const void* residual, void* y, void* stream);     // conv_pw.hip
 
 static int tile_rows_per_block(int, int) { return 1; }   // partial rows per (phase, M tile): the wave rows are added inside the launch
+
+// SP_CONV_TAP_SKIP=0 (or sp_conv_set_tap_skip(0)): every launch takes the (image, position) row order and the full K loop - same-box A/Bs
+static int g_tap_skip = -1;                              // -1: not decided yet (the environment is read at the first launch)
+static bool tap_skip_enabled() {
+    if (g_tap_skip < 0) { const char* e = getenv("SP_CONV_TAP_SKIP"); g_tap_skip = (e && atoi(e) == 0) ? 0 : 1; }
+    return g_tap_skip != 0;
+}
+extern "C" int sp_conv_set_tap_skip(int on) {
+    g_tap_skip = on ? 1 : 0;
+    return SP_OK;
+}
 
 struct BnBwdSrc { const void* y; const void* z; const float* mean; const float* invstd; const void* z2; const float* mean2; const float* invstd2; float* q2;
                   const void* res_mask = nullptr; };
@@ -1084,6 +1189,13 @@ static int conv_fwd_impl(const sp_conv_desc* d, const void* x, const void* w_pac
     a.bz2 = bsrc ? bsrc->z2 : nullptr; a.bmean2 = bsrc ? bsrc->mean2 : nullptr; a.binvstd2 = bsrc ? bsrc->invstd2 : nullptr; a.stats_q2 = bsrc ? bsrc->q2 : nullptr;
     a.bz_bytes = (int)(out_elems * es);
     a.c_in_g = d->c_in_group > 0 ? d->c_in_group : 0;
+    a.batch = d->batch;
+    // Tap skipping (conv_igemm_tapskip_kernel): the plain fp32 inference launch of a multi-tap, ungrouped convolution with whole K tiles per
+    // tap and an NHWC store (the NCHW store assumes four consecutive rows are four consecutive pixels of one image; the statistics epilogues
+    // sum per (phase, M tile) in row order).  PRECONDITION: finite weights - a K tile of out-of-image taps is not multiplied at all, so an
+    // inf / NaN weight no longer turns the zero padding into NaN.  Activations may hold anything: an in-image value is never skipped.
+    const bool tap_skip = !bf16 && !stats_s && !bsrc && !abn && !phs && uniform && d->taps_h * d->taps_w > 1 && d->c_in_group == 0 &&
+                          !(d->flags & (SP_CONV_OUT_NCHW | SP_CONV_PIXEL_SHUFFLE)) && tap_skip_enabled();
     a.abn_mean = nullptr; a.abn_invstd = a.abn_gamma = a.abn_beta = nullptr; a.abn_y = nullptr; a.abn_mask = nullptr;
     if (abn) {
         SP_REQUIRE(abn->mean && abn->invstd && abn->gamma && abn->beta && abn->y, "sp_conv2d_fwd_bn_stats_abn: null pointer");
@@ -1145,7 +1257,7 @@ static int conv_fwd_impl(const sp_conv_desc* d, const void* x, const void* w_pac
         SP_REQUIRE(rows <= stats_rows_capacity, "sp_conv2d_fwd_bn_stats: %lld partial rows needed, capacity %d", rows, stats_rows_capacity);
     }
 #define SP_TILE(BM_, BN_, WR_, WC_) \
-    if (bm == BM_ && bn == BN_) return launch<BM_, BN_, WR_, WC_>(a, phases, uniform, s);
+    if (bm == BM_ && bn == BN_) return launch<BM_, BN_, WR_, WC_>(a, phases, uniform, tap_skip, s);
     SP_TILE(128, 128, 2, 2)
     SP_TILE(64, 128, 2, 2)
     SP_TILE(128, 64, 2, 2)
