@@ -933,6 +933,79 @@ int sp_jpeg_decode_batch(const sp_jpeg_desc* descs_host, const sp_jpeg_desc* des
                          const int32_t* seg_offsets, int64_t seg_count, int16_t* coef, int64_t coef_size, uint8_t* planes, int64_t planes_size,
                          uint8_t* out, int64_t out_size, int32_t* status, int stages, void* stream);
 
+/* ---- baseline JPEG encoding: uint8 BGR [H,W,3] images in, file bytes out ---------------------------------------------------------------------
+ * (No new ABI version: these are additions.)  The file is the one libjpeg-turbo writes with its defaults (what PIL's save and cv2.imwrite
+ * give without optimised tables) byte for byte: 16.16 fixed-point BGR -> YCbCr, chroma averaged 2x1 / 2x2 without smoothing, the "islow"
+ * integer forward DCT, the Annex K quantisation tables scaled by `quality`, the Annex K Huffman tables, JFIF 1.01 header.  Baseline,
+ * three components, one interleaved scan, optional restart markers.  There is no CPU encode path. */
+#define SP_JPEG_ENC_HEADER_MAX 640          /* SOI .. SOS of any file this encoder writes is 623 bytes, 629 with a DRI segment */
+#define SP_JPEG_ENC_STATUS_OVERFLOW 1       /* the file does not fit out_capacity: nothing of it is written, its length is 0 */
+
+/* sp_jpeg_encode_batch `stages` */
+#define SP_JPEG_ENC_STAGE_COEF 1            /* colour, downsampling, forward DCT, quantisation, per-block bit counts */
+#define SP_JPEG_ENC_STAGE_SCAN 2            /* prefix sums: the bit offset of every block, the byte offset of every restart segment */
+#define SP_JPEG_ENC_STAGE_EMIT 4            /* Huffman codes into the unstuffed stream at those offsets */
+#define SP_JPEG_ENC_STAGE_STUFF 8           /* header, FF 00 stuffing, restart markers, EOI; length and status */
+#define SP_JPEG_ENC_STAGE_ALL 15
+
+/* bytes of workspace one image needs beyond desc.ws_bytes: they depend on the capacity the caller gives its file */
+#define SP_JPEG_ENC_STREAM_WS(cap) ((((int64_t)(cap) / 4096 + 2) * 8 + 63) / 64 * 64 + ((int64_t)(cap) + 127) / 64 * 64)
+
+/* One image.  sp_jpeg_enc_plan fills everything down to hlen; the caller fills the placement fields before sp_jpeg_encode_batch. */
+typedef struct sp_jpeg_enc_desc {
+    int32_t width, height;
+    int32_t subsampling;                              /* 444, 422 or 420 */
+    int32_t quality, restart_interval;                /* 1..100; MCUs per restart segment, 0 = no restart markers */
+    int32_t h_samp, v_samp;                           /* the luma sampling factors (chroma is 1x1) */
+    int32_t mcus_x, mcus_y;                           /* ceil(width / (8 h_samp)), ceil(height / (8 v_samp)) */
+    int32_t wb[3], hb[3];                             /* real blocks per row / column of each component: ceil(samples / 8) */
+    int32_t blocks_per_mcu;                           /* h_samp * v_samp + 2 */
+    int32_t blocks;                                   /* mcus_x * mcus_y * blocks_per_mcu: the scan, dummy blocks included */
+    int32_t segments;                                 /* ceil(MCUs / restart_interval), 1 without restart markers */
+    int32_t header_bytes;                             /* SOI .. SOS */
+    int64_t ws_bytes;                                 /* workspace of this image without its stream part (SP_JPEG_ENC_STREAM_WS) */
+    int64_t ws_coef, ws_bits, ws_pos, ws_seg, ws_chunk;   /* where its arrays lie in that region (bytes from ws_offset; see below) */
+    uint16_t quant[2][64];                            /* the scaled tables (0 luma, 1 chroma) in zigzag order */
+    uint8_t header[SP_JPEG_ENC_HEADER_MAX];           /* the file's first header_bytes bytes */
+    uint16_t hcode[4][256];                           /* code of symbol s in table 0 DC luma, 1 AC luma, 2 DC chroma, 3 AC chroma */
+    uint8_t hlen[4][256];                             /* ... and its length in bits (0: the table has no such symbol) */
+    /* the caller's part */
+    uint64_t src;                                     /* DEVICE address of the image: uint8 [height, width, 3] BGR, contiguous */
+    int64_t ws_offset;                                /* in bytes into `workspace`, a multiple of 64 */
+    int64_t out_offset;                               /* in bytes into `out` */
+    int64_t out_capacity;                             /* bytes the file may take at out_offset */
+} sp_jpeg_enc_desc;
+
+/* Host only, no GPU call: plan one image.  1 <= width, height <= 16384 (else SP_JPEG_ESIZE), subsampling 444 / 422 / 420 (else
+ * SP_JPEG_ESAMPLING), quality 1..100 and restart_interval 0..65535 (else SP_EINVAL).  Fills the geometry, the scaled tables, the complete
+ * header bytes and the workspace layout; the caller's part is zeroed. */
+int sp_jpeg_enc_plan(int width, int height, int subsampling, int quality, int restart_interval, sp_jpeg_enc_desc* desc);
+
+/* Encode `count` images of mixed sizes, sampling and quality.  descs_host / descs_dev: the same descriptors in HOST and in DEVICE memory;
+ * the host copy is planned again and compared, and its placement checked against workspace_size / out_size, before anything is launched.
+ * workspace: DEVICE, 64-byte aligned; image i owns [ws_offset, ws_offset + ws_bytes + SP_JPEG_ENC_STREAM_WS(out_capacity)).  out: DEVICE;
+ * image i's file is out + out_offset, length[i] bytes (header, entropy data, EOI).  length, status: int32 [count] DEVICE.  The regions of
+ * different images must not overlap (not checked).  The image's workspace, from ws_offset:
+ *   +0         uint64 [8]   total bits, unstuffed bytes, FF bytes, refused flag
+ *   +ws_coef   int16 [blocks][64]  quantised coefficients in zigzag order, blocks in scan order, DC absolute, dummy blocks zero
+ *   +ws_bits   uint16 [blocks]     bits of each block in the stream (at most 22 + 63 * 26)
+ *   +ws_pos    uint64 [blocks + 1] exclusive prefix sum of ws_bits
+ *   +ws_seg    uint64 [segments + 1]  first byte of each restart segment in the unstuffed stream
+ *   +ws_chunk  uint64 []    chunk sums of the two scans above;  +ws_bytes: those of the third, then the unstuffed stream
+ * `stages`: SP_JPEG_ENC_STAGE_ALL, or a subset (a bench / test runs them one at a time; later stages read what earlier ones left):
+ *   coef   one lane per block: colour, chroma averaging, forward DCT, quantisation, AC bit count; then the DC differences' bits
+ *   scan   three launches per prefix sum (256-element chunk sums; one workgroup per image scans the chunk sums; every chunk again, plus
+ *          its offset): bits per block -> ws_pos, then bytes per restart segment -> ws_seg.  An image whose unstuffed stream alone
+ *          exceeds out_capacity is refused here
+ *   emit   zero the stream's words, then one lane per block ORs its codes in at 8 * ws_seg[segment] + ws_pos[block] - ws_pos[segment's
+ *          first block]; the last block of a segment pads to the byte with 1-bits
+ *   stuff  a third prefix sum, over the FF bytes of the stream in 4096-byte chunks; its last launch writes header, data with FF 00
+ *          stuffing, FF D0..D7 between segments and FF D9, each lane 16 stream bytes.  length and status are written by this stage
+ * No lane walks more than one block, 16 stream bytes or (the chunk sums) blocks / 65536 entries.  An image that does not fit gets
+ * SP_JPEG_ENC_STATUS_OVERFLOW, length 0 and not one byte written to `out`.  Nothing synchronises; count == 0 is a no-op. */
+int sp_jpeg_encode_batch(const sp_jpeg_enc_desc* descs_host, const sp_jpeg_enc_desc* descs_dev, int count, void* workspace, int64_t workspace_size,
+                         uint8_t* out, int64_t out_size, int32_t* length, int32_t* status, int stages, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -69,6 +69,27 @@ SP_JPEG_STATUS = {1: "entropy data ended early", 2: "invalid Huffman code", 4: "
 SP_JPEG_STAGE_ENTROPY, SP_JPEG_STAGE_IDCT, SP_JPEG_STAGE_COLOR, SP_JPEG_STAGE_ALL = 1, 2, 4, 7
 
 
+class JpegEncDesc(ctypes.Structure):
+    """Mirror of `sp_jpeg_enc_desc` (field order is ABI): sp_jpeg_enc_plan fills it down to hlen, the caller places the image."""
+    _fields_ = [("width", c_int32), ("height", c_int32), ("subsampling", c_int32), ("quality", c_int32), ("restart_interval", c_int32),
+                ("h_samp", c_int32), ("v_samp", c_int32), ("mcus_x", c_int32), ("mcus_y", c_int32), ("wb", c_int32 * 3), ("hb", c_int32 * 3),
+                ("blocks_per_mcu", c_int32), ("blocks", c_int32), ("segments", c_int32), ("header_bytes", c_int32), ("ws_bytes", c_int64),
+                ("ws_coef", c_int64), ("ws_bits", c_int64), ("ws_pos", c_int64), ("ws_seg", c_int64), ("ws_chunk", c_int64),
+                ("quant", (ctypes.c_uint16 * 64) * 2), ("header", ctypes.c_uint8 * 640), ("hcode", (ctypes.c_uint16 * 256) * 4),
+                ("hlen", (ctypes.c_uint8 * 256) * 4), ("src", ctypes.c_uint64), ("ws_offset", c_int64), ("out_offset", c_int64),
+                ("out_capacity", c_int64)]
+
+
+SP_JPEG_ENC_HEADER_MAX = 640
+SP_JPEG_ENC_STATUS_OVERFLOW = 1
+SP_JPEG_ENC_STAGE_COEF, SP_JPEG_ENC_STAGE_SCAN, SP_JPEG_ENC_STAGE_EMIT, SP_JPEG_ENC_STAGE_STUFF, SP_JPEG_ENC_STAGE_ALL = 1, 2, 4, 8, 15
+
+
+def jpeg_enc_stream_ws(cap: int) -> int:
+    """SP_JPEG_ENC_STREAM_WS: the part of an image's encoder workspace that depends on its output capacity."""
+    return ((cap // 4096 + 2) * 8 + 63) // 64 * 64 + (cap + 127) // 64 * 64
+
+
 class RenderStyle(ctypes.Structure):
     """Mirror of `sp_render_style` (field order is ABI): host memory, copied into the kernel arguments by sp_render_poses_u8c3."""
     _fields_ = [("edges", c_int32), ("edge", (c_int32 * 2) * 64), ("joint_r", c_int32), ("limb_r", c_int32), ("box_r", c_int32),
@@ -223,6 +244,8 @@ SYMBOLS = {
     "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
     "sp_jpeg_parse": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32]),
     "sp_jpeg_decode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
+    "sp_jpeg_enc_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(JpegEncDesc)]),
+    "sp_jpeg_encode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int, _P]),
     "sp_render_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
     "sp_render_poses_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RenderStyle), _P, _P]),
 }

@@ -7,6 +7,13 @@ HipLibraryError with the parser's reason - there is no CPU decode path.
     dec = JpegDecoder("cuda:0")
     imgs = dec.decode([bytes, ...])                       # list of CUDA uint8 [H,W,3] BGR, views of one arena
     dec.decode_into([bytes, ...], frames)                 # equal-sized files into a [B,H,W,3] tensor (what estimate_batch takes)
+
+The way back (csrc/jpeg_enc.hip behind sp_jpeg_enc_plan / sp_jpeg_encode_batch): uint8 BGR frames in HBM in, the bytes of baseline JPEG
+files out, equal to what libjpeg-turbo writes with its defaults (PIL's save with optimize=False) byte for byte.
+
+    enc = JpegEncoder("cuda:0", quality=75, subsampling="4:2:0", restart_interval=0)
+    files = enc.encode(frames)                            # [B,H,W,3] CUDA uint8 BGR, or a list of [H,W,3] of any sizes -> list[bytes]
+    arena, offsets, lengths = enc.encode_device(frames)   # no synchronisation; lengths int32 [B] on the device
 """
 from __future__ import annotations
 
@@ -192,3 +199,153 @@ class JpegDecoder:
             raise _lib.HipLibraryError(f"decode_into: {len(files) if isinstance(files, (list, tuple)) else type(files).__name__} files for out {tuple(out.shape)}")
         self._run(files, out, check)
         return out
+
+
+_SUBSAMPLING = {"4:4:4": 444, "4:2:2": 422, "4:2:0": 420, 444: 444, 422: 422, 420: 420}
+
+
+class JpegEncoder:
+    """Batched encoder with reusable arenas on one device.  `encode` / `encode_device` run on torch's current stream of that device: one
+    pinned upload (the descriptors) and the launches of sp_jpeg_encode_batch (include/simple_pose_hip.h lists them).  What
+    `encode_device` returns are views of arenas that the next call overwrites.  There is no CPU encode path."""
+
+    def __init__(self, device="cuda", quality: int = 75, subsampling="4:2:0", restart_interval: int = 0):
+        if subsampling not in _SUBSAMPLING:
+            raise _lib.HipLibraryError(f"JpegEncoder: subsampling {subsampling!r}; expected '4:4:4', '4:2:2' or '4:2:0'")
+        for name, v in (("quality", quality), ("restart_interval", restart_interval)):
+            if isinstance(v, bool) or not isinstance(v, int):
+                raise TypeError(f"JpegEncoder: {name}: expected an int, got {type(v).__name__}")
+        self.quality, self.subsampling, self.restart_interval = quality, _SUBSAMPLING[subsampling], restart_interval
+        self._plans = {}
+        self._plan_for(8, 8)                      # quality / restart interval out of range: the planner's own refusal, before any GPU call
+        dev = torch.device(device)
+        if dev.type != "cuda":
+            raise _lib.HipLibraryError(f"JpegEncoder: device {dev}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
+        self.device = torch.device("cuda", _lib._device_index(dev))
+        self._pinned = self._upload_done = self._host_out = None
+        self._upload = self._ws = self._out = None
+        self.status = None                        # int32 [B] on the device after a call (0 = encoded, SP_JPEG_ENC_STATUS_OVERFLOW = does not fit)
+        self.lengths = None                       # int32 [B] on the device after a call
+        self.descs = None                         # the last call's descriptors (host copy)
+        self.coefficients = None                  # (int16 view of the workspace, [offset per image], [count per image]) of the last call, for tests
+        self.relaunch = None                      # after a call: relaunch(stages=SP_JPEG_ENC_STAGE_ALL) runs the same batch again without an upload
+
+    # ---- host side ------------------------------------------------------------------------------------------------------------------------------
+    def _plan_for(self, w: int, h: int):
+        d = self._plans.get((w, h))
+        if d is None:
+            d = _lib.JpegEncDesc()
+            _lib.check(_lib.lib().sp_jpeg_enc_plan(w, h, self.subsampling, self.quality, self.restart_interval, ctypes.byref(d)), "sp_jpeg_enc_plan")
+            if len(self._plans) < 64:
+                self._plans[(w, h)] = d
+        return d
+
+    def _frames(self, frames):
+        """-> list of contiguous CUDA uint8 [H,W,3] tensors on the encoder's device."""
+        if isinstance(frames, torch.Tensor):
+            if frames.dim() != 4:
+                raise _lib.HipLibraryError(f"frames: expected a uint8 tensor [B,H,W,3] or a list of [H,W,3] tensors, got shape {tuple(frames.shape)}")
+            self._check_frame(frames, "frames", 4)
+            return [frames[i] for i in range(frames.shape[0])]
+        if not isinstance(frames, (list, tuple)):
+            raise TypeError(f"frames: expected a uint8 tensor [B,H,W,3] or a list of [H,W,3] tensors, got {type(frames).__name__}")
+        for i, f in enumerate(frames):
+            self._check_frame(f, f"frames[{i}]", 3)
+        return list(frames)
+
+    def _check_frame(self, f, what, dims):
+        if not isinstance(f, torch.Tensor):
+            raise TypeError(f"{what}: expected a torch.Tensor, got {type(f).__name__}")
+        if f.dtype != torch.uint8:
+            raise TypeError(f"{what}: expected uint8, got {f.dtype}")
+        if not f.is_cuda or f.device != self.device:
+            raise _lib.HipLibraryError(f"{what}: tensor is on {f.device}, the encoder on {self.device} (no CPU fallback)")
+        if f.dim() != dims or f.shape[-1] != 3 or not f.is_contiguous() or f.shape[-2] < 1 or f.shape[-3] < 1:
+            raise _lib.HipLibraryError(f"{what}: expected a contiguous BGR image{'s' if dims == 4 else ''} [{'B,' if dims == 4 else ''}H,W,3], got shape "
+                                       f"{tuple(f.shape)}, strides {tuple(f.stride())}")
+
+    def default_capacity(self, w: int, h: int) -> int:
+        """Bytes reserved for one file unless the caller says otherwise: header + width * height * 3, rounded up to 64."""
+        return _round_up(self._plan_for(w, h).header_bytes + w * h * 3)
+
+    def _grow(self, name: str, size: int):
+        t = getattr(self, name)
+        if t is None or t.numel() < size:
+            t = torch.empty(max(size, 1), dtype=torch.uint8, device=self.device)
+            setattr(self, name, t)
+        return t
+
+    # ---- public ---------------------------------------------------------------------------------------------------------------------------------
+    def encode_device(self, frames, capacity=None):
+        """One batch of frames ([B,H,W,3] or a list of [H,W,3] of any sizes; CUDA uint8 BGR, contiguous) -> (arena, offsets, lengths): file i
+        is arena[offsets[i] : offsets[i] + lengths[i]], `lengths` an int32 [B] tensor on the device.  Nothing synchronises.  `capacity`:
+        bytes reserved per file (default: default_capacity); a file that does not fit has length 0 and SP_JPEG_ENC_STATUS_OVERFLOW in
+        `self.status`, and nothing of it is written."""
+        imgs = self._frames(frames)
+        n = len(imgs)
+        if capacity is not None and (isinstance(capacity, bool) or not isinstance(capacity, int) or capacity < 0 or capacity > 2 ** 31 - 1):
+            raise _lib.HipLibraryError(f"encode_device: capacity {capacity!r}; expected 0 .. 2^31 - 1 bytes")
+        descs = (_lib.JpegEncDesc * max(1, n))()
+        ws_at = out_at = 0
+        for i, f in enumerate(imgs):
+            h, w = int(f.shape[0]), int(f.shape[1])
+            try:
+                plan = self._plan_for(w, h)
+            except _lib.HipLibraryError as e:
+                raise _lib.HipLibraryError(f"frames[{i}]: {e}") from None
+            ctypes.memmove(ctypes.byref(descs[i]), ctypes.byref(plan), ctypes.sizeof(_lib.JpegEncDesc))
+            d = descs[i]
+            d.src, d.ws_offset, d.out_offset = f.data_ptr(), ws_at, out_at
+            d.out_capacity = self.default_capacity(w, h) if capacity is None else capacity
+            ws_at += _round_up(d.ws_bytes + _lib.jpeg_enc_stream_ws(d.out_capacity))
+            out_at += _round_up(d.out_capacity)
+        desc_bytes = ctypes.sizeof(_lib.JpegEncDesc) * n
+        if self._upload_done is not None:
+            self._upload_done.synchronize()       # the previous call's copy out of the pinned buffer
+        if self._pinned is None or self._pinned.numel() < desc_bytes:
+            self._pinned = torch.empty(max(desc_bytes, 1), dtype=torch.uint8).pin_memory()
+        if n:
+            self._pinned.numpy()[:desc_bytes] = np.frombuffer(descs, np.uint8, desc_bytes)
+        up = self._grow("_upload", desc_bytes)
+        ws = self._grow("_ws", ws_at)
+        out = self._grow("_out", out_at)
+        lengths = torch.empty(n, dtype=torch.int32, device=self.device)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            up[:desc_bytes].copy_(self._pinned[:desc_bytes], non_blocking=True)
+            self._upload_done = torch.cuda.Event()
+            self._upload_done.record()
+
+            def launch(stages=_lib.SP_JPEG_ENC_STAGE_ALL):
+                _lib.check(_lib.lib().sp_jpeg_encode_batch(descs, _lib.ptr(up), n, _lib.ptr(ws), ws.numel(), _lib.ptr(out), out.numel(), _lib.ptr(lengths),
+                                                           _lib.ptr(status), stages, _lib.current_stream(self.device)), "sp_jpeg_encode_batch")
+            launch()
+        self.relaunch, self.status, self.lengths, self.descs = launch, status, lengths, descs
+        self.coefficients = (ws.view(torch.int16), [(descs[i].ws_offset + descs[i].ws_coef) // 2 for i in range(n)], [descs[i].blocks * 64 for i in range(n)])
+        return out, [descs[i].out_offset for i in range(n)], lengths
+
+    def encode(self, frames, capacity=None) -> List[bytes]:
+        """-> the files as bytes objects.  One small device-to-host copy of the lengths and status words, then each file's own bytes (not
+        its capacity) into one pinned buffer.  A file that does not fit its capacity raises HipLibraryError naming its index."""
+        return self.collect(*self.encode_device(frames, capacity))
+
+    def collect(self, out, offsets, lengths) -> List[bytes]:
+        """What `encode_device` returned -> the files as bytes objects (the second half of `encode`; waits for the stream)."""
+        n = len(offsets)
+        if n == 0:
+            return []
+        meta = torch.stack([lengths, self.status]).cpu().numpy()
+        bad = np.nonzero(meta[1])[0]
+        if bad.size:
+            i = int(bad[0])
+            raise _lib.HipLibraryError(f"JpegEncoder: frames[{i}] does not fit its {self.descs[i].out_capacity} bytes (status {int(meta[1][i])}: "
+                                       f"overflow); {bad.size} of {n} files failed")
+        at = np.concatenate([[0], np.cumsum(meta[0])]).astype(np.int64)
+        if self._host_out is None or self._host_out.numel() < at[-1]:
+            self._host_out = torch.empty(int(at[-1]), dtype=torch.uint8).pin_memory()
+        with torch.cuda.device(self.device):
+            for i in range(n):
+                self._host_out[at[i]:at[i + 1]].copy_(out[offsets[i]:offsets[i] + int(meta[0][i])], non_blocking=True)
+            torch.cuda.current_stream().synchronize()
+        host = self._host_out.numpy()
+        return [host[at[i]:at[i + 1]].tobytes() for i in range(n)]

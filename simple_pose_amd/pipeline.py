@@ -15,7 +15,10 @@ With `flip_test=True` the crops are mirrored into a second half of the crop buff
 `2 * capacity` crops, and sp_heat_map_flip_merge averages the un-mirrored second half into the first before the decode: two more launches
 on the same stream, still one graph.
 With `renderer=PoseRenderer(...)` (visualize.py) the kept poses are drawn into a copy of the source image, `PoseResult.image`, by two more
-launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched."""
+launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched.
+With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer, the source - is encoded to a baseline JPEG file
+after the frame on the same stream (sp_jpeg_encode_batch, outside the graph: it uploads its descriptors), and `PoseResult.jpeg` holds the
+file's bytes; without one nothing is allocated or launched."""
 from __future__ import annotations
 
 import ctypes
@@ -28,6 +31,7 @@ import torch
 from . import _lib, engine
 from ._lib import HipLibraryError
 from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
+from .datasets.jpeg import JpegEncoder
 from .visualize import PoseRenderer
 
 P = _lib.ptr
@@ -44,6 +48,8 @@ class PoseResult:
     track_id: np.ndarray = None      # int32 [n]: the persons' identities (tracking.PoseTracker.update only; None from estimate*)
     image: torch.Tensor = None       # uint8 BGR [H, W, 3] on the device, the poses drawn in (estimators with a `renderer` only): a VIEW of the
                                      # frame's canvas, valid until the next call with the same source shape - .clone() it to keep it
+    jpeg: bytes = None               # the frame (the canvas, or the source without a renderer) as a baseline JPEG file (estimators with an
+                                     # `encoder` only)
 
     def __len__(self) -> int:
         return int(self.score.shape[0])
@@ -127,7 +133,7 @@ class TopDownPoseEstimator(object):
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
                  in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
-                 joint_pairs=None, shift_heatmap: bool = False, renderer=None):
+                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -153,6 +159,11 @@ class TopDownPoseEstimator(object):
         if renderer is not None and not isinstance(renderer, PoseRenderer):
             raise TypeError(f"renderer: expected a simple_pose_amd.visualize.PoseRenderer or None, got {type(renderer).__name__}")
         self.renderer = renderer
+        if encoder is not None and not isinstance(encoder, JpegEncoder):
+            raise TypeError(f"encoder: expected a simple_pose_amd.datasets.jpeg.JpegEncoder or None, got {type(encoder).__name__}")
+        if encoder is not None and encoder.device != torch.device(detector.device):
+            raise HipLibraryError(f"encoder: on {encoder.device}, the detector on {detector.device}")
+        self.encoder = encoder
         self._perm = None
         self.detector, self.pose_model, self.decoder = detector, pose_model, decoder
         self.capacity, self.person_cls, self.min_box_score = capacity, person_cls, float(min_box_score)
@@ -310,7 +321,10 @@ class TopDownPoseEstimator(object):
 
     def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
         """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
+        # the frames as JPEG files: launched behind the frame on its stream, before the fetch that waits for both
+        enc = None if self.encoder is None else self.encoder.encode_device(fr.src if self.renderer is None else fr.canvas)
         h = fr.fetch()
+        files = [None] * fr.B if enc is None else self.encoder.collect(*enc)
         if detected and (h["status"] & 1).any():
             b = int(np.nonzero(h["status"] & 1)[0][0])
             raise HipLibraryError(f"image {b}: more than {_lib.SP_YOLO_NMS_MAX_CANDIDATES} detector candidates after the multi-label expansion "
@@ -322,7 +336,7 @@ class TopDownPoseEstimator(object):
                 raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
             rows = h["keep"][lo:lo + n]
             out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b]),
-                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b]))
+                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b], files[b]))
         return out
 
     # -- public surface -----------------------------------------------------------------------------------------------------------------
