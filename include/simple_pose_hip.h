@@ -856,8 +856,8 @@ int sp_render_poses_u8c3(const unsigned char* src, unsigned char* dst, int h, in
  * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
  * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF
  * orientation is not applied.  Accepted: SOF0, 8-bit samples, 1 or 3 components, luma sampling 1x1, 2x1 or 2x2 with 1x1 chroma, one
- * interleaved scan, 8-bit quantisation tables, APPn / COM segments skipped.  Anything else is refused by sp_jpeg_parse with its own code;
- * there is no CPU decode path. */
+ * interleaved scan, 8-bit quantisation tables, APPn / COM segments skipped.  Anything else is refused by sp_jpeg_parse with its own code
+ * (progressive SOF2 files: SP_JPEG_EPROGRESSIVE, and sp_jpeg_parse_scans below takes them); there is no CPU decode path. */
 #define SP_JPEG_ETRUNCATED (-10)   /* a header segment runs past the end of the buffer (the message names the byte offset) */
 #define SP_JPEG_ENOT_JPEG (-11)    /* no SOI, or no marker where one has to be */
 #define SP_JPEG_EPROGRESSIVE (-12) /* SOF2 */
@@ -932,6 +932,60 @@ int sp_jpeg_parse(const uint8_t* data, int64_t size, sp_jpeg_desc* desc, int32_t
 int sp_jpeg_decode_batch(const sp_jpeg_desc* descs_host, const sp_jpeg_desc* descs_dev, int count, const uint8_t* bytes, int64_t bytes_size,
                          const int32_t* seg_offsets, int64_t seg_count, int16_t* coef, int64_t coef_size, uint8_t* planes, int64_t planes_size,
                          uint8_t* out, int64_t out_size, int32_t* status, int stages, void* stream);
+
+/* ---- progressive JPEG decoding: a second parser and a second entropy stage that fill the same coefficient arena ---------------------------
+ * (No new ABI version: these are additions.)  A complete progressive file goes through the same islow IDCT, fancy upsampling and colour
+ * conversion as a baseline one, so sp_jpeg_parse_scans + sp_jpeg_progressive_entropy replace sp_jpeg_parse + the entropy stage, and
+ * sp_jpeg_decode_batch(stages = IDCT | COLOR) finishes the image: the pixels are libjpeg-turbo's bit for bit.
+ * Accepted: SOF2, 8-bit samples, 1 or 3 components, the sampling factors and the Adobe rule of the baseline parser, any number of scans
+ * (spectral selection and successive approximation, DC scans interleaved or not, a new DHT / DRI before any scan).
+ * Refused: a scan header libjpeg rejects or warns about (SP_JPEG_EBAD_SCAN); a progression that ends before every component has its DC
+ * and its zigzag coefficients 1..9 down to bit 0 (SP_JPEG_EINCOMPLETE: libjpeg-turbo smooths such files between blocks, the ordinary
+ * IDCT does not give its pixels; coefficients 10..63 may stay unsent or unrefined); a DQT after the first SOS (SP_JPEG_EBAD_TABLE);
+ * SOF0 with several scans (SP_JPEG_ESCANS: baseline files go to sp_jpeg_parse); everything sp_jpeg_parse refuses, with the same codes.
+ * Block geometry.  A scan of two or three components is interleaved over the frame's MCU grid (mcus_x x mcus_y, h x v blocks per
+ * component per MCU), like the baseline scan.  A scan of ONE component is not interleaved: its MCU is one block, it covers
+ * ceil(comp_width / 8) x ceil(comp_height / 8) blocks with comp_width = ceil(width * h / hmax) - not the MCU-padded grid - and its
+ * restart interval counts blocks; the padding blocks keep what the interleaved scans gave them.  The arena layout is the baseline one. */
+#define SP_JPEG_EBAD_SCAN (-23)    /* Ss / Se / Ah / Al or the component list of a scan is invalid, or does not continue the progression */
+#define SP_JPEG_EINCOMPLETE (-24)  /* the progression ends before every component has DC and coefficients 1..9 down to bit 0 */
+
+/* One scan of a progressive file, as sp_jpeg_parse_scans found it. */
+typedef struct sp_jpeg_scan {
+    int32_t components, comp[3];                      /* 1..3 frame component indices, ascending */
+    int32_t ss, se, ah, al;                           /* spectral band (zigzag positions), successive approximation high / low bit */
+    int32_t restart_interval;                         /* the DRI value in force at this SOS (it may change between scans) */
+    int32_t ecs_offset, ecs_end;                      /* this scan's entropy bytes in the file */
+    int32_t seg_index, segments;                      /* this scan's restart segments: seg_index is relative to the file's desc.seg_index */
+    int32_t reserved;
+    uint8_t huff_counts[3][16];                       /* the tables THIS scan uses, as in force at its SOS: first DC scan: one per scan */
+    uint8_t huff_values[3][256];                      /* component; AC scan: [0]; a DC refinement scan uses none (all zero) */
+} sp_jpeg_scan;
+
+/* Host only, no GPU call: parse one progressive file.  *desc as sp_jpeg_parse fills it, with segments = the total over all scans,
+ * ecs_offset = the first scan's start, ecs_end = the last scan's end, restart_interval = the first scan's, dc_sel / ac_sel and the
+ * Huffman fields zero (the tables are per scan).  scans (HOST, may be NULL with scan_capacity 0) receives at most scan_capacity
+ * records, *scan_count the number found; seg_offsets (HOST, may be NULL with seg_capacity 0) the first entropy byte of every restart
+ * segment of every scan, in file order, at most seg_capacity of them (desc->segments is the number found): call again with larger
+ * arrays when a count exceeds its capacity.  Nothing is written past a capacity.  Returns SP_OK or SP_JPEG_E* with the reason and the
+ * byte offset in sp_last_error. */
+int sp_jpeg_parse_scans(const uint8_t* data, int64_t size, sp_jpeg_desc* desc, sp_jpeg_scan* scans, int32_t scan_capacity,
+                        int32_t* scan_count, int32_t* seg_offsets, int32_t seg_capacity);
+
+/* The entropy stage of `count` progressive files: what sp_jpeg_decode_batch(stages = ENTROPY) is for baseline ones.  descs, bytes,
+ * seg_offsets, coef, status: as there.  scans_host / scans_dev: scan_total records in HOST and DEVICE memory; scan_range_host /
+ * scan_range_dev int32 [count + 1]: file i owns scans [r[i], r[i + 1]), 1..256 of them.  Every host-side range (scan ranges, each
+ * scan's entropy bytes inside its file, its segments inside the table, the coefficient region inside the arena) is checked before
+ * anything is launched, the device pointers last.  Two launches: one zeroes every file's coefficient region, then
+ * jpeg_prog_entropy_kernel, one 64-lane workgroup per file, walks the file's scans in file order: per scan it builds the scan's
+ * Huffman tables in LDS, lane s decodes restart segments s, s + 64, ... of the scan, and a workgroup barrier ends the scan (refinement
+ * scans read what earlier scans wrote).  status[i]: the SP_JPEG_STATUS_* bits OR-ed over the file's scans (SEGMENTS: a scan whose
+ * segment count is not ceil(scan MCUs / interval); the excess is ignored).  A damaged stream ends in a non-zero status, never in an
+ * access outside the file's own regions.  Nothing synchronises; count == 0 is a no-op. */
+int sp_jpeg_progressive_entropy(const sp_jpeg_desc* descs_host, const sp_jpeg_desc* descs_dev, int count, const sp_jpeg_scan* scans_host,
+                                const sp_jpeg_scan* scans_dev, const int32_t* scan_range_host, const int32_t* scan_range_dev,
+                                int64_t scan_total, const uint8_t* bytes, int64_t bytes_size, const int32_t* seg_offsets, int64_t seg_count,
+                                int16_t* coef, int64_t coef_size, int32_t* status, void* stream);
 
 /* ---- baseline JPEG encoding: uint8 BGR [H,W,3] images in, file bytes out ---------------------------------------------------------------------
  * (No new ABI version: these are additions.)  The file is the one libjpeg-turbo writes with its defaults (what PIL's save and cv2.imwrite

@@ -67,6 +67,14 @@ SP_JPEG_ETRUNCATED, SP_JPEG_ENOT_JPEG, SP_JPEG_EPROGRESSIVE, SP_JPEG_EEXTENDED, 
 SP_JPEG_STATUS = {1: "entropy data ended early", 2: "invalid Huffman code", 4: "AC run past coefficient 63", 8: "restart segment count mismatch",
                   16: "invalid Huffman table"}
 SP_JPEG_STAGE_ENTROPY, SP_JPEG_STAGE_IDCT, SP_JPEG_STAGE_COLOR, SP_JPEG_STAGE_ALL = 1, 2, 4, 7
+SP_JPEG_EBAD_SCAN, SP_JPEG_EINCOMPLETE = -23, -24      # sp_jpeg_parse_scans (progressive files)
+
+
+class JpegScan(ctypes.Structure):
+    """Mirror of `sp_jpeg_scan` (field order is ABI): one scan of a progressive file, as sp_jpeg_parse_scans found it."""
+    _fields_ = [("components", c_int32), ("comp", c_int32 * 3), ("ss", c_int32), ("se", c_int32), ("ah", c_int32), ("al", c_int32),
+                ("restart_interval", c_int32), ("ecs_offset", c_int32), ("ecs_end", c_int32), ("seg_index", c_int32), ("segments", c_int32),
+                ("reserved", c_int32), ("huff_counts", (ctypes.c_uint8 * 16) * 3), ("huff_values", (ctypes.c_uint8 * 256) * 3)]
 
 
 class JpegEncDesc(ctypes.Structure):
@@ -244,6 +252,8 @@ SYMBOLS = {
     "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
     "sp_jpeg_parse": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32]),
     "sp_jpeg_decode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
+    "sp_jpeg_parse_scans": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32, ctypes.POINTER(c_int32), _P, c_int32]),
+    "sp_jpeg_progressive_entropy": (c_int, [_P, _P, c_int, _P, _P, _P, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "sp_jpeg_enc_plan": (c_int, [c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(JpegEncDesc)]),
     "sp_jpeg_encode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int, _P]),
     "sp_render_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
@@ -287,7 +297,9 @@ def conv_kernel_name(desc, has_residual: bool = False, variant: int = 0) -> str:
 def check(rc: int, what: str = ""):
     if rc != 0:
         msg = lib().sp_last_error().decode("utf-8", "replace")
-        raise HipLibraryError(f"{what or 'libsimple_pose_hip'} failed (code {rc}): {msg}")
+        err = HipLibraryError(f"{what or 'libsimple_pose_hip'} failed (code {rc}): {msg}")
+        err.code = rc                             # for a caller that answers one code itself (JpegDecoder: SP_JPEG_EPROGRESSIVE)
+        raise err
 
 
 def ptr(t):

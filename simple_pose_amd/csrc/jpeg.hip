@@ -12,6 +12,7 @@
 
 #include "sp_jpeg.h"
 #include "sp_jpeg_parse.h"
+#include "sp_jpeg_zero.h"
 
 namespace {
 
@@ -42,21 +43,10 @@ __device__ __forceinline__ JpegGeom jpeg_geom(const sp_jpeg_desc& d) {
 }
 
 // ---- zero the coefficient regions --------------------------------------------------------------------------------------------------------------
-// grid (x, image): the image's own region only (what lies between two regions is the caller's).  16-byte stores over the aligned body,
-// single int16 stores over the at most 7 + 7 elements around it.
+// grid (x, image): the image's own region only (sp_jpeg_zero.h, shared with jpeg_prog.hip)
 __global__ __launch_bounds__(256) void jpeg_zero_coef_kernel(const sp_jpeg_desc* __restrict__ descs, int16_t* __restrict__ coef) {
     const sp_jpeg_desc& d = descs[blockIdx.y];
-    int16_t* p = coef + d.coef_offset;
-    const int n = d.coef_count;
-    const int head = min(n, (int)((16 - ((uintptr_t)p & 15)) & 15) / 2);          // elements up to the first 16-byte boundary
-    const int vecs = (n - head) / 8;
-    const int tid = blockIdx.x * 256 + threadIdx.x;
-    u32x4* body = reinterpret_cast<u32x4*>(p + head);
-    const u32x4 zero = {0u, 0u, 0u, 0u};
-    for (int i = tid; i < vecs; i += gridDim.x * 256) body[i] = zero;
-    if (tid < head) p[tid] = 0;
-    const int tail0 = head + vecs * 8;
-    if (tid < n - tail0) p[tail0 + tid] = 0;
+    sp_jpeg_zero_region(coef + d.coef_offset, d.coef_count, blockIdx.x * 256 + threadIdx.x, gridDim.x * 256);
 }
 
 // ---- entropy decode ---------------------------------------------------------------------------------------------------------------------------

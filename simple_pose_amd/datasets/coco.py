@@ -1,7 +1,7 @@
 """Input contract of the hot path: the normalisation half of the reference's `MSCOCO.collate_fn`
 (`datasets/coco.py:124-148`), on the GPU; and `GpuAugmentLoader`, the training loader that replaces `MSCOCO`'s per-sample
 transform + `collate_fn` with one batched GPU transform (`commons.transforms.RefineSimpleTransform.batch`).  COCO parsing stays out
-of scope.  A sample carries either its decoded image on the device (`.img`) or the bytes of its baseline JPEG file (`.jpeg`), which
+of scope.  A sample carries either its decoded image on the device (`.img`) or the bytes of its baseline or progressive JPEG file (`.jpeg`), which
 the loader decodes on the device, a batch's files in one call (`datasets.jpeg.JpegDecoder`: libjpeg-turbo's pixels bit for bit, EXIF
 orientation not applied)."""
 from __future__ import annotations
@@ -63,7 +63,7 @@ class GpuAugmentLoader:
     `DDPProcessor(train_loader=...)` takes.  Yields (input fp32 [B,3,256,192], heat_maps fp32 [B,J,64,48], masks fp32 [B,J],
     trans_inv fp32 [B,2,3], img_ids).
 
-    `samples`: objects with `.img` (CUDA uint8 [H,W,3] BGR) or `.jpeg` (the bytes of a baseline JPEG file; decoded on `device`, one
+    `samples`: objects with `.img` (CUDA uint8 [H,W,3] BGR) or `.jpeg` (the bytes of a baseline or progressive JPEG file; decoded on `device`, one
     `JpegDecoder.decode` call per batch, just before the transform - a batch may mix both kinds), `.box` (x1, y1, x2, y2), `.joints` ([J,3] float32, host), `.shape`
     (w, h) and `.img_id` or `.img_path`.  The epoch's order is DistributedSampler's (torch.randperm under a generator seeded with
     seed + epoch, padded by wrap-around, every `world`-th index from `rank`, whole batches only); the augmentation draws of an

@@ -1,9 +1,12 @@
-"""Baseline JPEG decoding on the device: file bytes in, uint8 BGR images in HBM out (csrc/jpeg.hip behind sp_jpeg_parse /
-sp_jpeg_decode_batch).  The pixels are libjpeg-turbo's default decode (what cv2.imread and PIL give) bit for bit.  EXIF orientation is
-not applied.  Accepted: SOF0, 8-bit, 1 or 3 components, 4:4:4 / 4:2:2 / 4:2:0, one interleaved scan; anything else raises
-HipLibraryError with the parser's reason - there is no CPU decode path.
+"""JPEG decoding on the device: file bytes in, uint8 BGR images in HBM out (csrc/jpeg.hip behind sp_jpeg_parse /
+sp_jpeg_decode_batch; csrc/jpeg_prog.hip behind sp_jpeg_parse_scans / sp_jpeg_progressive_entropy for progressive files).  The pixels are
+libjpeg-turbo's default decode (what cv2.imread and PIL give) bit for bit.  EXIF orientation is not applied.  Accepted: 8-bit, 1 or 3
+components, 4:4:4 / 4:2:2 / 4:2:0; baseline SOF0 with one interleaved scan, or progressive SOF2 with a complete progression (every
+component's DC and zigzag coefficients 1..9 down to bit 0).  Anything else - incomplete progressions and multi-scan SOF0 among it -
+raises HipLibraryError with the parser's reason: there is no CPU decode path.
 
-    info = parse(open(path, "rb").read())                 # host only
+    info = parse(open(path, "rb").read())                 # host only; baseline files
+    info, scans = parse_scans(open(path, "rb").read())    # host only; progressive files
     dec = JpegDecoder("cuda:0")
     imgs = dec.decode([bytes, ...])                       # list of CUDA uint8 [H,W,3] BGR, views of one arena
     dec.decode_into([bytes, ...], frames)                 # equal-sized files into a [B,H,W,3] tensor (what estimate_batch takes)
@@ -77,14 +80,60 @@ def parse(data) -> JpegInfo:
                     np.ctypeslib.as_array(d.huff_values).copy())
 
 
+@dataclass
+class JpegScanInfo:
+    components: Tuple[int, ...]                   # frame component indices, ascending; more than one: interleaved over the MCU grid
+    ss: int
+    se: int
+    ah: int
+    al: int
+    restart_interval: int                         # MCUs per segment; blocks of the component when the scan has one component
+    segments: int
+
+
+def _parse_scans_raw(data: bytes, scan_buf, seg_buf: np.ndarray):
+    """-> (JpegDesc, JpegScan array of the file's scans, int32 segment offsets, scan scratch, segment scratch).  The scratch arrays are
+    replaced by larger ones when the file needs them, and returned for the caller to keep."""
+    desc, count = _lib.JpegDesc(), ctypes.c_int32(0)
+    lib = _lib.lib()
+    for _ in range(2):
+        rc = lib.sp_jpeg_parse_scans(data, len(data), ctypes.byref(desc), ctypes.addressof(scan_buf), len(scan_buf), ctypes.byref(count),
+                                     seg_buf.ctypes.data, seg_buf.size)
+        if rc != 0 or (count.value <= len(scan_buf) and desc.segments <= seg_buf.size):
+            break
+        if count.value > len(scan_buf):
+            scan_buf = (_lib.JpegScan * count.value)()
+        if desc.segments > seg_buf.size:
+            seg_buf = np.empty(desc.segments, np.int32)
+    _lib.check(rc, "sp_jpeg_parse_scans")
+    scans = (_lib.JpegScan * count.value)()
+    ctypes.memmove(scans, scan_buf, ctypes.sizeof(scans))
+    return desc, scans, seg_buf[:desc.segments].copy(), scan_buf, seg_buf
+
+
+def parse_scans(data) -> Tuple[JpegInfo, Tuple[JpegScanInfo, ...]]:
+    """Headers and scan list of one progressive file (host only, no GPU call).  The JpegInfo has no Huffman tables (they are per scan) and
+    the restart interval of the first scan; seg_offsets lists the segments of every scan, in file order.  Raises HipLibraryError with
+    the reason for anything the decoder does not take - baseline files among it, which `parse` takes."""
+    d, scans, segs, _, _ = _parse_scans_raw(_as_bytes(data), (_lib.JpegScan * 16)(), np.empty(1024, np.int32))
+    n = d.components
+    info = JpegInfo(d.width, d.height, n, tuple((d.h_samp[c], d.v_samp[c]) for c in range(n)), tuple(d.quant_sel[:n]), tuple(d.dc_sel[:n]),
+                    tuple(d.ac_sel[:n]), d.restart_interval, (d.mcus_x, d.mcus_y), d.ecs_offset, d.ecs_end, tuple(int(s) for s in segs),
+                    np.ctypeslib.as_array(d.quant).copy(), np.ctypeslib.as_array(d.huff_counts).copy(),
+                    np.ctypeslib.as_array(d.huff_values).copy())
+    return info, tuple(JpegScanInfo(tuple(s.comp[:s.components]), s.ss, s.se, s.ah, s.al, s.restart_interval, s.segments) for s in scans)
+
+
 def _round_up(v: int, m: int = _ALIGN) -> int:
     return (v + m - 1) // m * m
 
 
 class JpegDecoder:
     """Batched decoder with reusable arenas on one device.  `decode` / `decode_into` run on torch's current stream of that device: one
-    pinned upload (descriptors, segment tables and file bytes in one buffer) and four launches (zero, entropy, IDCT, colour).  The tensors `decode`
-    returns are views of the output arena and are overwritten by the next call."""
+    pinned upload (descriptors, segment tables and file bytes in one buffer) and four launches (zero, entropy, IDCT, colour).  A batch
+    with progressive files uploads their scan records in the same buffer and launches the entropy stage per kind (baseline files, then
+    progressive ones: zero + entropy each) before one IDCT and one colour launch over all files.  The tensors `decode` returns are views
+    of the output arena and are overwritten by the next call."""
 
     def __init__(self, device="cuda"):
         dev = torch.device(device)
@@ -92,6 +141,7 @@ class JpegDecoder:
             raise _lib.HipLibraryError(f"JpegDecoder: device {dev}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
         self.device = torch.device("cuda", _lib._device_index(dev))
         self._seg_scratch = np.empty(1024, np.int32)
+        self._scan_scratch = (_lib.JpegScan * 16)()
         self._pinned = self._upload_done = None
         self._upload = self._coef = self._planes = self._out = None
         self.status = None                        # int32 [B] on the device after a call (0 = decoded; bits: _lib.SP_JPEG_STATUS)
@@ -100,26 +150,52 @@ class JpegDecoder:
 
     # ---- host side: parse every file, lay the arenas out ------------------------------------------------------------------------------------
     def _plan(self, files: Sequence):
+        """-> (datas, descs, by_file, order, n_base, scans, scan_range, segs, arena sizes).  descs: [baseline files..., progressive files...]
+        (n_base of the first kind), each with its own offsets, laid out in the caller's order; descs[k] is files[order[k]] and by_file[i]
+        the descriptor of files[i] (a view into descs); scans: the progressive files' scan records, file k's at scan_range[k - n_base]."""
         if isinstance(files, (bytes, bytearray, memoryview, torch.Tensor)) or not isinstance(files, (list, tuple)):
             raise TypeError("files: expected a list or tuple of bytes objects (one per JPEG file)")
         datas = [_as_bytes(f, f"files[{i}]") for i, f in enumerate(files)]
-        descs = (_lib.JpegDesc * max(1, len(datas)))()
-        segs = []
-        seg_at = file_at = coef_at = plane_at = out_at = 0
+        parsed = []                               # per file: (descriptor, segment offsets, scan records or None)
+        file_at = coef_at = plane_at = out_at = 0
         for i, data in enumerate(datas):
             try:
-                d, s, self._seg_scratch = _parse_raw(data, self._seg_scratch)
+                try:
+                    d, s, self._seg_scratch = _parse_raw(data, self._seg_scratch)
+                    scans = None
+                except _lib.HipLibraryError as e:             # the baseline parser first; what it refuses as progressive goes to the scan parser
+                    if getattr(e, "code", 0) != _lib.SP_JPEG_EPROGRESSIVE:
+                        raise
+                    d, scans, s, self._scan_scratch, self._seg_scratch = _parse_scans_raw(data, self._scan_scratch, self._seg_scratch)
             except _lib.HipLibraryError as e:
                 raise _lib.HipLibraryError(f"files[{i}]: {e}") from None
-            d.seg_index, d.file_offset, d.coef_offset, d.plane_offset, d.out_offset = seg_at, file_at, coef_at, plane_at, out_at
-            descs[i] = d
-            segs.append(s)
-            seg_at += len(s)
+            d.file_offset, d.coef_offset, d.plane_offset, d.out_offset = file_at, coef_at, plane_at, out_at
+            parsed.append((d, s, scans))
             file_at += _round_up(len(data))
             coef_at += _round_up(d.coef_count * 2) // 2
             plane_at += _round_up(d.plane_bytes)
             out_at += _round_up(d.out_bytes)
-        return datas, descs, segs, (seg_at, file_at, coef_at, plane_at, out_at)
+        order = [i for i, p in enumerate(parsed) if p[2] is None] + [i for i, p in enumerate(parsed) if p[2] is not None]
+        n_base = sum(p[2] is None for p in parsed)
+        descs = (_lib.JpegDesc * max(1, len(datas)))()
+        segs, scan_range, seg_at = [], [0], 0
+        for k, i in enumerate(order):
+            d, s, scans = parsed[i]
+            d.seg_index = seg_at
+            descs[k] = d
+            segs.append(s)
+            seg_at += len(s)
+            if scans is not None:
+                scan_range.append(scan_range[-1] + len(scans))
+        scans = (_lib.JpegScan * max(1, scan_range[-1]))()
+        at = 0
+        for i in order[n_base:]:
+            ctypes.memmove(ctypes.byref(scans, at * ctypes.sizeof(_lib.JpegScan)), parsed[i][2], ctypes.sizeof(parsed[i][2]))
+            at += len(parsed[i][2])
+        by_file = [None] * len(datas)
+        for k, i in enumerate(order):
+            by_file[i] = descs[k]
+        return datas, descs, by_file, order, n_base, scans, scan_range, segs, (seg_at, file_at, coef_at, plane_at, out_at)
 
     def _grow(self, name: str, size: int, dtype):
         t = getattr(self, name)
@@ -129,19 +205,25 @@ class JpegDecoder:
         return t
 
     def _run(self, files, out_tensor=None, check=True):
-        datas, descs, segs, (n_seg, n_bytes, n_coef, n_plane, n_out) = self._plan(files)
+        datas, descs, by_file, order, n_base, scans, scan_range, segs, (n_seg, n_bytes, n_coef, n_plane, n_out) = self._plan(files)
         n = len(datas)
+        n_prog, n_scans = n - n_base, scan_range[-1]
         if out_tensor is not None:
             for i in range(n):
-                if (descs[i].height, descs[i].width) != tuple(out_tensor.shape[1:3]):
-                    raise _lib.HipLibraryError(f"decode_into: files[{i}] is {descs[i].width}x{descs[i].height}, out holds "
+                if (by_file[i].height, by_file[i].width) != tuple(out_tensor.shape[1:3]):
+                    raise _lib.HipLibraryError(f"decode_into: files[{i}] is {by_file[i].width}x{by_file[i].height}, out holds "
                                                f"{out_tensor.shape[2]}x{out_tensor.shape[1]} frames")
-                descs[i].out_offset = i * descs[0].out_bytes
-            n_out = n * descs[0].out_bytes if n else 0
-        # one upload: [descriptors | segment offsets | file bytes]
-        desc_bytes = ctypes.sizeof(_lib.JpegDesc) * n
+                by_file[i].out_offset = i * by_file[0].out_bytes
+            n_out = n * by_file[0].out_bytes if n else 0
+        # one upload: [descriptors | segment offsets | scan records | scan ranges | caller's order | file bytes]; the three in the middle
+        # are empty without progressive files
+        desc_size, scan_size = ctypes.sizeof(_lib.JpegDesc), ctypes.sizeof(_lib.JpegScan)
+        desc_bytes = desc_size * n
         seg_off = _round_up(desc_bytes)
-        byte_off = _round_up(seg_off + 4 * n_seg)
+        scan_off = _round_up(seg_off + 4 * n_seg)
+        range_off = _round_up(scan_off + scan_size * n_scans)
+        perm_off = _round_up(range_off + (4 * (n_prog + 1) if n_prog else 0))
+        byte_off = _round_up(perm_off + (8 * n if n_prog else 0))
         total = byte_off + n_bytes
         if self._upload_done is not None:
             self._upload_done.synchronize()       # the previous call's copy out of the pinned buffer (check=False does not wait for it)
@@ -151,36 +233,60 @@ class JpegDecoder:
         if n:
             host[:desc_bytes] = np.frombuffer(descs, np.uint8, desc_bytes)
             host[seg_off:seg_off + 4 * n_seg] = np.concatenate(segs).astype(np.int32).view(np.uint8)
+        if n_prog:
+            host[scan_off:scan_off + scan_size * n_scans] = np.frombuffer(scans, np.uint8, scan_size * n_scans)
+            host[range_off:range_off + 4 * (n_prog + 1)] = np.asarray(scan_range, np.int32).view(np.uint8)
+            where = np.empty(n, np.int64)
+            where[order] = np.arange(n)           # files[i] is descriptor where[i]
+            host[perm_off:perm_off + 8 * n] = where.view(np.uint8)
         for i, data in enumerate(datas):
-            o = byte_off + descs[i].file_offset
+            o = byte_off + by_file[i].file_offset
             host[o:o + len(data)] = np.frombuffer(data, np.uint8)
         up = self._grow("_upload", total, torch.uint8)
         coef = self._grow("_coef", n_coef, torch.int16)
         planes = self._grow("_planes", n_plane, torch.uint8)
         out = out_tensor if out_tensor is not None else self._grow("_out", n_out, torch.uint8)
         status = torch.empty(n, dtype=torch.int32, device=self.device)
+        range_host = (ctypes.c_int32 * (n_prog + 1))(*scan_range)
         with torch.cuda.device(self.device):
             up[:total].copy_(self._pinned[:total], non_blocking=True)
             self._upload_done = torch.cuda.Event()
             self._upload_done.record()
             base = up.data_ptr()
+            where_dev = up[perm_off:perm_off + 8 * n].view(torch.int64) if n_prog else None
+
+            def batch(first, count, stages):
+                _lib.check(_lib.lib().sp_jpeg_decode_batch(ctypes.addressof(descs) + first * desc_size, base + first * desc_size, count, base + byte_off,
+                                                           n_bytes, base + seg_off, n_seg, _lib.ptr(coef), coef.numel(), _lib.ptr(planes),
+                                                           planes.numel(), _lib.ptr(out), out.numel(), status.data_ptr() + 4 * first, stages,
+                                                           _lib.current_stream(self.device)), "sp_jpeg_decode_batch")
 
             def launch(stages=_lib.SP_JPEG_STAGE_ALL):
-                _lib.check(_lib.lib().sp_jpeg_decode_batch(descs, base, n, base + byte_off, n_bytes, base + seg_off, n_seg, _lib.ptr(coef),
-                                                           coef.numel(), _lib.ptr(planes), planes.numel(), _lib.ptr(out), out.numel(),
-                                                           _lib.ptr(status), stages, _lib.current_stream(self.device)), "sp_jpeg_decode_batch")
+                if not n_prog:                    # baseline files only: the one call there has always been
+                    batch(0, n, stages)
+                    self.status = status
+                    return
+                if stages & _lib.SP_JPEG_STAGE_ENTROPY:
+                    if n_base:
+                        batch(0, n_base, _lib.SP_JPEG_STAGE_ENTROPY)
+                    _lib.check(_lib.lib().sp_jpeg_progressive_entropy(
+                        ctypes.addressof(descs) + n_base * desc_size, base + n_base * desc_size, n_prog, scans, base + scan_off, range_host,
+                        base + range_off, n_scans, base + byte_off, n_bytes, base + seg_off, n_seg, _lib.ptr(coef), coef.numel(),
+                        status.data_ptr() + 4 * n_base, _lib.current_stream(self.device)), "sp_jpeg_progressive_entropy")
+                    self.status = status.index_select(0, where_dev)      # the caller's file order
+                if stages & ~_lib.SP_JPEG_STAGE_ENTROPY:
+                    batch(0, n, stages & ~_lib.SP_JPEG_STAGE_ENTROPY)    # writes no status
             launch()
         self.relaunch = launch                    # tools/bench_jpeg.py: the same batch again, or one stage of it (SP_JPEG_STAGE_*), no upload
-        self.status = status
-        self.coefficients = (coef, [descs[i].coef_offset for i in range(n)], [descs[i].coef_count for i in range(n)])
+        self.coefficients = (coef, [by_file[i].coef_offset for i in range(n)], [by_file[i].coef_count for i in range(n)])
         if check and n:
-            st = status.cpu().numpy()
+            st = self.status.cpu().numpy()
             bad = np.nonzero(st)[0]
             if bad.size:
                 i = int(bad[0])
                 why = ", ".join(t for b, t in _lib.SP_JPEG_STATUS.items() if st[i] & b)
                 raise _lib.HipLibraryError(f"JpegDecoder: files[{i}] is damaged (status {int(st[i])}: {why}); {bad.size} of {n} files failed")
-        return descs, out
+        return by_file, out
 
     # ---- public --------------------------------------------------------------------------------------------------------------------------------
     def decode(self, files: Sequence[bytes], check: bool = True) -> List[torch.Tensor]:

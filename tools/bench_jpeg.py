@@ -9,8 +9,10 @@ and 512 files per call it reports
 Every time is [median, min, max] in ms over separately timed runs (--iters device runs, 7 wall-clock runs); img/s is from the median.
 The parent process never touches the GPU: every configuration runs in a child of its own under `timeout`, one at a time, and the first
 child that fails ends the run.  Writes ONE JSON line (and --out, default profiles/jpeg_bench.json).
+--progressive: the same for PIL's progressive saves of the 640x480 images (10 scans; sp_jpeg_progressive_entropy is the entropy stage),
+written to profiles/jpeg_prog_bench.json.
 
-    python tools/bench_jpeg.py [--iters 10] [--out profiles/jpeg_bench.json]
+    python tools/bench_jpeg.py [--progressive] [--iters 10] [--out profiles/jpeg_bench.json]
 """
 from __future__ import annotations
 
@@ -28,14 +30,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 if ROOT not in sys.path:
     sys.path.insert(0, ROOT)
 
-CONFIGS = [("640x480", 640, 480, False), ("640x480_rst", 640, 480, True), ("1280x720", 1280, 720, False), ("1280x720_rst", 1280, 720, True)]
+CONFIGS = [("640x480", 640, 480, False, False), ("640x480_rst", 640, 480, True, False), ("1280x720", 1280, 720, False, False),
+           ("1280x720_rst", 1280, 720, True, False)]
+PROGRESSIVE_CONFIGS = [("640x480_prog", 640, 480, False, True), ("640x480_prog_rst", 640, 480, True, True)]
 BATCHES = (32, 128, 512)
 THREADS = 16
 DISTINCT = 16
 REPS = 7                        # wall-clock repetitions of decode() and of the PIL baseline
 
 
-def make_files(w, h, restart, n=DISTINCT, seed=0):
+def make_files(w, h, restart, progressive=False, n=DISTINCT, seed=0):
     from PIL import Image
     rng = np.random.RandomState(seed)
     yy, xx = np.mgrid[0:h, 0:w].astype(np.float32)
@@ -49,6 +53,8 @@ def make_files(w, h, restart, n=DISTINCT, seed=0):
         opts = dict(quality=90, subsampling=2)
         if restart:
             opts["restart_marker_rows"] = 1
+        if progressive:
+            opts["progressive"] = True
         Image.fromarray(np.clip(np.stack(ch, -1), 0, 255).astype(np.uint8), "RGB").save(buf, "JPEG", **opts)
         files.append(buf.getvalue())
     return files
@@ -60,8 +66,8 @@ def child(name, iters):
     from PIL import Image
     from simple_pose_amd import _lib
     from simple_pose_amd.datasets.jpeg import JpegDecoder
-    _, w, h, restart = next(c for c in CONFIGS if c[0] == name)
-    distinct = make_files(w, h, restart)
+    _, w, h, restart, progressive = next(c for c in CONFIGS + PROGRESSIVE_CONFIGS if c[0] == name)
+    distinct = make_files(w, h, restart, progressive)
     res = {"file_kB_mean": round(float(np.mean([len(f) for f in distinct])) / 1e3, 1)}
     dec = JpegDecoder("cuda")
     ref = np.asarray(Image.open(io.BytesIO(distinct[0])).convert("RGB"))[:, :, ::-1]
@@ -115,15 +121,19 @@ def child(name, iters):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--iters", type=int, default=10)
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jpeg_bench.json"))
+    ap.add_argument("--progressive", action="store_true", help="progressive files (PROGRESSIVE_CONFIGS) instead of baseline ones")
+    ap.add_argument("--out", default=None, help="default: profiles/jpeg_bench.json, profiles/jpeg_prog_bench.json with --progressive")
     ap.add_argument("--step-timeout", type=int, default=150)
     ap.add_argument("--child", default=None)
     args = ap.parse_args()
     if args.child:
         child(args.child, args.iters)
         return 0
-    res = {"bench": "jpeg", "threads": THREADS, "times": "[median, min, max] ms", "files": "PIL, 4:2:0, quality 90; _rst = one restart marker per MCU row"}
-    for name, *_ in CONFIGS:                                   # one GPU process at a time, each under its own timeout
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "jpeg_prog_bench.json" if args.progressive else "jpeg_bench.json")
+    res = {"bench": "jpeg_progressive" if args.progressive else "jpeg", "threads": THREADS, "times": "[median, min, max] ms",
+           "files": "PIL, 4:2:0, quality 90; _rst = one restart marker per MCU row" + ("; _prog = progressive=True (10 scans)" if args.progressive else "")}
+    for name, *_ in (PROGRESSIVE_CONFIGS if args.progressive else CONFIGS):                                   # one GPU process at a time, each under its own timeout
         cmd = ["timeout", "-k", "10", str(args.step_timeout), sys.executable, os.path.abspath(__file__), "--child", name, "--iters", str(args.iters)]
         r = subprocess.run(cmd, capture_output=True, text=True)
         line = next((l for l in r.stdout.splitlines() if l.startswith("RESULT ")), None)
