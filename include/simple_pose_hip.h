@@ -756,6 +756,37 @@ int sp_topdown_plan(const float* det, const int32_t* counts, int batch, int max_
 int sp_warp_affine_plan_u8c3(const unsigned char* src, int batch, int src_h, int src_w, const double* m_inv, const int32_t* src_index,
                              const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream);
 
+/* ---- batches of differently sized images: per-image geometry from a table in device memory ------------------------------------------------
+ * (No new ABI version: these are additions.)  sp_image_ref describes one source image: contiguous uint8 BGR [h, w, 3] in device memory
+ * (1 <= h, w <= 32767), its letterbox (ScalePadding.geometry: resized to new_h x new_w, placed at (top, left) of the canvas, ratio = the
+ * resize factor as a float) and dst_index, its position in the caller's order.  The kernels read an array of `batch` of them from DEVICE
+ * memory; the caller fills it on the host and uploads it.  Each entry point below is its counterpart above with the launch-wide scalars
+ * replaced by the table's: the same device functions produce every pixel and every box, so image b's results have the bits of the
+ * counterpart run on image b alone.  The table's contents cannot be checked on the host: the caller guarantees valid pointers and sizes,
+ * top, left >= 0, and dst_index inside det_all / counts_all / status_all. */
+typedef struct sp_image_ref {
+    const unsigned char* data;              /* device pointer */
+    int32_t h, w;
+    int32_t new_h, new_w, top, left;
+    float ratio;
+    int32_t dst_index;
+} sp_image_ref;                             /* 40 bytes */
+/* sp_yolo_letterbox with every image's own source size, resize target and placement on the common out_h x out_w canvas of 114 (a canvas
+ * pixel outside an image's new_h x new_w rectangle is padding, wherever the rectangle lies); both modes; out_h, out_w even. */
+int sp_yolo_letterbox_images(const sp_image_ref* images_dev, int batch, int out_h, int out_w, int mode, void* out, void* stream);
+/* sp_yolo_boxes_to_source, out of place, for one detector group of a larger batch: det_group fp32 [batch, max_det, 6], counts_group /
+ * status_group int32 [batch] as sp_yolo_nms_device wrote them for images letterboxed to img_h x img_w.  Rows [0, counts_group[b]) of
+ * block b are clipped and un-letterboxed with images[b]'s left, top, ratio and written to block images[b].dst_index of det_all
+ * (fp32 [total, max_det, 6]); the block's other rows are written as zeros; counts_all / status_all [dst_index] receive the count and the
+ * status word.  det_all must not overlap det_group.  One launch. */
+int sp_yolo_boxes_to_source_images(const float* det_group, const int32_t* counts_group, const int32_t* status_group,
+                                   const sp_image_ref* images_dev, int batch, int max_det, float img_h, float img_w, float* det_all,
+                                   int32_t* counts_all, int32_t* status_all, void* stream);
+/* sp_warp_affine_plan_u8c3 with the source pointer and size of slot s taken from images[src_index[s]] (src_index as sp_topdown_plan wrote
+ * it: the image's position in the plan's det, which is the table's order here; dst_index is not read).  Dead slots are written as zeros. */
+int sp_warp_affine_plan_images_u8c3(const sp_image_ref* images_dev, int batch, const double* m_inv, const int32_t* src_index,
+                                    const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream);
+
 /* ---- flip test: the mirrored network input and the merge of the two sets of heat maps ----------------------------------------------------
  * sp_mirror_w: dst[r, x] = src[r, w-1-x] over `rows` rows of `w` elements of elem_bytes bytes: 3 = uint8 BGR NHWC crops (rows = N*H),
  * 4 = fp32 NCHW inputs (rows = N*C*H).  Out of place only: dst may be the second half of the allocation that holds src, overlapping ranges

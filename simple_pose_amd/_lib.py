@@ -105,6 +105,13 @@ class RenderStyle(ctypes.Structure):
                 ("palette", (ctypes.c_uint8 * 3) * 32)]
 
 
+class ImageRef(ctypes.Structure):
+    """Mirror of `sp_image_ref` (field order is ABI): one source image of a batch of differently sized images.  An array of them is built on
+    the host and uploaded; the kernels read it from device memory."""
+    _fields_ = [("data", ctypes.c_uint64), ("h", c_int32), ("w", c_int32), ("new_h", c_int32), ("new_w", c_int32), ("top", c_int32),
+                ("left", c_int32), ("ratio", c_float), ("dst_index", c_int32)]
+
+
 SP_RENDER_COLOUR_PERSON, SP_RENDER_COLOUR_PART = 0, 1
 SP_RENDER_MAX_EDGES, SP_RENDER_MAX_PALETTE, SP_RENDER_MAX_RADIUS = 64, 32, 1024
 
@@ -245,6 +252,9 @@ SYMBOLS = {
     "sp_yolo_nms_device": (c_int, [_P, c_int, c_int, c_int, c_float, c_float, c_int, c_int, c_int, c_int, _P, c_int64, _P, _P, _P, _P]),
     "sp_topdown_plan": (c_int, [_P, _P, c_int, c_int, c_int, c_float, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
     "sp_warp_affine_plan_u8c3": (c_int, [_P, c_int, c_int, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
+    "sp_yolo_letterbox_images": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "sp_yolo_boxes_to_source_images": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
+    "sp_warp_affine_plan_images_u8c3": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
     "sp_mirror_w": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
     "sp_heat_map_flip_merge": (c_int, [_P, _P, ctypes.POINTER(c_int32), c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sp_track_associate": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,

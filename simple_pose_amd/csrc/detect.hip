@@ -22,18 +22,31 @@ __device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0
     a1 = __float2int_rn(f * 2048.f);
 }
 
-struct LbArgs {
+// one image's letterbox: source, resize target and placement on the canvas
+struct LbImage {
     const unsigned char* src;
-    int B, sh, sw, nh, nw, top, left, oh, ow, mode;
+    int sh, sw, nh, nw, top, left;
     double sy, sx;      // source / destination size ratios (OpenCV's scale_y / scale_x)
     int kind;           // 0 copy, 1 bilinear, 2 INTER_AREA 2x
 };
 
-// BGR values of canvas pixel (oy, ox) of image b: the source coefficients are computed once per pixel for its three channels
-__device__ __forceinline__ void canvas_px(const LbArgs& a, int b, int oy, int ox, int v[3]) {
+// OpenCV: inv_scale = dsize / ssize, scale = 1 / inv_scale.  Host and device: two IEEE double divisions, the same bits on both
+__host__ __device__ __forceinline__ void lb_scales(LbImage& im) {
+    im.sx = 1.0 / ((double)im.nw / im.sw);
+    im.sy = 1.0 / ((double)im.nh / im.sh);
+    im.kind = (im.nh == im.sh && im.nw == im.sw) ? 0 : ((im.sw == 2 * im.nw && im.sh == 2 * im.nh) ? 2 : 1);
+}
+
+struct LbArgs {
+    LbImage im;         // image 0; image b's source follows at b * sh * sw * 3
+    int B, oh, ow, mode;
+};
+
+// BGR values of canvas pixel (oy, ox) of one image: the source coefficients are computed once per pixel for its three channels
+__device__ __forceinline__ void canvas_px(const LbImage& a, int oy, int ox, int v[3]) {
     const int y = oy - a.top, x = ox - a.left;
     if (y < 0 || y >= a.nh || x < 0 || x >= a.nw) { v[0] = v[1] = v[2] = 114; return; }
-    const unsigned char* S = a.src + (size_t)b * a.sh * a.sw * 3;
+    const unsigned char* S = a.src;
     if (a.kind == 0) {
         const unsigned char* p = S + ((size_t)y * a.sw + x) * 3;
         for (int c = 0; c < 3; ++c) v[c] = p[c];
@@ -58,30 +71,23 @@ __device__ __forceinline__ void canvas_px(const LbArgs& a, int b, int oy, int ox
     }
 }
 
-__global__ void letterbox_kernel(const LbArgs a, void* out) {
+// output element i of the launch (SP_LETTERBOX_U8: canvas pixel r = oy * ow + ox of its image; SP_LETTERBOX_FOCUS: Focus cell
+// r = fy * (ow / 2) + fx), shared by the dense and the table launch
+__device__ __forceinline__ void letterbox_store(const LbImage& im, int mode, int ow, int r, long long i, void* out) {
     int px[3];
-    if (a.mode == SP_LETTERBOX_U8) {
-        const long long n = (long long)a.B * a.oh * a.ow;
-        const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-        if (i >= n) return;
-        const int b = (int)(i / ((long long)a.oh * a.ow));
-        const int r = (int)(i - (long long)b * a.oh * a.ow), oy = r / a.ow, ox = r - oy * a.ow;
+    if (mode == SP_LETTERBOX_U8) {
+        const int oy = r / ow, ox = r - oy * ow;
         unsigned char* o = reinterpret_cast<unsigned char*>(out) + i * 3;
-        canvas_px(a, b, oy, ox, px);
+        canvas_px(im, oy, ox, px);
         for (int c = 0; c < 3; ++c) o[c] = (unsigned char)px[c];
         return;
     }
-    const int fh = a.oh / 2, fw = a.ow / 2;
-    const long long n = (long long)a.B * fh * fw;
-    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
-    if (i >= n) return;
-    const int b = (int)(i / ((long long)fh * fw));
-    const int r = (int)(i - (long long)b * fh * fw), fy = r / fw, fx = r - fy * fw;
+    const int fw = ow / 2, fy = r / fw, fx = r - fy * fw;
     float v[12];
 #pragma unroll
     for (int g = 0; g < 4; ++g) {
         const int oy = 2 * fy + (g & 1), ox = 2 * fx + (g >> 1);         // Focus: (::2, ::2), (1::2, ::2), (::2, 1::2), (1::2, 1::2)
-        canvas_px(a, b, oy, ox, px);
+        canvas_px(im, oy, ox, px);
 #pragma unroll
         for (int c = 0; c < 3; ++c) v[3 * g + c] = (float)px[2 - c] / 255.f;     // BGR -> RGB, .div(255.0)
     }
@@ -89,6 +95,31 @@ __global__ void letterbox_kernel(const LbArgs a, void* out) {
     o[0] = f32x4{v[0], v[1], v[2], v[3]};
     o[1] = f32x4{v[4], v[5], v[6], v[7]};
     o[2] = f32x4{v[8], v[9], v[10], v[11]};
+}
+
+__global__ void letterbox_kernel(const LbArgs a, void* out) {
+    const long long per = a.mode == SP_LETTERBOX_U8 ? (long long)a.oh * a.ow : (long long)(a.oh / 2) * (a.ow / 2);
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= a.B * per) return;
+    const int b = (int)(i / per);
+    LbImage im = a.im;
+    im.src += (size_t)b * im.sh * im.sw * 3;
+    letterbox_store(im, a.mode, a.ow, (int)(i - b * per), i, out);
+}
+
+// every image's geometry from the table (sp_image_ref, device memory): differently sized sources on one canvas size.  An entry without a
+// source or with an empty size gives an all-padding canvas instead of a read
+__global__ void letterbox_images_kernel(const sp_image_ref* __restrict__ images, int B, int oh, int ow, int mode, void* out) {
+    const long long per = mode == SP_LETTERBOX_U8 ? (long long)oh * ow : (long long)(oh / 2) * (ow / 2);
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * per) return;
+    const int b = (int)(i / per);
+    const sp_image_ref ref = images[b];
+    LbImage im;
+    im.src = ref.data; im.sh = ref.h; im.sw = ref.w; im.nh = ref.new_h; im.nw = ref.new_w; im.top = ref.top; im.left = ref.left;
+    if (!im.src || im.sh <= 0 || im.sw <= 0 || im.nh <= 0 || im.nw <= 0) { im.nh = im.nw = 0; im.sh = im.sw = 1; }
+    lb_scales(im);
+    letterbox_store(im, mode, ow, (int)(i - b * per), i, out);
 }
 
 __global__ void focus_nchw_kernel(const float* __restrict__ x, int B, int h, int w, float* __restrict__ out) {
@@ -401,14 +432,41 @@ __global__ __launch_bounds__(NT) void nms_select_kernel(NmsWs ws, float iou_thr,
     }
 }
 
+// clip_coords to the letterboxed image, then the un-letterbox: one detection row (its box columns), shared by both launches below
+__device__ __forceinline__ void box_to_source(const float* s, float* d, float img_h, float img_w, float left, float top, float ratio) {
+    d[0] = (fminf(fmaxf(s[0], 0.f), img_w) - left) / ratio;
+    d[1] = (fminf(fmaxf(s[1], 0.f), img_h) - top) / ratio;
+    d[2] = (fminf(fmaxf(s[2], 0.f), img_w) - left) / ratio;
+    d[3] = (fminf(fmaxf(s[3], 0.f), img_h) - top) / ratio;
+}
+
 __global__ void boxes_to_source_kernel(float* det, int rows, float img_h, float img_w, float left, float top, float ratio) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= rows) return;
     float* d = det + (size_t)i * 6;
-    d[0] = (fminf(fmaxf(d[0], 0.f), img_w) - left) / ratio;
-    d[1] = (fminf(fmaxf(d[1], 0.f), img_h) - top) / ratio;
-    d[2] = (fminf(fmaxf(d[2], 0.f), img_w) - left) / ratio;
-    d[3] = (fminf(fmaxf(d[3], 0.f), img_h) - top) / ratio;
+    box_to_source(d, d, img_h, img_w, left, top, ratio);
+}
+
+// one detector group of a mixed batch: block b of the group's NMS output goes, un-letterboxed with image b's own offsets and ratio, to
+// block images[b].dst_index of the call-wide arrays; rows from the count on are written as zeros
+__global__ void boxes_to_source_images_kernel(const float* __restrict__ det, const int* __restrict__ counts, const int* __restrict__ status,
+                                              const sp_image_ref* __restrict__ images, int B, int max_det, float img_h, float img_w,
+                                              float* __restrict__ det_all, int* __restrict__ counts_all, int* __restrict__ status_all) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * max_det) return;
+    const int b = i / max_det, r = i - b * max_det;
+    const sp_image_ref ref = images[b];
+    if (ref.dst_index < 0) return;
+    const int n = counts[b];
+    const float* s = det + (size_t)i * 6;
+    float* d = det_all + ((size_t)ref.dst_index * max_det + r) * 6;
+    if (r < n) {
+        box_to_source(s, d, img_h, img_w, (float)ref.left, (float)ref.top, ref.ratio);
+        d[4] = s[4]; d[5] = s[5];
+    } else {
+        for (int k = 0; k < 6; ++k) d[k] = 0.f;
+    }
+    if (r == 0) { counts_all[ref.dst_index] = n; status_all[ref.dst_index] = status[b]; }
 }
 
 int64_t nms_ws_layout(int B, NmsWs* ws, void* base) {
@@ -436,14 +494,23 @@ extern "C" int sp_yolo_letterbox(const unsigned char* src, int batch, int src_h,
     SP_REQUIRE(mode == SP_LETTERBOX_U8 || (mode == SP_LETTERBOX_FOCUS && out_h % 2 == 0 && out_w % 2 == 0),
                "sp_yolo_letterbox: mode %d (Focus output needs an even canvas)", mode);
     LbArgs a;
-    a.src = src; a.B = batch; a.sh = src_h; a.sw = src_w; a.nh = new_h; a.nw = new_w; a.top = top; a.left = left; a.oh = out_h; a.ow = out_w;
-    a.mode = mode;
-    a.sx = 1.0 / ((double)new_w / src_w);        // OpenCV: inv_scale = dsize / ssize, scale = 1 / inv_scale
-    a.sy = 1.0 / ((double)new_h / src_h);
-    a.kind = (new_h == src_h && new_w == src_w) ? 0 : ((src_w == 2 * new_w && src_h == 2 * new_h) ? 2 : 1);
+    a.im.src = src; a.im.sh = src_h; a.im.sw = src_w; a.im.nh = new_h; a.im.nw = new_w; a.im.top = top; a.im.left = left;
+    lb_scales(a.im);
+    a.B = batch; a.oh = out_h; a.ow = out_w; a.mode = mode;
     const long long n = mode == SP_LETTERBOX_U8 ? (long long)batch * out_h * out_w : (long long)batch * (out_h / 2) * (out_w / 2);
     hipLaunchKernelGGL(letterbox_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, a, out);
     return sp_check_launch("letterbox_kernel");
+}
+
+extern "C" int sp_yolo_letterbox_images(const sp_image_ref* images_dev, int batch, int out_h, int out_w, int mode, void* out, void* stream) {
+    SP_REQUIRE(images_dev && out, "sp_yolo_letterbox_images: null pointer");
+    SP_REQUIRE(batch >= 1 && out_h > 0 && out_w > 0 && out_h % 2 == 0 && out_w % 2 == 0 && (long long)batch * out_h * out_w * 12 < (1ll << 31),
+               "sp_yolo_letterbox_images: batch %d (>= 1), canvas %dx%d (even sizes)", batch, out_h, out_w);
+    SP_REQUIRE(mode == SP_LETTERBOX_U8 || mode == SP_LETTERBOX_FOCUS, "sp_yolo_letterbox_images: mode %d", mode);
+    const long long n = mode == SP_LETTERBOX_U8 ? (long long)batch * out_h * out_w : (long long)batch * (out_h / 2) * (out_w / 2);
+    hipLaunchKernelGGL(letterbox_images_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, images_dev, batch, out_h, out_w, mode,
+                       out);
+    return sp_check_launch("letterbox_images_kernel");
 }
 
 extern "C" int sp_yolo_focus_nchw(const float* x, int batch, int h, int w, float* out, void* stream) {
@@ -576,4 +643,16 @@ extern "C" int sp_yolo_boxes_to_source(float* det, int rows, float img_h, float 
     if (rows == 0) return SP_OK;
     hipLaunchKernelGGL(boxes_to_source_kernel, dim3(sp_ceil_div(rows, 256)), dim3(256), 0, (hipStream_t)stream, det, rows, img_h, img_w, left, top, ratio);
     return sp_check_launch("boxes_to_source_kernel");
+}
+
+extern "C" int sp_yolo_boxes_to_source_images(const float* det_group, const int32_t* counts_group, const int32_t* status_group,
+                                              const sp_image_ref* images_dev, int batch, int max_det, float img_h, float img_w, float* det_all,
+                                              int32_t* counts_all, int32_t* status_all, void* stream) {
+    SP_REQUIRE(det_group && counts_group && status_group && images_dev && det_all && counts_all && status_all,
+               "sp_yolo_boxes_to_source_images: null pointer");
+    SP_REQUIRE(batch >= 1 && max_det > 0 && max_det <= SP_YOLO_NMS_MAX_DET && img_h > 0.f && img_w > 0.f,
+               "sp_yolo_boxes_to_source_images: batch %d (>= 1), max_det %d (1..%d)", batch, max_det, SP_YOLO_NMS_MAX_DET);
+    hipLaunchKernelGGL(boxes_to_source_images_kernel, dim3(sp_ceil_div(batch * max_det, 256)), dim3(256), 0, (hipStream_t)stream, det_group,
+                       counts_group, status_group, images_dev, batch, max_det, img_h, img_w, det_all, counts_all, status_all);
+    return sp_check_launch("boxes_to_source_images_kernel");
 }

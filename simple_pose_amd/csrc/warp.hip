@@ -8,6 +8,8 @@
 // normalisation, one source image per sample) runs the same per-pixel function and writes 12 B of fp32 (+ 3 B of optional crop).
 // The top-down estimator's crops (sp_warp_affine_plan_u8c3) take their maps and source indices from DEVICE memory (sp_topdown_plan wrote
 // them), so that the launch can sit in a captured graph; same per-pixel function, dead slots zero-filled.
+// sp_warp_affine_plan_images_u8c3 is that launch for a batch of differently sized images: each slot's source pointer and size come from a
+// table of sp_image_ref in device memory.
 #include "sp_common.h"
 
 #include <stdint.h>
@@ -64,15 +66,9 @@ __global__ __launch_bounds__(256) void warp_affine_u8c3_kernel(const unsigned ch
     }
 }
 
-// The crops of a device-side plan (sp_topdown_plan): slot blockIdx.y reads its map and its source image index from device memory, so
-// the launch needs nothing from the host.  Slots from seg[B] on (and any slot whose index is not an image of the batch) are zero-filled.
-// Per live crop: out_h * out_w * 3 B written, the 48 B map read, and the box's footprint of the source read once from HBM / L2.
-__global__ __launch_bounds__(256) void warp_affine_plan_u8c3_kernel(const unsigned char* __restrict__ src, int B, int H, int W,
-                                                                    const double* __restrict__ m_inv, const int* __restrict__ src_index,
-                                                                    const int* __restrict__ seg, unsigned char* __restrict__ dst, int oh, int ow) {
-    const int n = blockIdx.y;
-    const int b = src_index[n];
-    const bool live = n < seg[B] && b >= 0 && b < B;
+// The body both plan kernels share: slot n's crop of the H x W image S, or zeros when the slot is not live.
+__device__ __forceinline__ void plan_slot_u8c3(const unsigned char* __restrict__ S, int H, int W, bool live, const double* __restrict__ m_inv, int n,
+                                               unsigned char* __restrict__ dst, int oh, int ow) {
     unsigned char* D = dst + (size_t)n * oh * ow * 3;
     if (!live) {                                              // 16-byte stores where the slot allows it (256 x 192 x 3 B slots do)
         const size_t bytes = (size_t)oh * ow * 3;
@@ -87,7 +83,6 @@ __global__ __launch_bounds__(256) void warp_affine_plan_u8c3_kernel(const unsign
     double M[6];
 #pragma unroll
     for (int i = 0; i < 6; ++i) M[i] = m_inv[(size_t)n * 6 + i];
-    const unsigned char* S = src + (size_t)b * H * W * 3;
     for (int i = blockIdx.x * 256 + threadIdx.x; i < oh * ow; i += gridDim.x * 256) {
         const int y = i / ow, x = i - y * ow;
         unsigned char v[3];
@@ -95,6 +90,36 @@ __global__ __launch_bounds__(256) void warp_affine_plan_u8c3_kernel(const unsign
         unsigned char* d = D + (size_t)i * 3;
         d[0] = v[0]; d[1] = v[1]; d[2] = v[2];
     }
+}
+
+// The crops of a device-side plan (sp_topdown_plan): slot blockIdx.y reads its map and its source image index from device memory, so
+// the launch needs nothing from the host.  Slots from seg[B] on (and any slot whose index is not an image of the batch) are zero-filled.
+// Per live crop: out_h * out_w * 3 B written, the 48 B map read, and the box's footprint of the source read once from HBM / L2.
+__global__ __launch_bounds__(256) void warp_affine_plan_u8c3_kernel(const unsigned char* __restrict__ src, int B, int H, int W,
+                                                                    const double* __restrict__ m_inv, const int* __restrict__ src_index,
+                                                                    const int* __restrict__ seg, unsigned char* __restrict__ dst, int oh, int ow) {
+    const int n = blockIdx.y;
+    const int b = src_index[n];
+    const bool live = n < seg[B] && b >= 0 && b < B;
+    plan_slot_u8c3(live ? src + (size_t)b * H * W * 3 : src, H, W, live, m_inv, n, dst, oh, ow);
+}
+
+// The same for a batch of differently sized images: slot n's source pointer and size come from images[src_index[n]] (sp_image_ref, device
+// memory).  A slot whose image has no source or a size outside 1 .. 32767 is zero-filled like a dead slot.
+__global__ __launch_bounds__(256) void warp_affine_plan_images_u8c3_kernel(const sp_image_ref* __restrict__ images, int B,
+                                                                           const double* __restrict__ m_inv, const int* __restrict__ src_index,
+                                                                           const int* __restrict__ seg, unsigned char* __restrict__ dst, int oh,
+                                                                           int ow) {
+    const int n = blockIdx.y;
+    const int b = src_index[n];
+    bool live = n < seg[B] && b >= 0 && b < B;
+    const unsigned char* S = nullptr;
+    int H = 0, W = 0;
+    if (live) {
+        S = images[b].data; H = images[b].h; W = images[b].w;
+        live = S && H > 0 && W > 0 && H <= 32767 && W <= 32767;
+    }
+    plan_slot_u8c3(S, H, W, live, m_inv, n, dst, oh, ow);
 }
 
 // Training batches (RefineSimpleTransform + MSCOCO.collate_fn): every sample has its own source image, size, flip flag and map.
@@ -160,6 +185,18 @@ extern "C" int sp_warp_affine_plan_u8c3(const unsigned char* src, int batch, int
     hipLaunchKernelGGL(warp_affine_plan_u8c3_kernel, dim3(blocks, capacity), dim3(256), 0, (hipStream_t)stream, src, batch, src_h, src_w, m_inv,
                        src_index, seg, dst, out_h, out_w);
     return sp_check_launch("warp_affine_plan_u8c3_kernel");
+}
+
+extern "C" int sp_warp_affine_plan_images_u8c3(const sp_image_ref* images_dev, int batch, const double* m_inv, const int32_t* src_index,
+                                               const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream) {
+    SP_REQUIRE(images_dev && m_inv && src_index && seg && dst, "sp_warp_affine_plan_images_u8c3: null pointer");
+    SP_REQUIRE(batch >= 1 && out_h > 0 && out_w > 0 && (long long)out_h * out_w < (1ll << 28),
+               "sp_warp_affine_plan_images_u8c3: bad shape batch=%d (>= 1) out %dx%d", batch, out_h, out_w);
+    SP_REQUIRE(capacity >= 1 && capacity <= 2048, "sp_warp_affine_plan_images_u8c3: capacity %d (1..2048)", capacity);
+    const int blocks = sp_ceil_div((long long)out_h * out_w, 256 * 4);
+    hipLaunchKernelGGL(warp_affine_plan_images_u8c3_kernel, dim3(blocks, capacity), dim3(256), 0, (hipStream_t)stream, images_dev, batch, m_inv,
+                       src_index, seg, dst, out_h, out_w);
+    return sp_check_launch("warp_affine_plan_images_u8c3_kernel");
 }
 
 extern "C" int sp_warp_affine_batch_u8c3_to_nchw_f32(const unsigned char* const* srcs_host, const int* src_hw_host, const int* flip_host,

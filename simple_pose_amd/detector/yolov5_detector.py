@@ -140,6 +140,7 @@ class YOLOv5Detector(object):
         self.model.to(self.device)
         self.use_graph = True
         self._graphs: Dict[tuple, object] = {}
+        self._stage: dict = {}               # predict on differently sized images: the pinned staging buffer and the device arena
 
     def program(self, out_h: int, out_w: int) -> engine.Program:
         """The fp32 program of one letterboxed shape (uint8 source input, letterbox inside)."""
@@ -182,16 +183,32 @@ class YOLOv5Detector(object):
     @torch.no_grad()
     def predict(self, imgs: Union[torch.Tensor, Sequence[np.ndarray]]) -> list:
         """A batch of same-sized uint8 BGR images (CUDA [B, H, W, 3], or a list of [H, W, 3] arrays) in one forward and one NMS launch
-        sequence; per image what single_predict returns."""
+        sequence; per image what single_predict returns.  A list of differently sized images (numpy or CUDA) is grouped by letterboxed
+        net shape: one forward and one NMS sequence per group, every image letterboxed as single_predict letterboxes it alone."""
         if isinstance(imgs, torch.Tensor):
             src = _as_cuda_u8(imgs, self.device)
             if src.dim() != 4:
                 raise ValueError("predict takes a batch [B, H, W, 3]")
         else:
-            if len({tuple(np.shape(i)) for i in imgs}) != 1:
-                raise ValueError("predict: the images of one batch share one size")
+            if len({tuple(np.shape(i)) for i in imgs}) != 1 or any(isinstance(i, torch.Tensor) for i in imgs):
+                return self._predict_mixed(imgs)
             src = _as_cuda_u8(np.stack([np.asarray(i) for i in imgs]), self.device)
         g = self.transform.geometry(src.shape[1], src.shape[2])
         pred = self._forward(src, g, False)
         dets = non_max_suppression(pred, multi_label=True, iou_thresh=self.iou_thresh, conf_thresh=self.conf_thresh, merge=True)
         return self._finish(dets, g)
+
+    def _predict_mixed(self, imgs) -> list:
+        """predict for a list of differently sized images: the table of sp_image_ref goes up once, each net-shape group is one eager
+        forward (the letterbox launch reads its images through the table) and one NMS sequence; results in the caller's order."""
+        from ..mixed_batch import MixedBatch
+        mb = MixedBatch(imgs, self.transform, self.device, self._stage)
+        out = [None] * mb.B
+        for k, ((out_h, out_w), members) in enumerate(mb.groups):
+            prog = self.program(out_h, out_w)
+            engine.set_letterbox_images(prog)
+            pred = prog.run(mb.group_table(k))
+            dets = non_max_suppression(pred, multi_label=True, iou_thresh=self.iou_thresh, conf_thresh=self.conf_thresh, merge=True)
+            for i, box in zip(members, dets):
+                out[i] = self._finish([box], mb.geoms[i])[0]
+        return out

@@ -321,6 +321,12 @@ class Program:
             if not g:
                 raise ValueError("letterbox: set the source geometry first (engine.set_letterbox)")
             H, W, _ = self.shapes[op.dst]
+            if g.get("images"):                    # the input is a table of sp_image_ref, one per image (set_letterbox_images)
+                table = bufs[op.src]
+                if table.dtype != torch.uint8 or tuple(table.shape) != (B, ctypes.sizeof(_lib.ImageRef)) or not table.is_contiguous():
+                    raise ValueError(f"letterbox: expected a contiguous uint8 [{B}, {ctypes.sizeof(_lib.ImageRef)}] table of sp_image_ref")
+                _lib.check(lib.sp_yolo_letterbox_images(P(table), B, 2 * H, 2 * W, _lib.SP_LETTERBOX_FOCUS, P(bufs[op.dst]), stream), op.name)
+                return
             _lib.check(lib.sp_yolo_letterbox(P(bufs[op.src]), B, g["src_h"], g["src_w"], g["new_h"], g["new_w"], g["top"], g["left"], 2 * H, 2 * W,
                                              _lib.SP_LETTERBOX_FOCUS, P(bufs[op.dst]), stream), op.name)
         elif op.kind == "focus_nchw":
@@ -1506,6 +1512,20 @@ def set_letterbox(prog: Program, src_h: int, src_w: int, new_h: int, new_w: int,
         raise ValueError(f"letterbox {src_h}x{src_w} -> {new_h}x{new_w} at ({top}, {left}) does not fit {H}x{W}")
     for op in prog.ops:
         if op.kind == "letterbox":
+            op.args[0].clear()
             op.args[0].update(src_h=src_h, src_w=src_w, new_h=new_h, new_w=new_w, top=top, left=left)
+            return
+    raise ValueError("program has no letterbox launch (source='u8')")
+
+
+def set_letterbox_images(prog: Program) -> None:
+    """The other source form of a yolov5_program(source="u8"): the next run's input is a table of `sp_image_ref` (_lib.ImageRef) in device
+    memory, a contiguous uint8 tensor [B, sizeof(sp_image_ref)], instead of a dense image block.  Every image has its own source pointer,
+    size, resize target and placement (sp_yolo_letterbox_images); the canvas is the program's.  The caller guarantees what the table holds
+    (valid pointers, placements inside the canvas) and keeps the images alive until the run has finished.  set_letterbox switches back."""
+    for op in prog.ops:
+        if op.kind == "letterbox":
+            op.args[0].clear()
+            op.args[0].update(images=True)
             return
     raise ValueError("program has no letterbox launch (source='u8')")

@@ -3,6 +3,8 @@
     est = TopDownPoseEstimator(detector, pose_model, decoder=GaussTaylorKeyPointDecoder(), capacity=32)
     res = est.estimate(img)                       # uint8 BGR [H,W,3], numpy or CUDA -> PoseResult
     res = est.estimate_batch(imgs)                # same-sized batch [B,H,W,3] -> list of PoseResult
+    res = est.estimate_batch([img_a, img_b, ...]) # differently sized images (numpy or CUDA) -> list of PoseResult, caller's order
+    res = est.estimate_files(jpeg_files)          # JpegDecoder.decode, then that batch on the decoder's device tensors
     res = est.estimate_boxes(imgs, det, counts)   # caller-supplied detections (the reference's predicts_by_pred path)
 
 The reference runs the three stages as three offline scripts joined by JSON files (eval.py: gen_data_by_detector, predicts_by_pred,
@@ -18,10 +20,16 @@ With `renderer=PoseRenderer(...)` (visualize.py) the kept poses are drawn into a
 launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched.
 With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer, the source - is encoded to a baseline JPEG file
 after the frame on the same stream (sp_jpeg_encode_batch, outside the graph: it uploads its descriptors), and `PoseResult.jpeg` holds the
-file's bytes; without one nothing is allocated or launched."""
+file's bytes; without one nothing is allocated or launched.
+A list of differently sized images is one call too (mixed_batch.py): the images are grouped by letterboxed net shape, each group is one
+detector forward whose letterbox launch reads every image's own geometry from a table of sp_image_ref in device memory
+(sp_yolo_letterbox_images), sp_yolo_boxes_to_source_images scatters the groups' detections into the caller's order, and from
+sp_topdown_plan on there is one of everything for the whole batch, the crops by sp_warp_affine_plan_images_u8c3.  Eager: the table upload
+is not capturable."""
 from __future__ import annotations
 
 import ctypes
+import os
 from dataclasses import dataclass
 from typing import Dict, List, Sequence, Union
 
@@ -31,7 +39,8 @@ import torch
 from . import _lib, engine
 from ._lib import HipLibraryError
 from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
-from .datasets.jpeg import JpegEncoder
+from .datasets.jpeg import JpegDecoder, JpegEncoder
+from .mixed_batch import MixedBatch, check_det_counts, check_images
 from .visualize import PoseRenderer
 
 P = _lib.ptr
@@ -172,6 +181,9 @@ class TopDownPoseEstimator(object):
         self.device = detector.device
         self.use_graph = True
         self._frames: Dict[tuple, _Frame] = {}
+        self._stage: dict = {}           # differently sized images: the pinned staging buffer and the device arena (mixed_batch.MixedBatch)
+        self._force_mixed = False        # tests: send same-sized lists down the mixed path too
+        self._jpeg_decoder = None        # estimate_files' own decoder, made on first use
 
     # -- programs and buffers ---------------------------------------------------------------------------------------------------------
     def _pose_program(self) -> engine.Program:
@@ -265,8 +277,9 @@ class TopDownPoseEstimator(object):
                                                float(g["ratio"]), stream), "sp_yolo_boxes_to_source")
         fr.ws = ws                                   # (a captured graph holds its pointer)
 
-    def _poses(self, fr: _Frame, pose_prog, single_stream: bool) -> None:
-        """plan -> crops -> pose forward -> decode -> rescore -> OKS-NMS over the frame's `det` / `counts`."""
+    def _poses(self, fr: _Frame, pose_prog, single_stream: bool, images: torch.Tensor = None) -> None:
+        """plan -> crops -> pose forward -> decode -> rescore -> OKS-NMS over the frame's `det` / `counts`.  `images`: the table of
+        sp_image_ref of a batch of differently sized images, in the caller's order (the crops then come from it instead of `fr.src`)."""
         lib, cap = _lib.lib(), self.capacity
         stream = _lib.current_stream(self.device)
         iw, ih = self.input_shape
@@ -275,8 +288,12 @@ class TopDownPoseEstimator(object):
         _lib.check(lib.sp_topdown_plan(P(fr.det), P(fr.counts), fr.B, fr.max_det, self.person_cls, self.min_box_score, cap, iw, ih, ow, oh,
                                        P(fr.seg), P(fr.src_index), P(fr.m_inv), P(fr.trans_inv), P(fr.center), P(fr.scale), P(fr.area),
                                        P(fr.box_score), P(fr.box), P(fr.dropped), stream), "sp_topdown_plan")
-        _lib.check(lib.sp_warp_affine_plan_u8c3(P(fr.src), fr.B, fr.H, fr.W, P(fr.m_inv), P(fr.src_index), P(fr.seg), cap, P(fr.crops), ih, iw,
-                                                stream), "sp_warp_affine_plan_u8c3")
+        if images is None:
+            _lib.check(lib.sp_warp_affine_plan_u8c3(P(fr.src), fr.B, fr.H, fr.W, P(fr.m_inv), P(fr.src_index), P(fr.seg), cap, P(fr.crops), ih, iw,
+                                                    stream), "sp_warp_affine_plan_u8c3")
+        else:
+            _lib.check(lib.sp_warp_affine_plan_images_u8c3(P(images), fr.B, P(fr.m_inv), P(fr.src_index), P(fr.seg), cap, P(fr.crops), ih, iw,
+                                                           stream), "sp_warp_affine_plan_images_u8c3")
         if self.flip_test:
             half = fr.crops[:cap]
             _lib.check(lib.sp_mirror_w(P(half), P(fr.crops[cap:]), cap * ih, iw, 3, stream), "sp_mirror_w")     # dead slots: zeros mirror to zeros
@@ -367,20 +384,120 @@ class TopDownPoseEstimator(object):
         img = self._shape_of(img, batched=False)
         return self._run(img[None], self.use_graph)[0]
 
+    # -- differently sized images ---------------------------------------------------------------------------------------------------------
+    def _is_mixed(self, imgs) -> bool:
+        """A list whose images differ in size (or any list, with the tests' private switch); an empty list fails in check_images."""
+        if not isinstance(imgs, (list, tuple)):
+            return False
+        return self._force_mixed or len({tuple(np.shape(i)) for i in imgs}) != 1
+
+    def _mixed_frame(self, mb: MixedBatch, max_det: int, J: int) -> _Frame:
+        """The frame of a mixed batch: keyed without a source shape (H = W = 0: no dense source block); `src` is the call's list of images
+        and `canvas` a list of per-image canvases, which _render, the encoder and _results index like the dense blocks."""
+        fr = self._frame(mb.B, 0, 0, max_det, J)
+        fr.src = mb.srcs
+        if self.renderer is not None:
+            fr.canvas = [torch.empty_like(s) for s in mb.srcs]
+        return fr
+
+    def _detect_mixed(self, fr: _Frame, mb: MixedBatch) -> None:
+        """_detect per net-shape group: letterbox (through the table) + network + head decode, NMS on the device, then the un-letterbox
+        with every image's own offsets, which also scatters the group's rows into the frame's `det` / `counts` / `status` in caller order."""
+        lib, d = _lib.lib(), self.detector
+        from .detector.yolov5_detector import _workspace
+        stream = _lib.current_stream(self.device)
+        for k, ((out_h, out_w), members) in enumerate(mb.groups):
+            prog = d.program(out_h, out_w)
+            engine.set_letterbox_images(prog)
+            table = mb.group_table(k)
+            pred = _run_program(prog, table, False)
+            n, N, no = pred.shape
+            ws = _workspace(n, pred.device)
+            det = torch.empty((n, fr.max_det, 6), dtype=torch.float32, device=pred.device)
+            cnt = torch.empty((2, n), dtype=torch.int32, device=pred.device)     # counts, status
+            _lib.check(lib.sp_yolo_nms_device(P(pred), n, N, no, float(d.conf_thresh), float(d.iou_thresh), 1, 1, 0, fr.max_det, P(ws), ws.numel(),
+                                              P(det), P(cnt[0]), P(cnt[1]), stream), "sp_yolo_nms_device")
+            _lib.check(lib.sp_yolo_boxes_to_source_images(P(det), P(cnt[0]), P(cnt[1]), P(table), n, fr.max_det, float(out_h), float(out_w),
+                                                          P(fr.det), P(fr.counts), P(fr.status), stream), "sp_yolo_boxes_to_source_images")
+
+    def _run_mixed(self, imgs, det=None, counts=None) -> List[PoseResult]:
+        """estimate_batch / estimate_boxes on a list of differently sized images.  Eager: the table upload is not capturable."""
+        n = len(check_images(imgs))                  # every check before the first launch
+        M = self.MAX_DET if det is None else check_det_counts(n, det, counts)
+        if getattr(self.detector, "transform", None) is None:
+            # without the detector's letterbox the images cannot be grouped by net shape: the dense path's rule is all that is left
+            raise ValueError("the images of one batch share one size (differently sized images are grouped by the detector's letterbox, "
+                             "detector.transform, which this detector does not have)")
+        if det is not None:
+            det, cnt = self._det_counts(n, det, counts)
+        pose_prog = self._pose_program()
+        mb = MixedBatch(imgs, self.detector.transform, self.device, self._stage)
+        fr = self._mixed_frame(mb, M, pose_prog.out_shape[0])
+        if det is None:
+            self._detect_mixed(fr, mb)
+        else:
+            fr.det.copy_(det)
+            fr.counts.copy_(cnt)
+            fr.status.zero_()
+        self._poses(fr, pose_prog, False, mb.caller_table)
+        self._render(fr, pose_prog.out_shape[0])
+        return self._results(fr, detected=det is None)         # `mb` holds the caller's CUDA images until this fetch
+
     @torch.no_grad()
     def estimate_batch(self, imgs: Union[torch.Tensor, np.ndarray, Sequence]) -> List[PoseResult]:
-        """A batch of same-sized images ([B, H, W, 3], or a list of [H, W, 3]) -> one PoseResult per image.  One forward of the detector
-        on B images, one pose forward on the `capacity` slots the images share."""
+        """A batch of images -> one PoseResult per image, in the caller's order.  Same-sized ([B, H, W, 3], or a list of [H, W, 3]): one
+        forward of the detector on B images.  A list of differently sized images (numpy or CUDA): one detector forward per letterboxed net
+        shape, every image letterboxed as `estimate` letterboxes it alone.  Either way one pose forward on the `capacity` slots the images
+        share and one device-to-host transfer."""
+        if self._is_mixed(imgs):
+            return self._run_mixed(imgs)
         return self._run(self._shape_of(imgs, batched=True), False)
+
+    @torch.no_grad()
+    def estimate_files(self, files, decoder=None) -> List[PoseResult]:
+        """JPEG files (paths or bytes, of any sizes) -> one PoseResult per file: `JpegDecoder.decode`, then the batch on the decoder's device
+        tensors; nothing goes through the host in between.  `decoder`: a datasets.jpeg.JpegDecoder (default: one on this device, kept)."""
+        if decoder is None:
+            if self._jpeg_decoder is None:
+                self._jpeg_decoder = JpegDecoder(device=self.device)
+            decoder = self._jpeg_decoder
+        if not isinstance(decoder, JpegDecoder):
+            raise TypeError(f"decoder: expected a simple_pose_amd.datasets.jpeg.JpegDecoder or None, got {type(decoder).__name__}")
+        if not isinstance(files, (list, tuple)) or len(files) == 0:
+            raise ValueError("estimate_files takes a non-empty list of JPEG files")
+        datas = []
+        for f in files:
+            if isinstance(f, (str, os.PathLike)):
+                with open(f, "rb") as fh:
+                    f = fh.read()
+            datas.append(f)
+        return self.estimate_batch(list(decoder.decode(datas)))
 
     @torch.no_grad()
     def estimate_boxes(self, imgs, det, counts=None) -> List[PoseResult]:
         """Caller-supplied detections instead of the detector (the reference's predicts_by_pred path): imgs [B, H, W, 3] (or one image
         [H, W, 3]), det fp32 [B, M, 6] (or [M, 6]) rows (x1, y1, x2, y2, score, cls) in source pixels, counts int [B] valid rows per image
-        (default: all M).  Selection (`person_cls`, `min_box_score`, `capacity`) applies as in `estimate`."""
+        (default: all M).  Selection (`person_cls`, `min_box_score`, `capacity`) applies as in `estimate`.  A list of differently sized
+        images is taken as in `estimate_batch`, with det [B, M, 6] / counts [B] in the list's order."""
+        if self._is_mixed(imgs):
+            return self._run_mixed(imgs, det, counts)
         single = len(getattr(imgs, "shape", ())) == 3
         imgs = self._shape_of(imgs[None] if single else imgs, batched=True)
         B, H, W = imgs.shape[0], imgs.shape[1], imgs.shape[2]
+        det, cnt = self._det_counts(B, det, counts)
+        M = det.shape[1]
+        pose_prog = self._pose_program()
+        fr = self._frame(B, H, W, M, pose_prog.out_shape[0])
+        self._load(fr, imgs)
+        fr.det.copy_(det)
+        fr.counts.copy_(cnt)
+        fr.status.zero_()
+        self._poses(fr, pose_prog, False)
+        self._render(fr, pose_prog.out_shape[0])
+        return self._results(fr)
+
+    def _det_counts(self, B: int, det, counts):
+        """Caller-supplied detections of B images -> (det fp32 [B, M, 6], counts int32 [B]) on the device."""
         if isinstance(det, np.ndarray):
             det = torch.from_numpy(np.ascontiguousarray(det, dtype=np.float32)).to(self.device)
         if not (isinstance(det, torch.Tensor) and det.is_cuda and det.dtype == torch.float32):
@@ -398,12 +515,4 @@ class TopDownPoseEstimator(object):
             cnt = torch.from_numpy(np.ascontiguousarray(np.asarray(counts, dtype=np.int32).reshape(-1))).to(self.device)
         if cnt.numel() != B:
             raise ValueError(f"counts: expected {B} values")
-        pose_prog = self._pose_program()
-        fr = self._frame(B, H, W, M, pose_prog.out_shape[0])
-        self._load(fr, imgs)
-        fr.det.copy_(det)
-        fr.counts.copy_(cnt)
-        fr.status.zero_()
-        self._poses(fr, pose_prog, False)
-        self._render(fr, pose_prog.out_shape[0])
-        return self._results(fr)
+        return det, cnt

@@ -18,6 +18,11 @@ is kept as profiles/pipeline_kernel_stats.csv.  The pose models run with tile ti
 the off / graphed frame a second time: the measurement's own spread), plus the two kernels it adds (sp_mirror_w on 32 crops,
 sp_heat_map_flip_merge on 32 x 17 heat maps) timed with device events over back-to-back launches.  The result is merged into --out under
 the key "flip_test"; the other keys of the file stay.
+
+--mixed measures a set of differently sized images instead (mixed_bench below): `estimate` one by one against `estimate_batch` on lists of
+8 and 32, in images per second, into profiles/pipeline_mixed_bench.json under "mixed".  --mixed-baseline runs the one-by-one variants only
+and writes them under "baseline_one_by_one": that half uses nothing newer than `estimate`, so the same file can be run from the tree of an
+older commit to measure it there on the same box.
 """
 from __future__ import annotations
 
@@ -147,15 +152,113 @@ def flip_test_bench(args, det, img, decoder):
         print("wrote", args.out)
 
 
+MIXED_SIZES = ((480, 640), (427, 640), (640, 480), (375, 500), (640, 427), (500, 375))     # COCO's common sizes: four detector net shapes
+MIXED_IMAGES = 32
+
+
+def git_commit():
+    import subprocess
+    try:
+        return subprocess.run(["git", "-C", ROOT, "rev-parse", "--short", "HEAD"], capture_output=True, text=True, check=True).stdout.strip()
+    except Exception:
+        return None
+
+
+def mixed_bench(args, det, decoder):
+    """Images per second over a seeded set of MIXED_IMAGES differently sized images, fp32 DConv, capacity 32 per 8 images:
+      one_by_one_graph / one_by_one_eager   `estimate` per image (existing code: with --mixed-baseline only these run, so that the same
+                                            file measures them on an older commit)
+      batch8 / batch32                      `estimate_batch` on lists of 8 (capacity 32) and of all 32 (capacity 128)
+    Every variant sees the same `min_box_score`, chosen from the detector's own scores so that the set holds about four persons per image;
+    `persons` / `dropped` per variant are recorded.  `stages_ms` splits one list of 8 with a device synchronise after every stage (a
+    diagnostic: the synchronisations are not in the timed calls)."""
+    rng = np.random.default_rng(7)
+    order = rng.integers(0, len(MIXED_SIZES), MIXED_IMAGES)
+    order[:len(MIXED_SIZES)] = np.arange(len(MIXED_SIZES))                       # every size occurs
+    imgs = [rng.integers(0, 256, MIXED_SIZES[k] + (3,), dtype=np.uint8) for k in order]
+    nets = sorted({(g["out_h"], g["out_w"]) for g in (det.transform.geometry(*i.shape[:2]) for i in imgs)})
+    assert len(nets) >= 3
+    scores = np.sort(np.concatenate([(f[f[:, 5] == 0][:, 4].cpu().numpy() if not isinstance(f, list) else np.zeros(0, np.float32))
+                                     for f in (det.single_predict(i) for i in imgs)]))[::-1]
+    want = 4 * MIXED_IMAGES
+    min_score = 0.0 if scores.size <= want else float((np.float64(scores[want - 1]) + np.float64(scores[want])) / 2)
+    reps, warm = (3, 1) if args.quick else (10, 2)
+    model = pose_model("dconv", "fp32")
+    mk = lambda cap: TopDownPoseEstimator(det, model, decoder=decoder, capacity=cap, min_box_score=min_score)
+    single, e8, e32 = mk(CAPACITY), mk(CAPACITY), mk(4 * CAPACITY)
+
+    def one_by_one(graph):
+        single.use_graph = graph
+        return [single.estimate(i) for i in imgs]
+
+    variants = {"one_by_one_graph": lambda: one_by_one(True), "one_by_one_eager": lambda: one_by_one(False)}
+    if not args.mixed_baseline:
+        variants["batch8"] = lambda: [r for k in range(0, MIXED_IMAGES, 8) for r in e8.estimate_batch(imgs[k:k + 8])]
+        variants["batch32"] = lambda: e32.estimate_batch(imgs)
+        variants["one_by_one_graph2"] = variants["one_by_one_graph"]             # again: the measurement's own spread
+    first = {k: fn() for k, fn in variants.items()}
+    times = {k: [] for k in variants}
+    for r in range(warm + reps):
+        for k, fn in variants.items():
+            t = wall_ms(fn)
+            if r >= warm:
+                times[k].append(t)
+    res = {"device": torch.cuda.get_device_name(0), "commit": args.commit or git_commit(), "images": MIXED_IMAGES, "sizes": [list(s) for s in MIXED_SIZES],
+           "net_shapes": [list(s) for s in nets], "detector": "s fp32", "pose": "resnet50-dconv fp32", "pose_autotune": False,
+           "capacity_per_8_images": CAPACITY, "min_box_score": min_score, "reps": reps, "variants": {}}
+    for k, ts in times.items():
+        s = summary(ts)
+        s.update(images_per_s=MIXED_IMAGES / (s["median_ms"] * 1e-3), ms_per_image=s["median_ms"] / MIXED_IMAGES,
+                 persons=int(sum(len(r) for r in first[k])), dropped=int(sum(r.dropped for r in first[k])))
+        res["variants"][k] = s
+    if not args.mixed_baseline:
+        from simple_pose_amd.mixed_batch import MixedBatch
+        stages = {"upload": [], "detect": [], "poses": [], "fetch": []}
+        for _ in range(reps):
+            lst, t = imgs[:8], {}
+            pose_prog = e8._pose_program()
+            box = {}
+            t["upload"] = wall_ms(lambda: box.update(mb=MixedBatch(lst, det.transform, e8.device, e8._stage)))
+            fr = e8._mixed_frame(box["mb"], e8.MAX_DET, pose_prog.out_shape[0])
+            t["detect"] = wall_ms(lambda: e8._detect_mixed(fr, box["mb"]))
+            t["poses"] = wall_ms(lambda: e8._poses(fr, pose_prog, False, box["mb"].caller_table))
+            t["fetch"] = wall_ms(lambda: e8._results(fr))
+            for k, v in t.items():
+                stages[k].append(v)
+        res["stages_ms_list_of_8"] = {k: float(np.median(v)) for k, v in stages.items()}
+        res["stages_ms_list_of_8"]["detector_groups"] = len(MixedBatch(imgs[:8], det.transform, e8.device, e8._stage).groups)
+        v = res["variants"]
+        res["batch8_over_one_by_one_graph"] = v["batch8"]["images_per_s"] / v["one_by_one_graph"]["images_per_s"]
+        res["batch32_over_one_by_one_graph"] = v["batch32"]["images_per_s"] / v["one_by_one_graph"]["images_per_s"]
+    print(json.dumps(res), flush=True)
+    doc = {}
+    if os.path.isfile(args.out):
+        with open(args.out) as fh:
+            doc = json.load(fh)
+    doc["baseline_one_by_one" if args.mixed_baseline else "mixed"] = res
+    with open(args.out, "w") as fh:
+        json.dump(doc, fh, indent=1)
+    print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "pipeline_bench.json"))
+    ap.add_argument("--mixed", action="store_true", help="a seeded set of differently sized images: estimate one by one vs estimate_batch on "
+                    "lists of 8 and 32 (default --out: profiles/pipeline_mixed_bench.json)")
+    ap.add_argument("--mixed-baseline", action="store_true", help="--mixed, the one-by-one variants only (runs on commits without mixed batches)")
+    ap.add_argument("--commit", default=None, help="the commit to record with --mixed (default: git rev-parse of this tree)")
+    ap.add_argument("--out", default=None)
     ap.add_argument("--quick", action="store_true", help="DConv fp32 at n = 32 only, few repetitions (the kernel-trace run)")
     ap.add_argument("--flip-test", action="store_true", help="the frame at 32 persons with the flip test off / on, and its two kernels")
     args = ap.parse_args()
+    args.mixed = args.mixed or args.mixed_baseline
+    if args.out is None:
+        args.out = os.path.join(ROOT, "profiles", "pipeline_mixed_bench.json" if args.mixed else "pipeline_bench.json")
     reps, warm = (5, 2) if args.quick else (40, 5)
     det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
     det.conf_thresh, det.iou_thresh = 0.02, 0.45
+    if args.mixed:
+        return mixed_bench(args, det, GaussTaylorKeyPointDecoder())
     img = np.random.default_rng(0).integers(0, 256, (640, 640, 3), dtype=np.uint8)
     dev_img = torch.from_numpy(img).to(DEV)
     found = det.single_predict(img)
