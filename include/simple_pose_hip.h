@@ -832,6 +832,38 @@ int sp_track_associate(const double* kps, const double* area, const float* box, 
  * [0, img_w] x [0, img_h] (a NaN edge becomes 0).  One launch of one workgroup. */
 int sp_track_boxes(const int32_t* t_id, const int32_t* t_miss, const double* t_kps, const float* t_conf, int slots, int joints,
                    float in_vis_thre, float box_expand, float cls, int img_w, int img_h, int max_det, float* det, int32_t* counts, void* stream);
+/* Temporal smoothing of the tracked key points: the One-Euro filter (Casiez, Roussel, Vogel, CHI 2012) per track and joint, after
+ * sp_track_associate and before the overlay.  (No new ABI version: an addition.)  It reads what sp_track_associate leaves behind for one
+ * image - kps [rows, joints, 3], box fp32 [rows, 5], track_id [rows], keep / keep_count / seg (the count clamped to `slots` and to the keep
+ * list's end as sp_track_associate clamps it), t_id [slots] - and now_dev, ONE double in DEVICE memory: the frame's time in seconds (not an
+ * argument, so that a captured graph can be replayed with another time).  The filter state is DEVICE memory the caller owns between frames,
+ * zero-initialised: s_id int32 [slots] (the track id a slot's filters belong to), s_x double [slots, joints, 2] (filtered position),
+ * s_dx double [slots, joints, 2] (filtered speed, px / s), s_t double [slots, joints] (time of the last accepted sample), s_n int32
+ * [slots, joints] (samples accepted; 0 = uninitialised).
+ *   rows     kps_smooth [rows, joints, 3]: every row is the raw row, except a row the image kept (one of keep[seg[0] .. seg[0] + n)) whose
+ *            track_id > 0 and is found in t_id: its slot is the lowest with t_id[slot] == track_id.  When s_id[slot] != track_id the slot
+ *            was handed to another track: s_n[slot, :] = 0 and s_id[slot] = track_id (s_x, s_dx, s_t stay until a sample replaces them).
+ *            Then every joint goes through the filter.  Tracks not seen in the frame keep their state.  The kept rows of one frame carry
+ *            distinct ids (sp_track_associate's do).
+ *   size     of the row: w = x2 - x1, h = y2 - y1 of its box in fp32, (w > h ? w : h) widened to double, replaced by 1.0 unless > 0:
+ *            speeds are in body sizes per second, so the parameters do not depend on the resolution.
+ *   joint    sample (x, y, c), state x^[2], dx^[2], t_last, n (simple_pose_amd/csrc/sp_smooth.h states it once for the device and the
+ *            host).  fp64, contraction off, in this order, nothing but + - * / fabs and comparisons:
+ *              not usable   c > in_vis_thre is false (a NaN c included), or x or y is not finite: the raw sample, state untouched;
+ *              (re)start    else if n == 0, or now - t_last > 0 is false, or now - t_last > max_gap: x^ = (x, y), dx^ = 0, n = 1,
+ *                           t_last = now, the raw sample;
+ *              update       else Te = now - t_last and per axis  d = (x - x^) / Te;  rd = (TWO_PI * d_cutoff) * Te;  ad = rd / (rd + 1.0);
+ *                           dx^ = ad * d + (1.0 - ad) * dx^;  fc = min_cutoff + beta * (fabs(dx^) / size);  r = (TWO_PI * fc) * Te;
+ *                           a = r / (r + 1.0);  x^ = a * x + (1.0 - a) * x^ unless x == x^ (then x^ stays: the blend of two equal values rounds to
+ *                           them only within an ulp, and a pose at rest comes out exactly unchanged);  then n += 1, t_last = now, and the
+ *                           output is (x^x, x^y, c).
+ *            TWO_PI is the double 6.283185307179586; c is never filtered.
+ * slots 1 .. 256, joints 1 .. 64, rows >= 1; min_cutoff > 0, d_cutoff > 0, beta >= 0, max_gap > 0, all finite, in_vis_thre finite.
+ * One launch (one 64-lane workgroup per row, lane = joint); no copy, no synchronisation, capturable.  Works with zero kept poses. */
+int sp_track_smooth(const double* kps, const float* box, const int32_t* track_id, const int32_t* keep, const int32_t* keep_count,
+                    const int32_t* seg, int rows, int joints, const int32_t* t_id, int slots, const double* now_dev, double min_cutoff,
+                    double beta, double d_cutoff, double max_gap, double in_vis_thre, int32_t* s_id, double* s_x, double* s_dx, double* s_t,
+                    int32_t* s_n, double* kps_smooth, void* stream);
 
 /* ---- overlay: the kept poses of one image drawn into it - boxes, limbs, joints, coloured by person (track id) or by part ------------------
  * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] in and out, 1 <= h, w <= 16384; it reads exactly what sp_oks_nms (and

@@ -4,8 +4,11 @@
 // rules are restated for the CPU in tests/track_ref.py.
 // Similarity: oks_iou of the track's last pose and the candidate pose - sp_oks.h's oks_one, the function nms.hip calls - fp64,
 // contraction OFF for the whole file.  The track state (slots <= 256) lives in device memory the caller owns between frames.
+// sp_track_smooth: the One-Euro filter per track and joint on the frame's kept poses (the rules in sp_smooth.h, restated for the CPU in
+// tests/smooth_ref.py); its state lives next to the tracks', keyed by slot.
 #include "sp_common.h"
 #include "sp_oks.h"
+#include "sp_smooth.h"
 
 #include <stdint.h>
 
@@ -224,6 +227,61 @@ __global__ __launch_bounds__(TRK_NT) void track_boxes_kernel(const TrackState st
     if (tid == 0) counts[0] = total;
 }
 
+constexpr int SMOOTH_NT = 64;
+
+struct SmoothState {
+    int* id;                                     // [slots] the track id the slot's filters belong to
+    double* x;                                   // [slots, J, 2] filtered position
+    double* dx;                                  // [slots, J, 2] filtered speed
+    double* t;                                   // [slots, J] time of the last accepted sample
+    int* n;                                      // [slots, J] samples accepted, 0 = uninitialised
+};
+
+// One 64-lane workgroup per row, lane = joint.  The row is copied; when the image kept it and it has a track id, the workgroup finds the
+// id's slot (lowest slot with t_id == id), takes the slot over when its filters belonged to another id, and every lane filters its joint.
+// Rows of one frame carry distinct ids (sp_track_associate), so no two workgroups share a slot.  44 B of state per joint in and out.
+__global__ __launch_bounds__(SMOOTH_NT) void track_smooth_kernel(const FramePoses f, const int* __restrict__ track_id, const int* __restrict__ t_id,
+                                                                 int slots, int J, const double* __restrict__ now_dev, const sp_smooth_params prm,
+                                                                 const SmoothState st, double* __restrict__ out) {
+    const int row = blockIdx.x, lane = threadIdx.x;
+    const double* src = f.kps + (size_t)row * J * 3;
+    double* dst = out + (size_t)row * J * 3;
+    int lo;
+    const int n = frame_poses(f, slots, lo);
+    int kept = 0;
+    for (int p = lane; p < n; p += SMOOTH_NT) kept |= f.keep[lo + p] == row ? 1 : 0;
+    const int id = track_id[row];
+    int slot = TRK_MAX_SLOTS;
+    for (int t = lane; t < slots; t += SMOOTH_NT)
+        if (t_id[t] == id && t < slot) slot = t;
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        kept |= __shfl_xor(kept, off, 64);
+        const int os = __shfl_xor(slot, off, 64);
+        slot = os < slot ? os : slot;
+    }
+    if (!kept || id <= 0 || slot >= slots) {       // uniform: the raw row
+        for (int i = lane; i < J * 3; i += SMOOTH_NT) dst[i] = src[i];
+        return;
+    }
+    const bool fresh = st.id[slot] != id;
+    __syncthreads();                               // every lane has read the slot's owner
+    if (fresh && lane == 0) st.id[slot] = id;
+    if (lane >= J) return;
+    const size_t sj = (size_t)slot * J + lane;
+    double xh[2] = {st.x[sj * 2], st.x[sj * 2 + 1]}, dxh[2] = {st.dx[sj * 2], st.dx[sj * 2 + 1]}, tl = st.t[sj], o[3];
+    int nj = fresh ? 0 : st.n[sj];
+    const bool accepted = sp_smooth_joint(prm, src[lane * 3], src[lane * 3 + 1], src[lane * 3 + 2], now_dev[0],
+                                          sp_smooth_size(f.box + (size_t)row * 5), xh, dxh, &tl, &nj, o);
+    dst[lane * 3] = o[0]; dst[lane * 3 + 1] = o[1]; dst[lane * 3 + 2] = o[2];
+    if (accepted) {
+        st.x[sj * 2] = xh[0]; st.x[sj * 2 + 1] = xh[1];
+        st.dx[sj * 2] = dxh[0]; st.dx[sj * 2 + 1] = dxh[1];
+        st.t[sj] = tl;
+    }
+    if (accepted || fresh) st.n[sj] = nj;
+}
+
 }  // namespace
 
 extern "C" int sp_track_associate(const double* kps, const double* area, const float* box, const int32_t* keep, const int32_t* keep_count,
@@ -264,4 +322,28 @@ extern "C" int sp_track_boxes(const int32_t* t_id, const int32_t* t_miss, const 
     hipLaunchKernelGGL(track_boxes_kernel, dim3(1), dim3(TRK_NT), 0, (hipStream_t)stream, st, slots, joints, in_vis_thre, box_expand, cls,
                        (float)img_w, (float)img_h, det, counts);
     return sp_check_launch("track_boxes_kernel");
+}
+
+static bool smooth_finite(double v) { return v - v == 0.0; }
+
+extern "C" int sp_track_smooth(const double* kps, const float* box, const int32_t* track_id, const int32_t* keep, const int32_t* keep_count,
+                               const int32_t* seg, int rows, int joints, const int32_t* t_id, int slots, const double* now_dev, double min_cutoff,
+                               double beta, double d_cutoff, double max_gap, double in_vis_thre, int32_t* s_id, double* s_x, double* s_dx,
+                               double* s_t, int32_t* s_n, double* kps_smooth, void* stream) {
+    SP_REQUIRE(kps && box && track_id && keep && keep_count && seg && t_id && now_dev && s_id && s_x && s_dx && s_t && s_n && kps_smooth,
+               "sp_track_smooth: null pointer");
+    SP_REQUIRE(slots >= 1 && slots <= TRK_MAX_SLOTS, "sp_track_smooth: slots %d (1..%d)", slots, TRK_MAX_SLOTS);
+    SP_REQUIRE(joints >= 1 && joints <= SMOOTH_NT, "sp_track_smooth: joints %d (1..%d)", joints, SMOOTH_NT);
+    SP_REQUIRE(rows >= 1, "sp_track_smooth: rows %d", rows);
+    SP_REQUIRE(smooth_finite(min_cutoff) && min_cutoff > 0.0, "sp_track_smooth: min_cutoff %g (finite, > 0)", min_cutoff);
+    SP_REQUIRE(smooth_finite(beta) && beta >= 0.0, "sp_track_smooth: beta %g (finite, >= 0)", beta);
+    SP_REQUIRE(smooth_finite(d_cutoff) && d_cutoff > 0.0, "sp_track_smooth: d_cutoff %g (finite, > 0)", d_cutoff);
+    SP_REQUIRE(smooth_finite(max_gap) && max_gap > 0.0, "sp_track_smooth: max_gap %g (finite, > 0)", max_gap);
+    SP_REQUIRE(smooth_finite(in_vis_thre), "sp_track_smooth: in_vis_thre %g (finite)", in_vis_thre);
+    const FramePoses f = {kps, nullptr, box, keep, keep_count, seg, rows};
+    const sp_smooth_params prm = {min_cutoff, beta, d_cutoff, max_gap, in_vis_thre};
+    const SmoothState st = {s_id, s_x, s_dx, s_t, s_n};
+    hipLaunchKernelGGL(track_smooth_kernel, dim3(rows), dim3(SMOOTH_NT), 0, (hipStream_t)stream, f, track_id, t_id, slots, joints, now_dev, prm, st,
+                       kps_smooth);
+    return sp_check_launch("track_smooth_kernel");
 }

@@ -59,6 +59,8 @@ class PoseResult:
                                      # frame's canvas, valid until the next call with the same source shape - .clone() it to keep it
     jpeg: bytes = None               # the frame (the canvas, or the source without a renderer) as a baseline JPEG file (estimators with an
                                      # `encoder` only)
+    keypoints_smooth: np.ndarray = None     # float64 [n, J, 3]: `keypoints` through the tracker's One-Euro filter, c unfiltered
+                                     # (tracking.PoseTracker(smooth=...).update only)
 
     def __len__(self) -> int:
         return int(self.score.shape[0])
@@ -85,7 +87,7 @@ class _Frame:
     """The device buffers of one (batch, source shape, max_det): the static source, the plan, the crops, and ONE packed result buffer
     whose slices the kernels write directly, so that a call ends in a single device-to-host copy."""
 
-    def __init__(self, B: int, H: int, W: int, max_det: int, cap: int, J: int, in_hw, device, flip_test: bool = False):
+    def __init__(self, B: int, H: int, W: int, max_det: int, cap: int, J: int, in_hw, device, flip_test: bool = False, smooth: bool = False):
         self.B, self.H, self.W, self.max_det = B, H, W, max_det
         z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=device)
         self.src = z((B, H, W, 3), torch.uint8)
@@ -100,6 +102,8 @@ class _Frame:
                   ("keep", (cap,), torch.int32), ("keep_count", (B,), torch.int32), ("seg", (B + 1,), torch.int32),
                   ("status", (B,), torch.int32), ("dropped", (B,), torch.int32), ("counts", (B,), torch.int32),
                   ("track_id", (cap,), torch.int32))             # written by tracking.PoseTracker's frames only
+        if smooth:                                               # the frames of a tracker that smooths: sp_track_smooth's output rides along
+            fields += (("kps_smooth", (cap, J, 3), torch.float64),)
         self.layout, off = {}, 0
         for name, shape, dt in fields:
             nbytes = int(np.prod(shape)) * torch.empty((), dtype=dt).element_size()
@@ -204,13 +208,13 @@ class TopDownPoseEstimator(object):
         """Crops per run of the pose program: the slots, and with the flip test their mirrors."""
         return 2 * self.capacity if self.flip_test else self.capacity
 
-    def _frame(self, B: int, H: int, W: int, max_det: int, J: int) -> _Frame:
-        key = (B, H, W, max_det, J, self.flip_test)
+    def _frame(self, B: int, H: int, W: int, max_det: int, J: int, smooth: bool = False) -> _Frame:
+        key = (B, H, W, max_det, J, self.flip_test) + ((True,) if smooth else ())
         fr = self._frames.get(key)
         if fr is None:
             if len(self._frames) >= self.MAX_GRAPHS:
                 self._frames.pop(next(iter(self._frames)))
-            fr = _Frame(B, H, W, max_det, self.capacity, J, (self.input_shape[1], self.input_shape[0]), self.device, self.flip_test)
+            fr = _Frame(B, H, W, max_det, self.capacity, J, (self.input_shape[1], self.input_shape[0]), self.device, self.flip_test, smooth)
         else:
             self._frames.pop(key)                # most recently used last
         self._frames[key] = fr
@@ -308,14 +312,15 @@ class TopDownPoseEstimator(object):
         _lib.check(lib.sp_oks_nms(P(fr.kps64), P(fr.score), P(fr.area), P(fr.seg), fr.B, cap, J, None, self.oks_thre, -1.0, P(fr.keep),
                                   P(fr.keep_count), stream), "sp_oks_nms")
 
-    def _render(self, fr: _Frame, J: int, tracked: bool = False) -> None:
+    def _render(self, fr: _Frame, J: int, tracked: bool = False, kps: torch.Tensor = None) -> None:
         """The overlay of every image's kept poses into the frame's canvas: one sp_render_poses_u8c3 (two launches) per image index, reading
-        the buffers sp_oks_nms (and, `tracked`, sp_track_associate) just wrote.  Nothing without a renderer."""
+        the buffers sp_oks_nms (and, `tracked`, sp_track_associate) just wrote; `kps`: the poses to draw instead of the frame's own (a
+        smoothing tracker's kps_smooth).  Nothing without a renderer."""
         if self.renderer is None:
             return
         for b in range(fr.B):
-            self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64, fr.box, fr.track_id if tracked else None, fr.keep, fr.keep_count, fr.seg, b,
-                                 self.capacity, J, fr.render_ws)
+            self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
+                                 fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws)
 
     def _capture(self, fr: _Frame, det_prog, pose_prog) -> None:
         dev = self.device
@@ -353,7 +358,8 @@ class TopDownPoseEstimator(object):
                 raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
             rows = h["keep"][lo:lo + n]
             out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b]),
-                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b], files[b]))
+                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b], files[b],
+                                  h["kps_smooth"][rows] if tracked and "kps_smooth" in h else None))
         return out
 
     # -- public surface -----------------------------------------------------------------------------------------------------------------

@@ -1,8 +1,10 @@
 """Persons across video frames: persistent identities on top of `TopDownPoseEstimator`, and frames that leave the detector out.
 
-    trk = PoseTracker(estimator, slots=None, match_thre=0.5, max_age=30, detect_every=1, box_expand=1.25, sigmas=None)
+    trk = PoseTracker(estimator, slots=None, match_thre=0.5, max_age=30, detect_every=1, box_expand=1.25, sigmas=None, smooth=None)
     res = trk.update(img)      # PoseResult with track_id: int32 [n], aligned with keypoints / score / box
     trk.reset()
+    trk = PoseTracker(estimator, smooth=OneEuro(min_cutoff=1.0, beta=0.5, d_cutoff=1.0, max_gap=0.5, fps=30.0))
+    res = trk.update(img, timestamp=t)     # ... and keypoints_smooth: float64 [n, J, 3], the tracked poses through a One-Euro filter
 
 The association runs on the device, on the estimator's stream, right after sp_oks_nms: sp_track_associate matches the frame's kept poses
 with the tracks by OKS (the similarity OKS-NMS uses, the same device function), greedily, best pair first; unmatched poses start new
@@ -21,7 +23,18 @@ Tracks live in source-image pixels: call reset() when the stream (or its size) c
 are used on.
 
 `match_thre`, `max_age` and `box_expand` are design choices, not tuned values: there are no trained weights in this repository to tune
-them on."""
+them on.
+
+Smoothing (`smooth=OneEuro(...)`, off by default): the poses are decoded frame by frame, so sub-pixel decode noise and the crop changing
+between detector and propagated frames make a standing person's skeleton shiver.  sp_track_smooth, one more launch right after
+sp_track_associate, runs the One-Euro filter (Casiez, Roussel, Vogel, CHI 2012: a low-pass whose cut-off rises with the speed, so slow
+motion is steadied and fast motion is not lagged) per track and joint on the frame's kept poses; its state lives in device memory next to
+the tracks', keyed by slot, and a slot handed to another id starts again.  The frame's time is one double in device memory that the host
+writes before the launch or the replay (never a kernel argument: a captured graph freezes those), `timestamp` in seconds or, without one,
+frame index / fps.  The smoothed poses come back in the same packed buffer (`PoseResult.keypoints_smooth`; the confidences are not filtered)
+and are what the estimator's `renderer` draws, inside the same replay.  `keypoints`, `score`, `box`, `track_id`, the association and the
+propagated boxes keep using the raw poses: they are bit for bit what they are without smoothing.  Speeds are measured in body sizes (the
+box's longer side) per second, so the parameters do not depend on the resolution.  OneEuro's defaults are design choices as well."""
 from __future__ import annotations
 
 import ctypes
@@ -37,17 +50,46 @@ P = _lib.ptr
 MAX_SLOTS = 256                      # one thread per track in the match kernel (sp_track_associate)
 
 
+def _positive(name, v, what, zero_ok=False):
+    if not isinstance(v, (int, float)) or isinstance(v, bool) or not ((0.0 <= float(v) if zero_ok else 0.0 < float(v)) and float(v) < float("inf")):
+        raise ValueError(f"{name}: {what}, got {v!r}")
+    return float(v)
+
+
+class OneEuro(object):
+    """The parameters of the tracker's key-point smoother (sp_track_smooth).  `min_cutoff`: the cut-off frequency at rest, Hz (> 0; lower is
+    steadier and lags more).  `beta`: how fast the cut-off rises with the speed, per body size per second (>= 0; 0 is a fixed low-pass).
+    `d_cutoff`: the cut-off of the speed estimate, Hz (> 0).  `max_gap`: seconds without an accepted sample after which a joint starts again
+    from the raw value (> 0).  `fps`: the frame rate `update` assumes when it gets no timestamp (> 0).  The defaults are design choices, not
+    tuned values: there are no trained weights and no video in this repository to tune them on."""
+
+    def __init__(self, min_cutoff: float = 1.0, beta: float = 0.5, d_cutoff: float = 1.0, max_gap: float = 0.5, fps: float = 30.0):
+        self.min_cutoff = _positive("min_cutoff", min_cutoff, "a frequency > 0 (Hz)")
+        self.beta = _positive("beta", beta, "a finite factor >= 0", zero_ok=True)
+        self.d_cutoff = _positive("d_cutoff", d_cutoff, "a frequency > 0 (Hz)")
+        self.max_gap = _positive("max_gap", max_gap, "a time > 0 (seconds)")
+        self.fps = _positive("fps", fps, "a frame rate > 0")
+
+    def key(self) -> tuple:
+        """Everything sp_track_smooth's launch depends on (a captured graph is reused only while it is unchanged)."""
+        return (self.min_cutoff, self.beta, self.d_cutoff, self.max_gap)
+
+    def __repr__(self) -> str:
+        return f"OneEuro(min_cutoff={self.min_cutoff}, beta={self.beta}, d_cutoff={self.d_cutoff}, max_gap={self.max_gap}, fps={self.fps})"
+
+
 class PoseTracker(object):
     """`estimator`: a TopDownPoseEstimator (its `flip_test`, `use_graph`, thresholds and capacity apply unchanged).  `slots`: tracks kept
     at most (capacity .. 256; default: the estimator's capacity, so that every person of a frame finds a slot).  `match_thre`: the least OKS
     at which a pose continues a track.  `max_age`: frames a track survives without being seen.  `detect_every`: a detector frame every
     that many frames (1: every frame).  `box_expand`: the factor a propagated box grows about its centre, on top of the key points'
-    extent.  `sigmas`: per-joint OKS sigmas (default COCO's 17; required for any other joint count)."""
+    extent.  `sigmas`: per-joint OKS sigmas (default COCO's 17; required for any other joint count).  `smooth`: a `OneEuro`, or None (the
+    default: no filter, no extra launch, buffer or byte copied)."""
 
     MAX_GRAPHS = 8
 
     def __init__(self, estimator, slots=None, match_thre: float = 0.5, max_age: int = 30, detect_every: int = 1, box_expand: float = 1.25,
-                 sigmas=None):
+                 sigmas=None, smooth=None):
         if not isinstance(estimator, TopDownPoseEstimator):
             raise TypeError(f"estimator: expected a TopDownPoseEstimator, got {type(estimator).__name__}")
         if slots is None:
@@ -71,6 +113,11 @@ class PoseTracker(object):
             sigmas = np.asarray(sigmas, np.float64).reshape(-1)
             if sigmas.size < 1 or sigmas.size > 64 or not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
                 raise ValueError("sigmas: expected 1..64 positive per-joint values")
+        if smooth is not None and not isinstance(smooth, OneEuro):
+            raise TypeError(f"smooth: expected a simple_pose_amd.tracking.OneEuro or None, got {type(smooth).__name__}")
+        self.smooth = smooth
+        self.smooth_state: Dict[str, torch.Tensor] = {}  # device tensors: id, x, dx, t, n, now (allocated with the first smoothed frame)
+        self._frame_index = 0                          # frames since construction or reset(): the clock of an update without a timestamp
         self.estimator, self.slots = estimator, slots
         self.match_thre, self.max_age, self.detect_every, self.box_expand = float(match_thre), max_age, detect_every, float(box_expand)
         self.sigmas = sigmas
@@ -86,6 +133,12 @@ class PoseTracker(object):
             raise ValueError(f"sigmas: the default OKS sigmas are COCO's 17; the pose model has {J} joints, pass `sigmas`")
         if self.sigmas is not None and self.sigmas.size != J:
             raise ValueError(f"sigmas: {self.sigmas.size} values for a pose model with {J} joints")
+        if self.smooth is not None and not (self.smooth_state and self.smooth_state["n"].shape[1] == J):
+            dev, n = self.estimator.device, self.slots
+            z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+            self.smooth_state = {"id": z((n,), torch.int32), "x": z((n, J, 2), torch.float64), "dx": z((n, J, 2), torch.float64),
+                                 "t": z((n, J), torch.float64), "n": z((n, J), torch.int32), "now": z((1,), torch.float64)}
+            self._graphs.clear()
         if self.state and self.state["kps"].shape[1] == J:
             return
         dev, n = self.estimator.device, self.slots
@@ -98,10 +151,13 @@ class PoseTracker(object):
         self.reset()
 
     def reset(self) -> None:
-        """Forget every track: the next frame is a detector frame and ids restart at 1."""
+        """Forget every track: the next frame is a detector frame and ids restart at 1; the smoother starts again, and so does the clock
+        of updates without a timestamp."""
         for k, t in self.state.items():
             t.fill_(1) if k == "next_id" else t.zero_()
-        self._since_detect, self._prev_n = 0, 0
+        for t in self.smooth_state.values():
+            t.zero_()
+        self._since_detect, self._prev_n, self._frame_index = 0, 0, 0
 
     def tracks(self) -> Dict[str, np.ndarray]:
         """A host copy of the live tracks (id, age, miss, keypoints, area, conf), in slot order.  For inspection: it synchronises."""
@@ -126,6 +182,14 @@ class PoseTracker(object):
                                                  P(st["kps"]), P(st["area"]), P(st["conf"]), P(st["next_id"]), P(self._sim), P(fr.track_id),
                                                  _lib.current_stream(est.device)), "sp_track_associate")
 
+    def _smooth(self, fr: _Frame, J: int) -> None:
+        """sp_track_smooth on what sp_track_associate just left in the frame; the time is read from smooth_state["now"] by the kernel."""
+        est, sm, ss = self.estimator, self.smooth, self.smooth_state
+        _lib.check(_lib.lib().sp_track_smooth(P(fr.kps64), P(fr.box), P(fr.track_id), P(fr.keep), P(fr.keep_count), P(fr.seg), est.capacity, J,
+                                              P(self.state["id"]), self.slots, P(ss["now"]), sm.min_cutoff, sm.beta, sm.d_cutoff, sm.max_gap,
+                                              est.in_vis_thre, P(ss["id"]), P(ss["x"]), P(ss["dx"]), P(ss["t"]), P(ss["n"]), P(fr.kps_smooth),
+                                              _lib.current_stream(est.device)), "sp_track_smooth")
+
     def _launch(self, fr: _Frame, detect: bool, det_prog, pose_prog, single_stream: bool) -> None:
         J = pose_prog.out_shape[0]
         if detect:
@@ -134,13 +198,17 @@ class PoseTracker(object):
             self._boxes(fr, J)
         self.estimator._poses(fr, pose_prog, single_stream)
         self._associate(fr, J)
-        self.estimator._render(fr, J, tracked=True)  # (nothing without estimator.renderer) the frame's ids colour the persons
+        if self.smooth is not None:
+            self._smooth(fr, J)
+        # (nothing without estimator.renderer) the frame's ids colour the persons; a smoothing tracker draws the smoothed poses
+        self.estimator._render(fr, J, tracked=True, kps=None if self.smooth is None else fr.kps_smooth)
 
     def _params(self, det_prog, pose_prog) -> tuple:
-        return (self.estimator._params(det_prog, pose_prog), self.match_thre, self.max_age, self.box_expand, self.slots, id(self._sim))
+        return (self.estimator._params(det_prog, pose_prog), self.match_thre, self.max_age, self.box_expand, self.slots, id(self._sim),
+                None if self.smooth is None else self.smooth.key() + (id(self.smooth_state["n"]),))
 
     def _graph(self, fr: _Frame, detect: bool, det_prog, pose_prog):
-        key = (fr.H, fr.W, detect)
+        key = (fr.H, fr.W, detect, None if self.smooth is None else self.smooth.key())
         entry = self._graphs.get(key)
         params = self._params(det_prog, pose_prog)
         if entry is not None and entry[0] is fr and entry[2] == params:
@@ -152,14 +220,15 @@ class PoseTracker(object):
             if detect:                               # Without the association: it allocates nothing, and the tracks must advance once per frame
                 est._detect(fr, det_prog, True)
             est._poses(fr, pose_prog, True)
-            est._render(fr, pose_prog.out_shape[0], tracked=True)      # (changes no state: whatever ids the frame holds)
+            # (changes no state: whatever ids - and, smoothing, whatever smoothed poses - the frame holds)
+            est._render(fr, pose_prog.out_shape[0], tracked=True, kps=None if self.smooth is None else fr.kps_smooth)
         torch.cuda.current_stream(dev).wait_stream(side)
         torch.cuda.synchronize(dev)
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self._launch(fr, detect, det_prog, pose_prog, True)
         keepalive = (det_prog, pose_prog, None if det_prog is None else det_prog.pool_for(1, dev), pose_prog.pool_for(est._pose_batch(), dev),
-                     getattr(fr, "ws", None), self.state, self._sim)
+                     getattr(fr, "ws", None), self.state, self._sim, self.smooth_state)
         self._graphs.pop(key, None)
         if len(self._graphs) >= self.MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
@@ -167,10 +236,17 @@ class PoseTracker(object):
         return graph
 
     @torch.no_grad()
-    def update(self, img) -> PoseResult:
+    def update(self, img, timestamp=None) -> PoseResult:
         """One uint8 BGR image [H, W, 3] (numpy or CUDA), the next frame of the stream -> the persons in it with their `track_id`s.
-        A propagated frame (see the module docstring) does not run the detector: new persons appear at the next detector frame."""
+        A propagated frame (see the module docstring) does not run the detector: new persons appear at the next detector frame.
+        `timestamp`: the frame's time in seconds, for a tracker that smooths (default: frame index / `smooth.fps`, the index counted from
+        the first frame after construction or reset()).  A time that does not advance is not an error: the filter starts again."""
         est = self.estimator
+        if timestamp is not None:
+            if self.smooth is None:
+                raise ValueError("timestamp: this tracker does not smooth (PoseTracker(..., smooth=OneEuro(...))); nothing would read it")
+            if not isinstance(timestamp, (int, float)) or isinstance(timestamp, bool) or not (abs(float(timestamp)) < float("inf")):
+                raise ValueError(f"timestamp: a finite time in seconds, got {timestamp!r}")
         img = est._shape_of(img, batched=False)
         imgs = img[None]
         H, W = imgs.shape[1], imgs.shape[2]
@@ -182,8 +258,11 @@ class PoseTracker(object):
         pose_prog = est._pose_program()
         J = pose_prog.out_shape[0]
         self._ensure_state(J)
-        fr = est._frame(1, H, W, est.MAX_DET, J)
+        fr = est._frame(1, H, W, est.MAX_DET, J, smooth=self.smooth is not None)
         est._load(fr, imgs)
+        if self.smooth is not None:                  # the frame's time, on the frame's stream ahead of the launch or replay that reads it
+            self.smooth_state["now"].fill_(self._frame_index / self.smooth.fps if timestamp is None else float(timestamp))
+        self._frame_index += 1
         self._prev_n = 0                             # (a frame that raises below is followed by a detector frame)
         if est.use_graph:
             self._graph(fr, detect, det_prog, pose_prog).replay()

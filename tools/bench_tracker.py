@@ -1,6 +1,7 @@
 """tools/bench_tracker.py - what tracking costs per frame, and what leaving the detector out of three frames in four gains, on one MI355X.
 
     python tools/bench_tracker.py [--out profiles/tracker_bench.json] [--quick]
+    python tools/bench_tracker.py --smooth [--out ...] [--quick]       what the key-point smoother adds to the tracked frame (see below)
 
 Per frame, median wall time ending in a device synchronise, warm, the variants ALTERNATED in one process (so that clock ramps and
 neighbours hit them alike), all graphed (one replay per frame):
@@ -12,6 +13,11 @@ The set-up is tools/bench_pipeline.py's: the s detector on a 640 x 640 source, c
 tests' conditioned (random) weights - the detections are not people, the work per frame is what is measured.  track4's median is over
 all frames, detector frames included; its two kinds of frame are also reported apart.  The two new entry points are timed with device
 events over back-to-back launches on a full state (32 tracks, 32 poses): sp_track_associate is two kernels per launch.
+
+--smooth times the tracked frame (detect_every = 1, graphed) with and without PoseTracker(smooth=OneEuro()) in the same process, the two
+ALTERNATED, plus the plain tracker a second time for the measurement's own spread, and sp_track_smooth alone with device events (32 kept
+rows, every track found again, the time advancing from launch to launch so that every joint takes the update path).  The result is merged
+into the output file under the key "smooth"; the other keys of the file stay as they are.
 """
 from __future__ import annotations
 
@@ -32,7 +38,7 @@ from simple_pose_amd.detector.nets.yolov5 import YOLOv5  # noqa: E402
 from simple_pose_amd.detector.yolov5_detector import YOLOv5Detector  # noqa: E402
 from simple_pose_amd.metrics import GaussTaylorKeyPointDecoder  # noqa: E402
 from simple_pose_amd.pipeline import TopDownPoseEstimator  # noqa: E402
-from simple_pose_amd.tracking import PoseTracker  # noqa: E402
+from simple_pose_amd.tracking import OneEuro, PoseTracker  # noqa: E402
 from tests.detector_ref import detector_state_dict  # noqa: E402
 from tools.bench_pipeline import CAPACITY, DEV, kernel_us, pose_model, summary, wall_ms  # noqa: E402
 
@@ -65,16 +71,82 @@ def kernel_times():
     return out
 
 
+def smooth_kernel_time():
+    """sp_track_smooth alone: 32 kept rows of 17 joints whose tracks sit in slots 0..31, the time 1/30 s further at every launch."""
+    rng = np.random.default_rng(4)
+    slots, J = CAPACITY, 17
+    d = lambda a: torch.from_numpy(np.ascontiguousarray(a)).to(DEV)
+    z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=DEV)
+    kps = d(np.concatenate([rng.uniform(0, 640, (slots, J, 2)), rng.uniform(0.3, 1, (slots, J, 1))], 2))
+    xy = rng.uniform(0, 400, (slots, 2))
+    box = d(np.concatenate([xy, xy + rng.uniform(40, 200, (slots, 2)), rng.uniform(0, 1, (slots, 1))], 1).astype(np.float32))
+    ids = d(np.arange(1, slots + 1, dtype=np.int32))
+    keep, kc, seg = d(np.arange(slots, dtype=np.int32)), d(np.array([slots], np.int32)), d(np.array([0, slots], np.int32))
+    st = {"id": z((slots,), torch.int32), "x": z((slots, J, 2), torch.float64), "dx": z((slots, J, 2), torch.float64),
+          "t": z((slots, J), torch.float64), "n": z((slots, J), torch.int32)}
+    now, out = z((1,), torch.float64), z((slots, J, 3), torch.float64)
+    lib, stream = _lib.lib(), _lib.current_stream(torch.device(DEV))
+
+    def launch():
+        now.add_(1.0 / 30.0)                                      # (one more tiny launch inside the timed window: reported as such)
+        _lib.check(lib.sp_track_smooth(P(kps), P(box), P(ids), P(keep), P(kc), P(seg), slots, J, P(ids), slots, P(now), 1.0, 0.5, 1.0, 0.5, 0.2,
+                                       P(st["id"]), P(st["x"]), P(st["dx"]), P(st["t"]), P(st["n"]), P(out), stream), "sp_track_smooth")
+
+    launch()
+    us = kernel_us(launch)
+    assert int(st["n"].min().item()) > 2                          # every joint was filtered at every launch
+    return {"sp_track_smooth 32 rows x 17 joints + the clock's add_ back_to_back_us": us}
+
+
+def smooth_main(args, det, img, decoder):
+    reps, warm = (8, 4) if args.quick else (80, 8)
+    out = {"device": torch.cuda.get_device_name(0), "source": [640, 640], "capacity": CAPACITY, "reps": reps, "one_euro": repr(OneEuro()),
+           "kernels": smooth_kernel_time(), "runs": []}
+    print(json.dumps(out["kernels"]), flush=True)
+    for head, dtype in ([("dconv", "fp32")] if args.quick else [("dconv", "fp32"), ("duc", "bf16")]):
+        est = TopDownPoseEstimator(det, pose_model(head, dtype), decoder=decoder, capacity=CAPACITY)
+        plain, smooth, plain2 = PoseTracker(est), PoseTracker(est, smooth=OneEuro()), PoseTracker(est)
+        variants = {"track": lambda: plain.update(img), "track_smooth": lambda: smooth.update(img), "track2": lambda: plain2.update(img)}
+        first = {k: fn() for k, fn in variants.items()}
+        times = {k: [] for k in variants}
+        for r in range(warm + reps):
+            for k, fn in variants.items():
+                t = wall_ms(fn)
+                if r >= warm:
+                    times[k].append(t)
+        last = smooth.update(img)
+        run = {"pose": f"resnet50-{head} {dtype}", "poses_kept": len(first["track"]), "packed_bytes": int(est._frame(1, 640, 640, est.MAX_DET, 17).pack.numel()),
+               "packed_bytes_smooth": int(est._frame(1, 640, 640, est.MAX_DET, 17, smooth=True).pack.numel()),
+               "raw_results_equal": bool(np.array_equal(last.keypoints, first["track"].keypoints))}
+        run.update({k: summary(v) for k, v in times.items()})
+        run["track_self_spread_ms"] = abs(run["track"]["median_ms"] - run["track2"]["median_ms"])
+        run["smoothing_cost_ms"] = run["track_smooth"]["median_ms"] - run["track"]["median_ms"]
+        out["runs"].append(run)
+        print(json.dumps(run), flush=True)
+    if not args.quick:
+        whole = {}
+        if os.path.isfile(args.out):
+            with open(args.out) as fh:
+                whole = json.load(fh)
+        whole["smooth"] = out
+        with open(args.out, "w") as fh:
+            json.dump(whole, fh, indent=1)
+        print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "tracker_bench.json"))
     ap.add_argument("--quick", action="store_true", help="DConv fp32 only, few repetitions; nothing is written")
+    ap.add_argument("--smooth", action="store_true", help="the tracked frame with and without the key-point smoother; merged into --out under 'smooth'")
     args = ap.parse_args()
     reps, warm = (8, 4) if args.quick else (80, 8)                # multiples of 4: track4 sees whole detector / propagated cycles
     det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
     det.conf_thresh, det.iou_thresh = 0.02, 0.45
     img = np.random.default_rng(0).integers(0, 256, (640, 640, 3), dtype=np.uint8)
     decoder = GaussTaylorKeyPointDecoder()
+    if args.smooth:
+        return smooth_main(args, det, img, decoder)
     out = {"device": torch.cuda.get_device_name(0), "source": [640, 640], "detector": "s fp32", "capacity": CAPACITY, "reps": reps,
            "pose_autotune": False, "kernels": kernel_times(), "runs": []}
     print(json.dumps(out["kernels"]), flush=True)
