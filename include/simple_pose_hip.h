@@ -397,7 +397,11 @@ int sp_masked_mse(const float* pred, const float* target, const float* mask, int
  * Activations NHWC; argument `bf16`: bit 0 = activations (z, relu_src, dz, pool input) are bf16, bit 1 = activation
  * gradients (dy, dres, pool dx/dy) are bf16; statistics and the gradients of the affine parameters are always fp32;
  * `rows` = B*H*W.  `workspace` of the reductions: >= SP_REDUCE_WORKSPACE_BYTES(c) bytes (per-workgroup partial sums in fp64,
- * folded in a fixed order by a second small kernel: deterministic, no float atomics); c <= 4096. */
+ * folded in a fixed order by a second small kernel: deterministic, no float atomics); c <= 4096.
+ * Widths the reductions take: c % 4 == 0 and c/4 either <= 256 or a multiple of 256 (c <= 1024, 2048, 3072, 4096 - every width of the
+ * nets here).  Their workgroups walk c/4 channel quads 256 at a time with a barrier in every trip, so a width such as 1536 (one and a
+ * half trips) is refused with SP_EINVAL by every entry point that runs one: sp_bn_train_stats_nhwc, sp_bn_train_partial_nhwc,
+ * sp_bn_train_bwd_reduce_nhwc, sp_bn_train_bwd_nhwc, sp_bn_maxpool_bwd_nhwc and sp_channel_sum_nhwc. */
 #define SP_REDUCE_WORKSPACE_BYTES(c) ((int64_t)4 << 20)
 
 /* nn.BatchNorm2d in train mode, statistics half: per-channel batch mean and 1/sqrt(biased var + eps) of z [rows, c];
@@ -469,7 +473,9 @@ int sp_bn_fold_apply_nhwc(const void* z, int bf16, const float* stats_sum, const
                           void* stream);
 /* `bf16` of the backward passes is a bit word: 1 = activations (z, relu_src, dz) are bf16; 2 = the activation gradients (dy, dres) are bf16 too
  * (PoseTrainer grad_dtype "bf16"); 4 = relu_src is the ReLU BIT MASK the forward pass left in `relu_mask` (uint8 [rows * c / 8], bit e of
- * byte i = channel 8 i + e passed the ReLU; bf16 activations, c % 8 == 0) instead of the tensor y: 1/16 of the bytes. */
+ * byte i = channel 8 i + e passed the ReLU; bf16 activations, c % 8 == 0) instead of the tensor y: 1/16 of the bytes.  Flag 4 belongs to the
+ * apply passes (sp_bn_fold_bwd_apply_nhwc, sp_bn_train_bwd_apply_nhwc); the reduction sp_bn_train_bwd_reduce_nhwc (and with it
+ * sp_bn_train_bwd_nhwc) reads relu_src as the tensor y and refuses it. */
 int sp_bn_fold_bwd_apply_nhwc(const void* dy, int bf16, const void* relu_src, const void* z, const float* sum_g, const float* sum_g_xhat,
                               const float* sum_g_xhat2, int partial_rows, int stride, const float* mean, const float* invstd,
                               const float* gamma, int64_t total_rows, int64_t rows, int c, float* dgamma, float* dbeta, float* dgamma2,

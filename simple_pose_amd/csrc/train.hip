@@ -58,6 +58,12 @@ static int red_blocks(long long rows, int c) {
     return (int)(n < 1 ? 1 : n);
 }
 
+// Widths channel_reduce_kernel takes: its threads walk the c/4 channel quads min(c/4, 256) at a time and meet at a workgroup barrier in
+// every trip, so all of them must make the same number of trips (c = 1536: threads 0..127 would make two, threads 128..255 one).
+// Every entry point that launches the kernel refuses other widths with SP_REDUCE_WIDTH_MSG behind its own name.
+static bool reduce_width_ok(int c) { return c > 0 && c % 4 == 0 && ((c / 4) <= 256 || (c / 4) % 256 == 0); }
+#define SP_REDUCE_WIDTH_MSG "bad shape rows=%lld c=%d (c %% 4 == 0; c/4 must be <= 256 or a multiple of 256)"
+
 // ---------------------------------------------------------------------------------------------------------------
 // per-channel sums over the M rows of an NHWC tensor: thread = (4 channels) x (row stripe)
 //   mode 0: s0 = sum z,            s1 = sum z^2                         (BN forward statistics)
@@ -1188,8 +1194,7 @@ extern "C" int sp_permute4_batched_tiled(const float* src, const void* jobs_devi
 extern "C" int sp_bn_train_stats_nhwc(const void* z, int bf16, int64_t rows, int c, float eps, float momentum, float* mean, float* invstd,
                                       float* running_mean, float* running_var, void* workspace, void* stream) {
     SP_REQUIRE(z && mean && invstd && workspace, "sp_bn_train_stats_nhwc: null pointer");
-    SP_REQUIRE(rows > 0 && c > 0 && c % 4 == 0 && rows < (1ll << 31) && ((c / 4) <= 256 ? 256 % 1 == 0 : (c / 4) % 256 == 0),
-               "sp_bn_train_stats_nhwc: bad shape rows=%lld c=%d (c/4 must be <= 256 or a multiple of 256)", (long long)rows, c);
+    SP_REQUIRE(rows > 0 && rows < (1ll << 31) && reduce_width_ok(c), "sp_bn_train_stats_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)rows, c);
     SP_REQUIRE((running_mean == nullptr) == (running_var == nullptr), "sp_bn_train_stats_nhwc: running stats come in pairs");
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
@@ -1202,7 +1207,7 @@ extern "C" int sp_bn_train_stats_nhwc(const void* z, int bf16, int64_t rows, int
 
 extern "C" int sp_bn_train_partial_nhwc(const void* z, int bf16, int64_t rows, int c, double* sums, void* workspace, void* stream) {
     SP_REQUIRE(z && sums && workspace, "sp_bn_train_partial_nhwc: null pointer");
-    SP_REQUIRE(rows > 0 && c > 0 && c % 4 == 0 && rows < (1ll << 31), "sp_bn_train_partial_nhwc: bad shape rows=%lld c=%d", (long long)rows, c);
+    SP_REQUIRE(rows > 0 && rows < (1ll << 31) && reduce_width_ok(c), "sp_bn_train_partial_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)rows, c);
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
     if (bf16 & 1) hipLaunchKernelGGL((channel_reduce_kernel<0, true>), dim3(red_blocks(rows, c)), dim3(256), 0, s, z, nullptr, nullptr, nullptr, nullptr, (int)rows, c, part);
@@ -1366,11 +1371,12 @@ extern "C" int sp_bn_apply_sums_nhwc(const void* z, int bf16, const double* sums
 extern "C" int sp_bn_train_bwd_reduce_nhwc(const void* dy, int bf16, const void* relu_src, const void* z, const float* mean, const float* invstd,
                                            int64_t rows, int c, float* dgamma, float* dbeta, void* workspace, void* stream) {
     SP_REQUIRE(dy && z && mean && invstd && dgamma && dbeta && workspace, "sp_bn_train_bwd_reduce_nhwc: null pointer");
-    SP_REQUIRE(rows > 0 && c > 0 && c % 4 == 0 && rows < (1ll << 31), "sp_bn_train_bwd_reduce_nhwc: bad shape");
+    SP_REQUIRE(rows > 0 && rows < (1ll << 31) && reduce_width_ok(c), "sp_bn_train_bwd_reduce_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)rows, c);
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
     const bool a16 = bf16 & 1, g16 = bf16 & 2;
     SP_REQUIRE(a16 || !g16, "sp_bn_train_bwd_reduce_nhwc: bf16 gradients with fp32 activations is not a supported mix");
+    SP_REQUIRE(!(bf16 & 4), "sp_bn_train_bwd_reduce_nhwc: the reduction reads relu_src as the tensor y (the ReLU bit mask, flag 4, is for the apply passes)");
     if (a16 && g16) hipLaunchKernelGGL((channel_reduce_kernel<1, true, true>), dim3(red_blocks(rows, c)), dim3(256), 0, s, dy, relu_src, z, mean, invstd, (int)rows, c, part);
     else if (a16) hipLaunchKernelGGL((channel_reduce_kernel<1, true, false>), dim3(red_blocks(rows, c)), dim3(256), 0, s, dy, relu_src, z, mean, invstd, (int)rows, c, part);
     else hipLaunchKernelGGL((channel_reduce_kernel<1, false, false>), dim3(red_blocks(rows, c)), dim3(256), 0, s, dy, relu_src, z, mean, invstd, (int)rows, c, part);
@@ -1405,6 +1411,7 @@ extern "C" int sp_bn_train_bwd_apply_nhwc(const void* dy, int bf16, const void* 
 extern "C" int sp_bn_train_bwd_nhwc(const void* dy, int bf16, const void* relu_src, const void* z, const float* mean, const float* invstd,
                                     const float* gamma, int64_t rows, int c, void* dz, float* dgamma, float* dbeta, void* dres,
                                     int dres_accumulate, void* workspace, void* stream) {
+    SP_REQUIRE(rows > 0 && rows < (1ll << 31) && reduce_width_ok(c), "sp_bn_train_bwd_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)rows, c);
     const int rc = sp_bn_train_bwd_reduce_nhwc(dy, bf16, relu_src, z, mean, invstd, rows, c, dgamma, dbeta, workspace, stream);
     if (rc) return rc;
     return sp_bn_train_bwd_apply_nhwc(dy, bf16, relu_src, z, mean, invstd, gamma, dgamma, dbeta, rows, rows, c, dz, dres, dres_accumulate, stream);
@@ -1464,7 +1471,8 @@ extern "C" int sp_channel_sum_nchw(const float* x, int batch, int channels, int 
 }
 
 extern "C" int sp_channel_sum_nhwc(const float* a, int64_t rows, int c, float* sum, void* workspace, void* stream) {
-    SP_REQUIRE(a && sum && workspace && rows > 0 && c > 0 && c % 4 == 0 && rows < (1ll << 31), "sp_channel_sum_nhwc: bad argument");
+    SP_REQUIRE(a && sum && workspace, "sp_channel_sum_nhwc: null pointer");
+    SP_REQUIRE(rows > 0 && rows < (1ll << 31) && reduce_width_ok(c), "sp_channel_sum_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)rows, c);
     hipStream_t s = (hipStream_t)stream;
     double* part = reinterpret_cast<double*>(workspace);
     hipLaunchKernelGGL((channel_reduce_kernel<0, false>), dim3(red_blocks(rows, c)), dim3(256), 0, s, a, nullptr, nullptr, nullptr, nullptr, (int)rows, c, part);
@@ -1533,6 +1541,8 @@ extern "C" int sp_bn_maxpool_bwd_nhwc(const void* dy_pooled, int bf16, const voi
                                       void* workspace, void* stream) {
     SP_REQUIRE(dy_pooled && idx && z && mean && invstd && gamma && beta && dgamma && dbeta && dz && workspace, "sp_bn_maxpool_bwd_nhwc: null pointer");
     SP_REQUIRE(batch > 0 && h > 0 && w > 0 && c > 0 && c % 4 == 0, "sp_bn_maxpool_bwd_nhwc: bad shape");
+    // (stem_pool_bwd_reduce_kernel has channel_reduce_kernel's block structure, barrier included)
+    SP_REQUIRE(reduce_width_ok(c), "sp_bn_maxpool_bwd_nhwc: " SP_REDUCE_WIDTH_MSG, (long long)batch * h * w, c);
     const bool a16 = bf16 & 1, g16 = bf16 & 2;
     SP_REQUIRE(a16 || !g16, "sp_bn_maxpool_bwd_nhwc: bf16 gradients with fp32 activations is not a supported mix");
     const int ho = (h + 2 - 3) / 2 + 1, wo = (w + 2 - 3) / 2 + 1;
