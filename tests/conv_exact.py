@@ -5,7 +5,11 @@ holds the exact result in any reduction order, on any tile, in any kernel.  The 
 ReLU) stays exact; the one inexact step left is the final store, whose bits are unique: round-to-nearest-even of the exact value.  A float64
 torch convolution therefore predicts every stored bit of every launch - one wrong, missing or doubled term in one element is a mismatch.
 
-tests/test_conv_exact_host.py holds the case table against the descriptor interpreter (no GPU), tests/test_gpu_conv_exact.py the kernels.
+The launches that run several convolutions at once (Fused, below) are chains of such stages: each stage's pre-store value is exact, so its store
+rounding is unique, and so is everything after it.
+
+tests/test_conv_exact_host.py holds the case tables against the descriptor interpreter (no GPU), tests/test_gpu_conv_exact.py the kernels that run
+one convolution, tests/test_gpu_fused_exact.py the fused ones.
 """
 import zlib
 from dataclasses import dataclass, replace
@@ -336,3 +340,270 @@ def stats_conditions(z: torch.Tensor, store_dtype) -> dict:
     top = (z * z).sum(0).max().item()
     assert top < LIMIT and z.abs().sum(0).max().item() < LIMIT, top
     return {"column_sumsq_max": top}
+
+
+# ---- fused launches: several convolutions in one launch -----------------------------------------------------------------------------------------
+# A fused case is a chain of stages.  One stage: convolution (float64), times a per-channel power-of-two scale, plus an integer shift, plus an
+# optional residual, optional ReLU, then the store rounding of THAT stage: bf16 where the per-conv program stores bf16, none where it stores fp32.
+# The pre-store value of a stage is an fp32 value (asserted), so its round-to-nearest-even is unique - and with it every later stage.
+def _p2(*exponents):
+    return tuple(2.0 ** -e for e in exponents)
+
+
+# family -> channels of x, operand magnitudes, and per stage the scale choices and what is added to every channel's shift (integers in +-4)
+FAMILIES = {
+    # t1 = bf16(relu(s1 (x.W1) + b1)), 0 outside the image; t2 = bf16(relu(s2 conv3x3(t1) + b2)); y = bf16(relu(s3 (t2.W3) + b3 + x))
+    "bneck64": dict(c=256, x_mag=3, scales=(_p2(1, 0, -1), _p2(4, 3, 2), _p2(5, 4, 3)), bias=(4, 0, 0)),
+    # t = bf16(relu(s1 conv3x3(x) + b1)), 0 outside the image; y = bf16(relu(s2 conv3x3(t) + b2 + x))
+    "bb32": dict(c=32, x_mag=16, w_mag=(8, 1), scales=(_p2(1, 0, -1), _p2(9, 8, 7)), bias=(128, 0)),
+    "bb64": dict(c=64, x_mag=16, w_mag=(8, 1), scales=(_p2(1, 0, -1), _p2(10, 9, 8)), bias=(128, 0)),
+    # r = [bf16](sd (x.Wd) + hd); y = [bf16](relu(s3 (t.W3) + h3 + r)): the shortcut's shift lifts r to where a third of a bf16's bits are dropped
+    "dual_bf16": dict(c=64, x_mag=4, w_mag=4, scales=(_p2(4, 3, 2), _p2(3, 2, 1)), bias=(160, -148)),
+    "dual_f32": dict(c=64, x_mag=4, w_mag=4, scales=(_p2(4, 3, 2), _p2(3, 2, 1)), bias=(160, -148)),
+    # y = relu(s3 (t.W3) + b3 + residual); t_next = relu(s1 (y.W1) + b1): fp32 stores, nothing rounded
+    "pwchain64": dict(c=64, x_mag=3, scales=(_p2(2, 1, 0), _p2(3, 2, 1)), bias=(0, 0), c_next=64),
+    "pwchain128": dict(c=64, x_mag=3, scales=(_p2(2, 1, 0), _p2(3, 2, 1)), bias=(0, 0), c_next=128),
+    # y_hi = bf16(relu(sa conv3x3(x) + ha)), y_lo = bf16(relu(sb conv3x3_stride2(x) + hb)): two one-stage convolutions of the same x
+    "htrans": dict(c=256, x_mag=3, scales=(_p2(4, 3, 2), _p2(4, 3, 2)), bias=(0, 0)),
+}
+POINTWISE = ("dual_bf16", "dual_f32", "pwchain64", "pwchain128")       # B = H = 1, W = rows
+FUSED_TILES = {"bneck64": (16, 8), "bb32": (8, 48), "bb64": (4, 24), "htrans": (32, 16)}       # output tile of the default kernel (rows, columns)
+KERNEL_VARIANT = {"bb32": 4, "bneck64": 5, "bb64": 6}                   # sp_conv2d_kernel_name's variant of the families the library names
+
+
+@dataclass(frozen=True)
+class Fused:
+    family: str
+    B: int
+    H: int
+    W: int
+
+    @property
+    def name(self) -> str:
+        return f"{self.family}_{self.W}" if self.family in POINTWISE else f"{self.family}_{self.B}x{self.H}x{self.W}"
+
+
+def fused_tiles(c: Fused, tile=None) -> int:
+    th, tw = tile or FUSED_TILES[c.family]
+    return c.B * (-(-c.H // th)) * (-(-c.W // tw))
+
+
+def fused_operands(c: Fused) -> dict:
+    """The operands of one fused case (float64, reference layouts: activations NCHW, weights [O, I, k, k], vectors [C])."""
+    f, g = FAMILIES[c.family], generator(c.name)
+    pick = lambda choices, n: torch.tensor(choices, dtype=torch.float64)[torch.randint(0, len(choices), (n,), generator=g)]
+    wm = f.get("w_mag", 1)
+    wm = wm if isinstance(wm, tuple) else (wm,) * 3
+    o = {"x": ints((c.B, f["c"], c.H, c.W), f["x_mag"], g)}
+    if c.family == "bneck64":
+        shapes = ((64, 256, 1, 1), (64, 64, 3, 3), (256, 64, 1, 1))
+    elif c.family in ("bb32", "bb64"):
+        shapes = ((f["c"], f["c"], 3, 3),) * 2
+    elif c.family.startswith("dual"):
+        o["t"] = ints((c.B, 64, c.H, c.W), f["x_mag"], g)
+        shapes = ((256, 64, 1, 1),) * 2                                    # the shortcut's Wd, then W3
+    elif c.family.startswith("pwchain"):
+        o["res"] = ints((c.B, 256, c.H, c.W), 4, g)
+        shapes = ((256, 64, 1, 1), (f["c_next"], 256, 1, 1))               # W3, then the next block's W1
+    else:
+        shapes = ((32, 256, 3, 3), (64, 256, 3, 3))
+    for i, (shape, choices, bias) in enumerate(zip(shapes, f["scales"], f["bias"])):
+        o[f"w{i}"], o[f"s{i}"], o[f"b{i}"] = ints(shape, wm[i], g), pick(choices, shape[0]), ints((shape[0],), 4, g) + bias
+    return o
+
+
+@dataclass
+class FusedData:
+    """One fused case evaluated: the operands, what every stage saw, the intermediates and the exact outputs (float64, NCHW)."""
+    case: Fused
+    ops: dict
+    stages: list                       # per stage: name, pre (before ReLU and store), relu, bound_units, unit
+    inter: dict                        # intermediates as stored
+    pre: dict                          # output name -> its stage's value before ReLU and store
+    ref: dict                          # output name -> the exact stored value
+    store_dtype: torch.dtype
+
+    def expected(self, name: str) -> torch.Tensor:
+        """What the launch must store in output `name` (NHWC): torch's conversion rounds to nearest even."""
+        return self.ref[name].permute(0, 2, 3, 1).contiguous().to(self.store_dtype)
+
+
+def _pad_with(t, fill):
+    """t [B, C, H, W] with a one-pixel ring of the per-channel value `fill` around it."""
+    B, C, H, W = t.shape
+    out = fill.view(1, C, 1, 1).expand(B, C, H + 2, W + 2).clone()
+    out[:, :, 1:-1, 1:-1] = t
+    return out
+
+
+def _stage(log, name, x, w, scale, shift, *, pad=0, stride=1, res=None, relu=True, store=None, unit_in=1.0, res_unit=1.0, ring=None, trunc=False):
+    """One stage.  `unit_in` / `res_unit`: the finest bit of x / of the residual (weights, shifts are integers, scales powers of two, so every
+    partial sum of the stage is a multiple of `unit`); `ring`: MUTATION - x outside the image holds this per-channel value instead of 0;
+    `trunc`: MUTATION - a bf16 store that cuts the dropped bits off."""
+    bc = lambda v: v.view(1, -1, 1, 1)
+    xin = x
+    if ring is not None:
+        assert pad == 1
+        xin, pad = _pad_with(x, ring), 0
+    pre = F.conv2d(xin, w, stride=stride, padding=pad) * bc(scale) + bc(shift)
+    top = F.conv2d(xin.abs(), w.abs(), stride=stride, padding=pad).max().item() * scale.max().item() + shift.abs().max().item()
+    if res is not None:
+        pre, top = pre + res, top + res.abs().max().item()
+    unit = min(unit_in * scale.min().item(), res_unit, 1.0)
+    out = torch.relu(pre) if relu else pre
+    if store == "bf16":
+        out = (truncate_to_bf16(out) if trunc else out.float().bfloat16()).double()
+    log.append(dict(name=name, pre=pre, relu=relu, bound_units=top / unit, unit=unit))
+    return out + 0.0, unit
+
+
+def _drop(w, term):
+    """MUTATION: one (output channel, input channel, tap) product left out."""
+    if term is None:
+        return w
+    o, i, tap = term
+    w = w.clone()
+    assert w[o, i].reshape(-1)[tap] != 0
+    w[o, i].view(-1)[tap] = 0
+    return w
+
+
+def fused_eval(c: Fused, o: dict, ring=False, trunc=False, drop=None, shift_res=False) -> FusedData:
+    """The float64 chain of case `c` on operands `o`.  The keyword arguments are the four mutations of the negative self-check (each family takes
+    those that exist for it): `ring` - the 3x3's input outside the image is bf16(relu(shift)) of the stage before, not 0; `trunc` - every
+    intermediate bf16 store (transition1: its only store) truncates; `drop` - one term of the 3x3 (pointwise families: of the first product)
+    left out; `shift_res` - the residual comes from the neighbouring pixel."""
+    fam, log, inter = c.family, [], {}
+    bf = None if fam in ("dual_f32", "pwchain64", "pwchain128") else "bf16"
+    x = o["x"]
+    side = lambda t: torch.roll(t, 1, dims=-1) if shift_res else t
+    edge = lambda i: torch.relu(o[f"b{i}"]).float().bfloat16().double() if ring else None
+    if fam == "bneck64":
+        t1, u = _stage(log, "t1", x, o["w0"], o["s0"], o["b0"], store=bf, trunc=trunc)
+        t2, u = _stage(log, "t2", t1, _drop(o["w1"], drop), o["s1"], o["b1"], pad=1, store=bf, unit_in=u, ring=edge(0), trunc=trunc)
+        y, _ = _stage(log, "y", t2, o["w2"], o["s2"], o["b2"], res=side(x), store=bf, unit_in=u)
+        inter, outs = {"t1": t1, "t2": t2}, {"y": y}
+    elif fam in ("bb32", "bb64"):
+        t, u = _stage(log, "t", x, _drop(o["w0"], drop), o["s0"], o["b0"], pad=1, store=bf, trunc=trunc)
+        y, _ = _stage(log, "y", t, o["w1"], o["s1"], o["b1"], pad=1, res=side(x), store=bf, unit_in=u, ring=edge(0))
+        inter, outs = {"t": t}, {"y": y}
+    elif fam.startswith("dual"):
+        r, u = _stage(log, "r", x, _drop(o["w0"], drop), o["s0"], o["b0"], relu=False, store=bf, trunc=trunc)
+        y, _ = _stage(log, "y", o["t"], o["w1"], o["s1"], o["b1"], res=side(r), res_unit=u, store=bf)
+        inter, outs = {"r": r}, {"y": y}
+    elif fam.startswith("pwchain"):
+        y, u = _stage(log, "y", x, _drop(o["w0"], drop), o["s0"], o["b0"], res=side(o["res"]))
+        tn, _ = _stage(log, "t_next", y, o["w1"], o["s1"], o["b1"], unit_in=u)
+        outs = {"y": y, "t_next": tn}
+    else:
+        assert fam == "htrans", fam
+        hi, _ = _stage(log, "y_hi", x, _drop(o["w0"], drop), o["s0"], o["b0"], pad=1, store=bf, trunc=trunc)
+        lo, _ = _stage(log, "y_lo", x, o["w1"], o["s1"], o["b1"], pad=1, stride=2, store=bf, trunc=trunc)
+        outs = {"y_hi": hi, "y_lo": lo}
+    pre = {s["name"]: s["pre"] for s in log if s["name"] in outs}
+    return FusedData(c, o, log, inter, pre, outs, torch.bfloat16 if bf else torch.float32)
+
+
+def make_fused(c: Fused) -> FusedData:
+    return fused_eval(c, fused_operands(c))
+
+
+def fused_conditions(d: FusedData) -> dict:
+    """What makes a fused case exact and worth running, asserted on the reference alone; returns the figures."""
+    out = {}
+    for k, v in d.ops.items():
+        assert torch.equal(v, v.round()) or k[0] == "s", k
+        if k[0] in "xtw":
+            assert not bool((v == 0).any()), k                              # every product counts
+        if k[0] == "s":
+            assert torch.equal(torch.log2(v), torch.log2(v).round()), k     # powers of two
+    for s in d.stages:
+        n = s["name"]
+        out[n + "_bound_units"] = s["bound_units"]
+        assert s["bound_units"] < LIMIT, (d.case.name, n, s["bound_units"])   # every partial sum, in any order, is below 2^24 of the stage's finest bit
+        assert torch.equal(s["pre"].float().double(), s["pre"]), (d.case.name, n)
+        if s["relu"]:
+            out[n + "_positive"] = (s["pre"] > 0).double().mean().item()
+            assert out[n + "_positive"] >= 0.40, (d.case.name, out)         # ReLU does not blank what follows
+    for n, p in d.pre.items():
+        out[n + "_below_256"] = (p.abs() < 256).double().mean().item()
+        assert out[n + "_below_256"] >= 0.90, (d.case.name, out)
+    return out
+
+
+@dataclass
+class LoweredFused:
+    """One fused case lowered through engine.ProgramBuilder: the program's ops (one fused op, or the per-conv launches it replaces), the
+    operands in the launch's layouts under their buffer names, and the buffer of every output."""
+    ops: list
+    bufs: dict
+    outs: dict
+    shapes: dict
+
+
+def lower_fused(d: FusedData, packer, device, fused: bool = True) -> LoweredFused:
+    """`fused`: through the builder methods the engine itself uses (bottleneck_c64, basic_block_c32, dual_pointwise_tail, the `pwchain` / `htrans`
+    lowerings); else the per-conv program of the same block.  Scale and shift are the exact fp32 vectors of the case."""
+    c, o, fam = d.case, d.ops, d.case.family
+    bf = d.store_dtype == torch.bfloat16
+    adt = d.store_dtype
+    dev = lambda t: t.float().to(device)
+    nhwc = lambda t: t.permute(0, 2, 3, 1).contiguous().to(adt).to(device)
+    b = engine.ProgramBuilder(c.H, c.W, dtype="bf16" if bf else "fp32", packer=packer)
+    b.fuse_bottlenecks = b.fuse_blocks = b.fuse_blocks64 = b.fuse_tail = b.fuse_chain = b.fuse_transition = fused
+    b.p.shapes["input"] = (c.H, c.W, FAMILIES[fam]["c"])
+    bufs = {"input": nhwc(o["x"])}
+    W, S, Hh = ([dev(o[f"{k}{i}"]) for i in range(3) if f"{k}{i}" in o] for k in "wsb")
+    if fam == "bneck64":
+        y = b.bottleneck_c64("input", W[0], S[0], Hh[0], W[1], S[1], Hh[1], W[2], S[2], Hh[2], name="blk")
+        if not fused:
+            assert y is None
+            t1 = b.conv("input", W[0], scale=S[0], shift=Hh[0], relu=True, name="blk.conv1")
+            t2 = b.conv(t1, W[1], pad=1, scale=S[1], shift=Hh[1], relu=True, name="blk.conv2")
+            y = b.conv(t2, W[2], scale=S[2], shift=Hh[2], relu=True, res="input", name="blk.conv3")
+        outs = {"y": y}
+    elif fam in ("bb32", "bb64"):
+        y = b.basic_block_c32("input", W[0], S[0], Hh[0], W[1], S[1], Hh[1], name="blk")
+        if not fused:
+            assert y is None
+            t = b.conv("input", W[0], pad=1, scale=S[0], shift=Hh[0], relu=True, name="blk.conv1")
+            y = b.conv(t, W[1], pad=1, scale=S[1], shift=Hh[1], relu=True, res="input", name="blk.conv2")
+        outs = {"y": y}
+    elif fam.startswith("dual"):
+        b.p.shapes["t"] = (c.H, c.W, 64)
+        bufs["t"] = nhwc(o["t"])
+        y = b.dual_pointwise_tail("t", W[1], S[1], Hh[1], "input", W[0], S[0], Hh[0], name="blk")
+        if not fused:
+            assert y is None
+            r = b.conv("input", W[0], scale=S[0], shift=Hh[0], name="blk.downsample")
+            y = b.conv("t", W[1], scale=S[1], shift=Hh[1], relu=True, res=r, name="blk.conv3")
+        outs = {"y": y}
+    elif fam.startswith("pwchain"):
+        b.p.shapes["res"] = (c.H, c.W, 256)
+        bufs["res"] = nhwc(o["res"])
+        y = b.conv("input", W[0], scale=S[0], shift=Hh[0], relu=True, res="res", name="blk.conv3")
+        tn = b.conv(y, W[1], scale=S[1], shift=Hh[1], relu=True, name="next.conv1")
+        engine._fuse_pw_chains(b, {})
+        outs = {"y": y, "t_next": tn}
+    else:
+        hi = b.conv("input", W[0], pad=1, scale=S[0], shift=Hh[0], relu=True, name="transition1.0")
+        lo = b.conv("input", W[1], stride=2, pad=1, scale=S[1], shift=Hh[1], relu=True, name="transition1.1")
+        engine._fuse_transition1(b)
+        outs = {"y_hi": hi, "y_lo": lo}
+    assert all(v is not None for v in outs.values()), (c.name, outs)
+    kinds = [op.kind for op in b.p.ops]
+    want = {"bneck64": "bneck64", "bb32": "bb32", "bb64": "bb64", "dual_bf16": "dual1x1", "dual_f32": "dual1x1", "pwchain64": "pwchain",
+            "pwchain128": "pwchain", "htrans": "htrans"}[fam]
+    assert (kinds == [want]) if fused else (set(kinds) == {"conv"}), (c.name, kinds)
+    for op in b.p.ops:
+        if op.desc is not None:
+            op.desc.batch = c.B
+    return LoweredFused(b.p.ops, bufs, outs, b.p.shapes)
+
+
+def fused_kernel_name(low: LoweredFused, family: str) -> str:
+    """The instantiation the fused launch resolves to where the library names it (variants 4, 5, 6), else the entry point."""
+    if family in KERNEL_VARIANT:
+        return _lib.conv_kernel_name(low.ops[0].desc, False, KERNEL_VARIANT[family])
+    return {"dual_bf16": "sp_dual_pw_bf16", "dual_f32": "sp_dual_pw_f32", "pwchain64": "sp_pw_chain_f32<64>", "pwchain128": "sp_pw_chain_f32<128>",
+            "htrans": "sp_hrnet_transition1"}[family]

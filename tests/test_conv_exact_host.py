@@ -1,7 +1,8 @@
 """The exact-integer convolution cases (tests/conv_exact.py) without a GPU: every case's conditions hold on its reference, the descriptor
 interpreter (tests/desc_interp.conv_desc_cpu on TorchPacker's layouts) reproduces the integer reference exactly - packing and geometry against an
 independent float64 convolution - the case table reaches every kernel family the GPU module must run, and the method catches what it is for: one
-dropped product at K = 4608, and a store that truncates."""
+dropped product at K = 4608, and a store that truncates.  The same for the fused launches (conv_exact.Fused): the tables of tests/test_gpu_fused_exact.py,
+the float64 chain against the per-conv chain of the interpreter, and four mutated chains that must store other bits."""
 import pytest
 import torch
 
@@ -16,6 +17,34 @@ BACKWARD_LAYERS = ("1x1", "1x1_wide_m", "3x3_s1", "3x3_s2", "1x1_s2_shortcut", "
 GROUPED = [(128, 32, 1, 3, 12, 10), (256, 32, 2, 2, 16, 12)]
 STEM = (3, 64, 7, 2, 3, 32, 24, 3)                                      # conv1: I, O, k, stride, pad, H, W, B (only its weight gradient exists)
 STATS = {"1x1_64_128": 2, "3x3_64_64": 2, "3x3_s2_128_128": 1}          # case -> operand magnitude that keeps every |z| a bf16 value
+
+# ---- the launches that run several convolutions at once (conv_exact.Fused): (B, H, W) per entry point, the smallest maps at which its tiling can go
+# wrong - one pixel, below one tile, exactly one tile, ragged in both directions - and one ragged map with more tiles than the part has compute units
+CUS = 256                                                               # MI355X; the GPU module asserts tiles > the device's own count
+
+
+def _more_tiles_than_cus(family, H, W):
+    return (CUS // ce.fused_tiles(ce.Fused(family, 1, H, W)) + 1, H, W)
+
+
+FUSED_SHAPES = {
+    "bneck64": [(1, 1, 1), (2, 5, 3), (1, 16, 8), (3, 19, 11), (2, 17, 9), (1, 24, 40), (70, 17, 9)],                 # 16x8 tiles, persistent
+    "bb32": [(1, 1, 1), (2, 7, 5), (1, 8, 48), (3, 9, 50), (2, 23, 100), _more_tiles_than_cus("bb32", 9, 50)],        # 8x48 strips (8x16 tiles behind the knob)
+    "bb64": [(1, 1, 1), (2, 3, 5), (1, 4, 24), (3, 5, 26), (2, 32, 24), _more_tiles_than_cus("bb64", 5, 26)],         # 4x24 strips
+    "dual_bf16": [(1, 1, r) for r in (77, 128, 1000, 128 * 300 + 5)],                                                 # 128-row tiles
+    "dual_f32": [(1, 1, r) for r in (50, 64 * 9, 1000, 64 * 700 + 3)],
+    "pwchain64": [(1, 1, r) for r in (50, 64 * 9, 1000, 64 * 700 + 3)],
+    "pwchain128": [(1, 1, r) for r in (50, 64 * 9, 1000, 64 * 700 + 3)],
+    "htrans": [(1, 2, 2), (1, 8, 6), (3, 34, 18), (2, 32, 16), (1, 66, 34)],                                          # 32x16 tiles, h and w even
+}
+FUSED_CASES = [ce.Fused(f, *shape) for f, shapes in FUSED_SHAPES.items() for shape in shapes]
+MANY_TILES = {f: ce.Fused(f, *FUSED_SHAPES[f][-1]) for f in ("bneck64", "bb32", "bb64")}
+# the mutation checks run on one ragged case per family; which of the four exist for it (no 3x3 padding in a pointwise chain, no intermediate bf16 store
+# in an fp32 one or in transition1, no residual in transition1)
+MUTATIONS = {"bneck64": ((3, 19, 11), ("ring", "trunc", "drop", "shift_res")), "bb32": ((3, 9, 50), ("ring", "trunc", "drop", "shift_res")),
+             "bb64": ((3, 5, 26), ("ring", "trunc", "drop", "shift_res")), "dual_bf16": ((1, 1, 1000), ("trunc", "drop", "shift_res")),
+             "dual_f32": ((1, 1, 1000), ("drop", "shift_res")), "pwchain64": ((1, 1, 1000), ("drop", "shift_res")),
+             "pwchain128": ((1, 1, 1000), ("drop", "shift_res")), "htrans": ((3, 34, 18), ("drop",))}
 
 
 def _interpret(d: ce.Data) -> torch.Tensor:
@@ -130,3 +159,116 @@ def test_a_truncating_store_fails_the_rounding_case(name):
     share = (wrong.view(torch.int16) != d.expected().view(torch.int16)).double().mean().item()
     print(name, "a truncating store differs on", share)
     assert share >= 0.10
+
+
+# ---- fused launches: conditions, the per-conv chain of the descriptor interpreter, the four mutations -------------------------------------------
+def _interpret_chain(d: ce.FusedData) -> dict:
+    """The per-conv program of the block, launch by launch through conv_desc_cpu on TorchPacker's layouts, every buffer in the activation dtype."""
+    low = ce.lower_fused(d, TorchPacker(), "cpu", fused=False)
+    bufs, B = dict(low.bufs), d.case.B
+    for op in low.ops:
+        y = torch.full((B, op.desc.out_h, op.desc.out_w, op.desc.out_c), float("nan"), dtype=d.store_dtype)
+        conv_desc_cpu(op.desc, bufs[op.src], op.w, op.scale, op.shift, bufs[op.res] if op.res else None, y, B)
+        assert not torch.isnan(y).any(), op.name
+        bufs[op.dst] = y
+    return {n: bufs[b] for n, b in low.outs.items()}
+
+
+@pytest.mark.parametrize("case", FUSED_CASES, ids=lambda c: c.name)
+def test_fused_conditions_and_per_conv_chain_equals_the_chain_reference(case):
+    """Every fused case: its conditions hold, the per-conv chain of tests/desc_interp.py (packing, geometry and the place of every bf16 store,
+    independent of the float64 chain) stores the reference's bits, and the engine's builder lowers it to the one fused op the GPU module launches."""
+    d = ce.make_fused(case)
+    print(case.name, ce.fused_conditions(d))
+    for name, y in _interpret_chain(d).items():
+        want = d.expected(name)
+        assert y.dtype == want.dtype and y.shape == want.shape, (name, y.shape, want.shape)
+        diff = y.view(torch.int16 if y.dtype == torch.bfloat16 else torch.int32) != want.view(torch.int16 if y.dtype == torch.bfloat16 else torch.int32)
+        assert not bool(diff.any()), f"{name}: {int(diff.sum())} of {diff.numel()} differ, first at {tuple(diff.nonzero()[0].tolist())}"
+    low = ce.lower_fused(d, TorchPacker(), "cpu")
+    assert len(low.ops) == 1
+    print(case.name, "->", ce.fused_kernel_name(low, case.family))
+
+
+def test_the_many_tile_cases_have_more_tiles_than_compute_units():
+    for fam, case in MANY_TILES.items():
+        assert case in FUSED_CASES and ce.fused_tiles(case) > CUS and (case.H % ce.FUSED_TILES[fam][0] and case.W % ce.FUSED_TILES[fam][1]), case
+    assert ce.fused_tiles(MANY_TILES["bb32"], (8, 16)) > 2 * CUS           # the 8x16 kernel behind SP_BB32_W8=0 runs two workgroups per unit
+
+
+def _ring(t):
+    """Mask of the outermost ring of pixels of t [B, C, H, W]."""
+    m = torch.zeros(t.shape[-2:], dtype=torch.bool)
+    m[0], m[-1], m[:, 0], m[:, -1] = True, True, True, True
+    return m.expand_as(t)
+
+
+def _moved(d, m, name):
+    """Where the mutated reference `m` stores other bits than the true one."""
+    return m.ref[name].to(d.store_dtype) != d.ref[name].to(d.store_dtype)
+
+
+@pytest.mark.parametrize("family,mutation", [(f, m) for f, (_, ms) in MUTATIONS.items() for m in ms])
+def test_a_mutated_chain_differs_from_the_reference(family, mutation):
+    """The negative self-check, per chain family: a reference with one of the mistakes a fused kernel can make - the intermediate outside the image
+    not zero, an intermediate store that truncates, one term of a product dropped, the residual of the neighbouring pixel - stores other bits, on
+    at least the share of the outputs that makes the comparison sensitive to it.  Conditions on the inputs; no kernel runs here."""
+    case = ce.Fused(family, *MUTATIONS[family][0])
+    o = ce.fused_operands(case)
+    d = ce.fused_eval(case, o)
+    ce.fused_conditions(d)
+    if mutation == "drop":
+        term = (5, 3, 4 if o["w1" if family == "bneck64" else "w0"].shape[-1] == 3 else 0)
+        m = ce.fused_eval(case, o, drop=term)
+    else:
+        m = ce.fused_eval(case, o, **{mutation: True})
+    final = "y_hi" if family == "htrans" else "y"
+    moved = _moved(d, m, final)
+    if mutation == "ring":
+        share = moved[_ring(moved)].double().mean().item()
+        print(family, "padding bug moves", share, "of the border ring")
+        assert share >= 0.30
+    elif mutation == "trunc":
+        share = moved.double().mean().item()
+        print(family, "truncating intermediate stores move", share, "of all outputs")
+        assert share >= 0.25
+    elif mutation == "shift_res":
+        pos = d.pre[final] > 0
+        share = moved[pos].double().mean().item()
+        print(family, "the neighbour's residual moves", share, "of the positive outputs,", moved.double().mean().item(), "of all")
+        assert share >= 0.60
+    else:
+        ch = term[0]
+        only = lambda t: not bool(t[:, :ch].any()) and not bool(t[:, ch + 1:].any())
+        pix = lambda t: t[:, ch:ch + 1]                                    # [B, 1, H, W]: the pixels at which channel `ch` moved
+        if family == "bneck64":                                            # one product of the 3x3: t2 moves in that channel, y only at those pixels
+            src = m.inter["t2"] != d.inter["t2"]
+            assert only(src) and not bool((moved & ~pix(src)).any())
+        elif family in ("bb32", "bb64"):                                   # conv1: t moves in that channel, y only within one pixel of it
+            src = m.inter["t"] != d.inter["t"]
+            near = torch.nn.functional.max_pool2d(pix(src).double(), 3, 1, 1) > 0
+            assert only(src) and not bool((moved & ~near).any())
+        elif family.startswith("dual"):                                    # the shortcut's product: r and y move in that channel alone
+            src = m.inter["r"] != d.inter["r"]
+            assert only(src) and only(moved) and not bool((moved & ~src).any())
+        elif family.startswith("pwchain"):                                 # conv3: y moves in that channel, t_next only in those rows
+            assert only(moved)
+            nxt = _moved(d, m, "t_next")
+            assert bool(nxt.any()) and not bool((nxt & ~pix(moved)).any())
+        else:                                                              # transition1.0: y_hi in that channel, y_lo not at all
+            assert only(moved) and not bool(_moved(d, m, "y_lo").any())
+        share = moved.double().mean().item()
+        print(family, "one dropped term moves", share, "of all outputs,", int(moved.sum()), "elements")
+        assert int(moved.sum()) >= 1
+    assert not all(torch.equal(m.ref[n], d.ref[n]) for n in d.ref)
+
+
+def test_a_truncating_store_fails_transition1():
+    """transition1 has one store per output and no intermediate: a store that truncates must still change bits of both outputs."""
+    case = ce.Fused("htrans", *MUTATIONS["htrans"][0])
+    o = ce.fused_operands(case)
+    d, m = ce.fused_eval(case, o), ce.fused_eval(case, o, trunc=True)
+    for n in d.ref:
+        share = _moved(d, m, n).double().mean().item()
+        print(n, "a truncating store differs on", share)
+        assert share > 0
