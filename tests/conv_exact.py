@@ -15,6 +15,7 @@ import zlib
 from dataclasses import dataclass, replace
 from typing import Optional, Tuple
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
@@ -61,6 +62,12 @@ class Case:
     role: str = "index"                # "index": sums below 256, a change of one term changes the stored bf16 | "rounding": ties and inexact sums
     dtypes: Tuple[str, ...] = ("fp32", "bf16")
     w_even_bf16: Optional[int] = None  # the bf16 stem reads pixel pairs: its image width must be even
+    # ---- the detector's epilogues (fp32 only) ----
+    hardswish: bool = False            # SP_CONV_HARDSWISH: y = hardswish(scale * conv + shift), the residual added AFTER the activation
+    slice_of: Optional[Tuple[int, int]] = None     # SP_CONV_OUT_SLICE: (out_c, c0) - the launch writes channels [c0, c0 + c_out) of an out_c-channel tensor
+    scales: Optional[Tuple[float, ...]] = None     # per-channel powers of two to draw from instead of {0.5, 1, 2}: a hardswish case needs small values
+    head: Optional[Tuple[int, int]] = None         # (anchors, no): the detector's head conv - bias, no activation, every anchor's `no` rows padded
+    #                                                to engine.yolo_anchor_stride(no) with zero rows (c_out = anchors * that stride)
 
     def width(self, dtype: str) -> int:
         return self.w_even_bf16 if (dtype == "bf16" and self.w_even_bf16) else self.W
@@ -104,6 +111,31 @@ FORWARD_CASES = [
     Case("round_deconv_256", "deconv", 1, 7, 5, 256, 256, 4, 2, 1, 8, 8, scale=False, role="rounding"),
     Case("round_stem7", "stem", 2, 33, 47, 3, 64, 7, 2, 3, 16, 8, scale=False, role="rounding", w_even_bf16=46),
 ]
+
+# ---- the YOLOv5 detector's convolutions: hardswish (before the residual) and the channel-slice store, fp32 only ----------------------------------
+# Magnitudes of 1 and scales of 1/8 .. 1/2 keep the pre-activation v (exact: a multiple of 1/8) within a few units of 0, where hardswish is not
+# the identity; conditions() asserts the shares on the reference of each case.
+_HS = dict(kind="conv", x_mag=1, w_mag=1, hardswish=True, scales=(0.125, 0.25, 0.5), dtypes=("fp32",))
+_HS3 = dict(_HS, k=3, pad=1)
+DETECTOR_CASES = [
+    Case("hsw_pw_64_40", B=2, H=10, W=12, c_in=64, c_out=40, **_HS),                                      # M = 240 and N = 40 ragged against every tile
+    Case("hsw_pw_64_40_res", B=2, H=10, W=12, c_in=64, c_out=40, residual=True, **_HS),                   # the activation before the add
+    Case("hsw_slice_pw_64_40_of56_c8", B=2, H=10, W=12, c_in=64, c_out=40, slice_of=(56, 8), **_HS),
+    Case("slice_pw_64_64_of128_c64", "conv", 2, 10, 12, 64, 64, x_mag=3, w_mag=3, slice_of=(128, 64), dtypes=("fp32",)),   # the last pixel's slice ends the extent
+    Case("hsw_c3_12_32", B=2, H=9, W=7, c_in=12, c_out=32, **_HS3),                                       # Focus conv: c_in below a K tile
+    Case("hsw_c3s2_32_64", B=3, H=13, W=11, c_in=32, c_out=64, stride=2, **_HS3),                         # the downsampling convs, odd map
+    Case("hsw_c3_64_64_res", B=3, H=13, W=11, c_in=64, c_out=64, residual=True, **_HS3),                  # BottleNeck (batch 3: the plain kernel)
+    Case("hsw_c3_64_64_res_b70", B=70, H=3, W=2, c_in=64, c_out=64, residual=True, **_HS3),               # the same in the tap-skipping kernel
+    Case("hsw_slice_c3_64_64_of128_c64", B=70, H=3, W=2, c_in=64, c_out=64, slice_of=(128, 64), **_HS3),  # tiles straddle images; slice store
+    Case("hsw_pw_384_128", B=2, H=9, W=7, c_in=384, c_out=128, **_HS),                                    # the concat widths: six K tiles
+    # the 128-column tiles need n_pad % 128 == 0: the residual and the slice once more at 128 output channels
+    Case("hsw_pw_64_128_res", B=2, H=9, W=7, c_in=64, c_out=128, residual=True, **_HS),
+    Case("hsw_slice_pw_64_128_of192_c64", B=2, H=9, W=7, c_in=64, c_out=128, slice_of=(192, 64), **_HS),
+    Case("hsw_slice_c3_64_128_of192_c64", B=70, H=3, W=2, c_in=64, c_out=128, slice_of=(192, 64), **_HS3),
+    # the one detector conv without hardswish: 3 anchors x 6 columns at a stride of 8, bias, no scale
+    Case("head_pw_128_a3_no6", "conv", 2, 5, 7, 128, 24, x_mag=2, w_mag=2, scale=False, head=(3, 6), dtypes=("fp32",)),
+]
+FORWARD_CASES += DETECTOR_CASES
 FORWARD_IDS = [c.name for c in FORWARD_CASES]
 
 
@@ -123,9 +155,10 @@ class Data:
     scale: Optional[torch.Tensor]
     shift: Optional[torch.Tensor]
     res: Optional[torch.Tensor]        # [B, c_out, oh, ow]
-    pre: torch.Tensor                  # before ReLU, NCHW (after the pixel shuffle where flagged)
+    pre: torch.Tensor                  # before ReLU, NCHW (after the pixel shuffle where flagged); hardswish: the pre-activation v (no residual)
     step: torch.Tensor                 # what one term of magnitude 1 more or less adds to each element of `pre`: its channel's scale
     ref: torch.Tensor                  # the exact result, NCHW
+    bias: Optional[torch.Tensor] = None    # head cases: the bias per (anchor, column) before the padding (`shift` holds the padded vector)
 
     @property
     def store_dtype(self):
@@ -148,29 +181,72 @@ def _conv(c: Case, x, w):
     return F.conv2d(x, w, stride=c.stride, padding=c.pad, groups=c.groups)
 
 
-def make(c: Case, dtype: str) -> Data:
+def hardswish_f32(v: torch.Tensor, res: Optional[torch.Tensor] = None, *, act_after_res: bool = False, trunc_div: bool = False) -> torch.Tensor:
+    """The kernel's epilogue on an exact pre-activation `v` (float64 holding fp32 values), one IEEE fp32 operation at a time in the kernel's own
+    order (numpy: each operation rounds once): h = (v * clamp(v + 3, 0, 6)) / 6, then h + residual.  With v + 3 and the product exact
+    (conditions() asserts both) the division and the add round once each, so the bits are unique.  Returns float64 (-0.0 where v <= -3 and
+    nothing is added: -|v| * 0).  MUTATIONS for the negative self-check: `act_after_res` - hardswish(v + residual); `trunc_div` - the
+    quotient's last bit cleared."""
+    f = np.float32
+    a = v.numpy().astype(f)
+    assert np.array_equal(a.astype(np.float64), v.numpy())
+    r = None if res is None else res.numpy().astype(f)
+    if act_after_res:
+        a, r = a + r, None
+    q = (a * np.minimum(np.maximum(a + f(3), f(0)), f(6))) / f(6)
+    assert q.dtype == f
+    if trunc_div:
+        q = (q.view(np.int32) & ~np.int32(1)).view(f)
+    if r is not None:
+        q = q + r
+    return torch.from_numpy(q.astype(np.float64))
+
+
+def head_rows(t: torch.Tensor, anchors: int, no: int) -> torch.Tensor:
+    """[anchors * no, ...] -> [anchors * a_stride, ...]: every anchor's `no` rows followed by zero rows up to engine.yolo_anchor_stride(no)."""
+    a_stride = engine.yolo_anchor_stride(no)
+    out = torch.zeros((anchors, a_stride) + tuple(t.shape[1:]), dtype=t.dtype)
+    out[:, :no] = t.reshape((anchors, no) + tuple(t.shape[1:]))
+    return out.reshape((anchors * a_stride,) + tuple(t.shape[1:]))
+
+
+def make(c: Case, dtype: str, mutation: Optional[str] = None) -> Data:
+    """`mutation` (hardswish cases; the negative self-check of tests/test_conv_exact_host.py): "act_after_res" | "trunc_div"."""
     g = generator(c.name)
     W = c.width(dtype)
     x = ints((c.B, c.c_in, c.H, W), c.x_mag, g)
     wshape = (c.c_in, c.c_out, 4, 4) if c.kind == "deconv" else (c.c_out, c.c_in // c.groups, c.k, c.k)
+    if c.head:
+        assert c.c_out == c.head[0] * engine.yolo_anchor_stride(c.head[1]) and not c.scale and c.k == 1
+        wshape = (c.head[0] * c.head[1], c.c_in, 1, 1)
     w = ints(wshape, c.w_mag, g)
-    z = _conv(c, x, w)
-    scale = shift = res = None
+    z = _conv(c, x, head_rows(w, *c.head) if c.head else w)
+    scale = shift = res = bias = None
     bc = lambda v: v.view(1, -1, 1, 1)
     step = torch.ones_like(z)
     if c.scale:
-        scale = torch.tensor([0.5, 1.0, 2.0], dtype=torch.float64)[torch.randint(0, 3, (c.c_out,), generator=g)]
+        scale = torch.tensor(c.scales or (0.5, 1.0, 2.0), dtype=torch.float64)[torch.randint(0, len(c.scales or (0, 0, 0)), (c.c_out,), generator=g)]
         z, step = z * bc(scale), step * bc(scale)
     if c.shift:
-        shift = ints((c.c_out,), 4, g) + c.shift_bias
+        if c.head:
+            bias = ints((c.head[0] * c.head[1],), 4, g) + c.shift_bias
+            shift = head_rows(bias, *c.head)
+        else:
+            shift = ints((c.c_out,), 4, g) + c.shift_bias
         z = z + bc(shift)
+    v = z
     if c.residual:
         res = ints(tuple(z.shape), 4, g)
         z = z + res
+    if c.hardswish:
+        assert not c.relu and not c.pshuf
+        ref = hardswish_f32(v, res, **({mutation: True} if mutation else {}))
+        return Data(c, dtype, x, w, scale, shift, res, v, step, ref, bias)
+    assert mutation is None
     pre, ref = z, (torch.relu(z) if c.relu else z)
     if c.pshuf:
         pre, ref, step = F.pixel_shuffle(pre, 2), F.pixel_shuffle(ref, 2), F.pixel_shuffle(step, 2)
-    return Data(c, dtype, x, w, scale, shift, res, pre, step, ref + 0.0)
+    return Data(c, dtype, x, w, scale, shift, res, pre, step, ref + 0.0, bias)
 
 
 def bf16_low_bits(t: torch.Tensor) -> torch.Tensor:
@@ -189,6 +265,26 @@ def conditions(d: Data) -> dict:
     assert top < LIMIT, (c.name, top)                                     # exactness: every partial sum in every order is an integer below 2^24
     assert not bool((d.x == 0).any()) and not bool((d.w == 0).any())       # every product counts
     assert torch.equal(d.ref.float().double(), d.ref)                      # the exact result is an fp32 value
+    if c.hardswish or c.slice_of or c.head:
+        assert c.dtypes == ("fp32",) and not (c.slice_of and c.residual), c.name          # fp32-only epilogues; a slice takes no residual
+    if c.slice_of:
+        out_c, c0 = c.slice_of
+        assert c0 % 4 == 0 and c.c_out % 4 == 0 and out_c % 4 == 0 and c0 + c.c_out <= out_c, c.name
+    if c.hardswish:
+        # v is exact (above: integer sums below 2^24 times a power of two, plus an integer), and so are v + 3 and the product: the division
+        # and the residual add are the only roundings, once each
+        v = d.pre
+        assert torch.equal(v.float().double(), v)
+        for t in (v + 3, v * (v + 3), v * torch.clamp(v + 3, 0, 6)):
+            assert torch.equal(t.float().double(), t), c.name
+        out["above_minus_3"] = (v > -3).double().mean().item()
+        out["inside_pm_3"] = ((v > -3) & (v < 3)).double().mean().item()
+        assert out["above_minus_3"] >= 0.40, (c.name, out)                 # the activation does not blank the comparison
+        assert out["inside_pm_3"] >= 0.20, (c.name, out)                   # where the division is inexact and "residual first" differs
+        q = v * torch.clamp(v + 3, 0, 6) / 6
+        out["inexact_quotients"] = (q.float().double() != q).double().mean().item()
+        assert out["inexact_quotients"] >= 0.10, (c.name, out)             # the division really rounds
+        return out
     if c.role == "index":
         below = (d.pre.abs() < 256).double().mean().item()
         out["below_256"] = below
@@ -245,24 +341,38 @@ def lower(d: Data, packer, device) -> Lowered:
         x = d.x.permute(0, 2, 3, 1).contiguous().to(adt).to(device)
         if c.kind == "deconv":
             out = b.deconv_k4s2p1("input", dev(d.w), scale=dev(scale), shift=dev(shift), relu=c.relu, name=c.name)
+        elif c.head:                   # as engine.yolov5_program lowers a head: the padded rows and bias of engine._head_conv, no scale
+            wp, bp = engine._head_conv(dev(d.w), dev(d.bias), c.head[0], c.head[1], engine.yolo_head_columns(c.head[1], -1))
+            out = b.conv("input", wp, shift=b.packer.bias(bp), name=c.name)
         else:
             if c.residual:
                 b.p.shapes["res"] = tuple(d.res.shape[2:]) + (c.c_out,)
+            out_slice = None
+            if c.slice_of:             # the producers of a concat write their channel slices of one buffer (engine._cbr's `out`)
+                out_slice = (b.buffer("cat", d.ref.shape[2], d.ref.shape[3], c.slice_of[0]), c.slice_of[1])
             out = b.conv("input", dev(d.w), stride=c.stride, pad=c.pad, scale=dev(scale), shift=dev(shift), relu=c.relu,
-                         res="res" if c.residual else None, pixel_shuffle=c.pshuf, out_nchw=c.nchw, groups=c.groups, name=c.name)
+                         res="res" if c.residual else None, pixel_shuffle=c.pshuf, out_nchw=c.nchw, groups=c.groups, name=c.name,
+                         hardswish=c.hardswish, out_slice=out_slice)
     op = b.p.ops[-1]
     op.desc.batch = c.B
     if c.out_f32:
         op.desc.flags |= _lib.SP_CONV_OUT_F32
         op.direct = False
+    want_flags = (_lib.SP_CONV_HARDSWISH if c.hardswish else 0) | (_lib.SP_CONV_OUT_SLICE if c.slice_of else 0)
+    assert op.desc.flags & (_lib.SP_CONV_HARDSWISH | _lib.SP_CONV_OUT_SLICE) == want_flags, (c.name, op.desc.flags)
+    assert op.c0 == (c.slice_of[1] if c.slice_of else 0)
     res = None if d.res is None else d.res.permute(0, 2, 3, 1).contiguous().to(d.store_dtype).to(device)      # (read in the dtype of the store)
-    oh, ow, oc = b.p.shapes[out]
+    oh, ow, oc = b.p.shapes[out]       # a slice launch: the whole buffer (oc = out_c); the launch writes [c0, c0 + c_out) of it
+    assert oc == (c.slice_of[0] if c.slice_of else c.c_out if not c.pshuf else c.c_out // 4), (c.name, oc)
     return Lowered(op, b.p, x, res, (c.B, oc, oh, ow) if c.nchw else (c.B, oh, ow, oc))
 
 
 def candidates(low: Lowered, case: Case):
     """Every (tile_m, tile_n, kernel) the launch can run as (engine.Program._candidates); the in-place form belongs to the implicit GEMM."""
     cands = low.prog._candidates(_lib.lib(), low.op)
+    if case.hardswish or case.slice_of:
+        # the library runs these flags on the implicit GEMM alone: the engine must not offer the tuner anything else
+        assert cands and all(k[0] > 0 and k[2] == _lib.SP_CONV_KERNEL_IGEMM for k in cands), (case.name, cands)
     if case.inplace:
         cands = [k for k in cands if k[0] > 0 and k[2] == _lib.SP_CONV_KERNEL_IGEMM]
     return cands
@@ -290,6 +400,20 @@ def family(low: Lowered, cand, has_res: bool) -> tuple:
              _lib.SP_CONV_KERNEL_PW: "pw"}[cand[2]],)
 
 
+def detector_families(case: Case, fam: tuple) -> set:
+    """What a launch of a detector case adds to the coverage condition besides its kernel family `fam`: per implicit-GEMM tile "hsw", "slice"
+    (at c0 > 0) and "hsw_res"; for the tap-skipping kernel (at any tile) ("tapskip", "hsw") and ("tapskip", "slice")."""
+    tags = (["hsw"] if case.hardswish else []) + (["slice"] if case.slice_of and case.slice_of[1] > 0 else []) + \
+           (["hsw_res"] if case.hardswish and case.residual else [])
+    if fam[0] == "tapskip":
+        return {("tapskip", t) for t in tags if t != "hsw_res"}
+    return {(t, fam[1]) for t in tags} if fam[0] == "igemm" else set()
+
+
+def required_detector_families() -> set:
+    return {(t, tile) for t in ("hsw", "slice", "hsw_res") for tile in _lib.CONV_TILES} | {("tapskip", "hsw"), ("tapskip", "slice")}
+
+
 def required_families() -> set:
     need = {("igemm", t, dt) for t in _lib.CONV_TILES for dt in ("fp32", "bf16")}
     return need | {("ring",), ("ring_lw",), ("ring_lw4",), ("pw",), ("direct", 32), ("direct", 64), ("direct", 128)}
@@ -297,8 +421,8 @@ def required_families() -> set:
 
 def missing_families(seen: set) -> set:
     """Families of the coverage condition that `seen` lacks (the tap-skip kernel counts at any tile)."""
-    miss = required_families() - seen
-    if not any(f[0] == "tapskip" for f in seen):
+    miss = (required_families() | required_detector_families()) - seen
+    if not any(f[0] == "tapskip" and isinstance(f[1], tuple) for f in seen):
         miss.add(("tapskip",))
     return miss
 

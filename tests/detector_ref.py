@@ -132,6 +132,40 @@ def nms_np(pred, conf_thresh=0.1, iou_thresh=0.6, merge=False, agnostic=False, m
     return (out, cands) if return_candidates else out
 
 
+def nms_trace_np(boxes, scores, thr, limit=None):
+    """greedy_nms_np with its bookkeeping: (keep, order, suppressed) - `order` the candidate indices by rank, `suppressed` a list of
+    (rank of the suppressed candidate, rank of the FIRST kept box that suppresses it).  The scan stops like greedy_nms_np's at `limit` kept."""
+    order = np.lexsort((np.arange(len(scores)), -scores.astype(np.float64)))
+    keep, keep_rank, suppressed = [], [], []
+    for rank, i in enumerate(order):
+        hit = np.nonzero(_iou_f32(boxes[i], boxes[np.asarray(keep, dtype=np.int64)]) > np.float32(thr))[0] if keep else []
+        if len(hit):
+            suppressed.append((rank, keep_rank[hit[0]]))
+            continue
+        keep.append(int(i)); keep_rank.append(rank)
+        if limit is not None and len(keep) >= limit:
+            break
+    return np.asarray(keep, dtype=np.int64), order, suppressed
+
+
+# ---- head decode ------------------------------------------------------------------------------------------------------------------------
+def head_decode_torch(heads, anchors, no, a_stride, strides, anchor_wh, dtype=torch.float64):
+    """YOLOv5Head.forward's eval branch (yolov5.py:134-149) on the packed head outputs, evaluated in `dtype`: heads[l] is NHWC
+    [B, ny, nx, anchors * a_stride] with anchor a's `no` values at [a * a_stride, a * a_stride + no) (the columns between are never read);
+    anchor_wh [3][anchors][2].  Returns [B, N, no], rows ordered (level, anchor, y, x)."""
+    ag = torch.as_tensor(anchor_wh, dtype=dtype).view(3, anchors, 2)
+    z = []
+    for l, t in enumerate(heads):
+        B, ny, nx, _ = t.shape
+        v = t.to(dtype).view(B, ny, nx, anchors, a_stride)[..., :no].permute(0, 3, 1, 2, 4).sigmoid()
+        yv, xv = torch.meshgrid(torch.arange(ny), torch.arange(nx), indexing="ij")
+        g = torch.stack((xv, yv), 2).view(1, 1, ny, nx, 2).to(dtype)
+        xy = (v[..., 0:2] * 2. - 0.5 + g) * torch.as_tensor(strides[l], dtype=dtype)
+        wh = (v[..., 2:4] * 2) ** 2 * ag[l].view(1, anchors, 1, 1, 2)
+        z.append(torch.cat([xy, wh, v[..., 4:]], -1).reshape(B, -1, no))
+    return torch.cat(z, 1)
+
+
 # ---- torch forward of the reference network ---------------------------------------------------------------------------------------------
 def yolov5_forward_torch(sd, x, num_cls=80, strides=(8., 16., 32.)):
     """YOLOv5.forward (eval) in plain torch on `sd` (reference keys), fp32 NCHW RGB input -> [B, N, num_cls + 5]."""

@@ -3,6 +3,8 @@ interpreter (tests/desc_interp.conv_desc_cpu on TorchPacker's layouts) reproduce
 independent float64 convolution - the case table reaches every kernel family the GPU module must run, and the method catches what it is for: one
 dropped product at K = 4608, and a store that truncates.  The same for the fused launches (conv_exact.Fused): the tables of tests/test_gpu_fused_exact.py,
 the float64 chain against the per-conv chain of the interpreter, and four mutated chains that must store other bits."""
+import copy
+
 import pytest
 import torch
 
@@ -47,7 +49,11 @@ MUTATIONS = {"bneck64": ((3, 19, 11), ("ring", "trunc", "drop", "shift_res")), "
              "pwchain128": ((1, 1, 1000), ("drop", "shift_res")), "htrans": ((3, 34, 18), ("drop",))}
 
 
-def _interpret(d: ce.Data) -> torch.Tensor:
+def _interpret(d: ce.Data, c0_shift: int = 0) -> torch.Tensor:
+    """The lowered launch through the descriptor interpreter.  SP_CONV_HARDSWISH / SP_CONV_OUT_SLICE as include/simple_pose_hip.h documents them
+    (detector_ref.run_yolo_program_cpu does the same for the whole network): the plain launch of c_out channels, then the activation in fp32 - one
+    torch operation per IEEE operation, the divisor a tensor - then the residual, stored at channels [c0, c0 + c_out) of the out_c-channel
+    tensor, whose other channels stay NaN.  `c0_shift`: MUTATION - the slice lands that many channels further on."""
     low = ce.lower(d, TorchPacker(), "cpu")
     c, op = d.case, low.op
     x = low.x
@@ -56,9 +62,40 @@ def _interpret(d: ce.Data) -> torch.Tensor:
         x4[..., :3] = x.permute(0, 2, 3, 1)
         x = x4.to(torch.bfloat16 if d.dtype == "bf16" else torch.float32)
     y = torch.full(low.out_shape, float("nan"), dtype=torch.float64)
+    if op.desc.flags & (_lib.SP_CONV_HARDSWISH | _lib.SP_CONV_OUT_SLICE):
+        dd = copy.copy(op.desc)
+        dd.flags = op.desc.flags & ~(_lib.SP_CONV_HARDSWISH | _lib.SP_CONV_OUT_SLICE)
+        dd.out_c = dd.c_out
+        t = torch.full(low.out_shape[:3] + (dd.c_out,), float("nan"), dtype=torch.float64)
+        conv_desc_cpu(dd, x, op.w, op.scale, op.shift, None, t, c.B)
+        assert torch.equal(t.float().double(), t)
+        if op.desc.flags & _lib.SP_CONV_HARDSWISH:
+            v = t.float()
+            t = ((v * torch.clamp(v + 3.0, 0.0, 6.0)) / torch.full_like(v, 6.0)).double()
+        if low.res is not None:
+            t = (t.float() + low.res).double()
+        c0 = op.c0 + c0_shift
+        y[..., c0:c0 + dd.c_out] = t
+        return y
     conv_desc_cpu(op.desc, x, op.w, op.scale, op.shift, low.res, y, c.B)
     assert not torch.isnan(y).any()
     return y
+
+
+def _full(d: ce.Data) -> torch.Tensor:
+    """What the whole output tensor of the launch must hold (float64): d.stored(), for a slice launch inside NaN channels."""
+    want = d.stored()
+    if not d.case.slice_of:
+        return want
+    out_c, c0 = d.case.slice_of
+    full = torch.full(tuple(want.shape[:3]) + (out_c,), float("nan"), dtype=torch.float64)
+    full[..., c0:c0 + d.case.c_out] = want
+    return full
+
+
+def _same64(a, b):
+    """Bit equality of two float64 tensors, NaN and the sign of zero included."""
+    return torch.equal(a.contiguous().view(torch.int64), b.contiguous().view(torch.int64))
 
 
 @pytest.mark.parametrize("case,dtype", PAIRS + [(c, "fp32") for c in TAP_SKIP], ids=lambda v: v if isinstance(v, str) else v.name)
@@ -66,10 +103,14 @@ def test_conditions_and_interpreter_equals_the_integer_reference(case, dtype):
     d = ce.make(case, dtype)
     print(case.name, dtype, ce.conditions(d))
     y = _interpret(d)
-    want = d.stored()
-    diff = y != want
+    want = _full(d)
+    if case.hardswish or case.slice_of:    # the sign of a zero and the untouched channels count: compare the bits
+        diff = y.view(torch.int64) != want.view(torch.int64)
+    else:
+        diff = y != want
     assert not bool(diff.any()), f"{int(diff.sum())} of {diff.numel()} differ, first at {tuple(diff.nonzero()[0].tolist())}"
-    assert tuple(d.expected().shape) == tuple(y.shape) and d.expected().dtype == d.store_dtype
+    assert tuple(d.expected().shape) == tuple(d.stored().shape) and d.expected().dtype == d.store_dtype
+    assert tuple(y.shape[:-1]) == tuple(d.stored().shape[:-1]) or case.nchw
 
 
 def test_the_case_table_reaches_every_kernel_family():
@@ -87,6 +128,8 @@ def test_the_case_table_reaches_every_kernel_family():
             assert cands, case.name
             lib.sp_conv_set_tap_skip(1)
             fams = {ce.family(low, k, case.residual) for k in cands}
+            for f in set(fams):
+                fams |= ce.detector_families(case, f)
             if case in TAP_SKIP:
                 assert fams == {("tapskip", cands[0][:2])}, fams
                 lib.sp_conv_set_tap_skip(0)
@@ -119,6 +162,59 @@ def test_statistics_conditions(name):
     r = ce.backward_reference("conv", I, O, k, s, p, H, W, B, seed=3, mag=STATS[name])
     ce.backward_conditions(r)
     print(name, ce.stats_conditions(r["y"].permute(0, 2, 3, 1).reshape(-1, O), torch.bfloat16))
+
+
+# ---- the detector's epilogues ---------------------------------------------------------------------------------------------------------------------
+DETECTOR_3X3 = [c for c in ce.DETECTOR_CASES if c.k == 3]
+
+
+@pytest.mark.parametrize("case", DETECTOR_3X3, ids=lambda c: c.name)
+def test_detector_3x3_cases_resolve_to_the_tap_skipping_kernel_where_eligible(case):
+    """With the knob on, a 3x3 detector case whose c_in fills whole K tiles runs the tap-skipping kernel on every tile that holds at most two
+    images' worth of one position (batch >= tile_m / 2: the batch-70 cases on the 64- and 128-row tiles), every other launch - the Focus conv
+    with c_in = 12 among them - the plain kernel; with the knob off all run the plain kernel.  The library's own dispatch decides; nothing is
+    launched."""
+    lib = _lib.lib()
+    low = ce.lower(ce.make(case, "fp32"), TorchPacker(), "cpu")
+    cands = ce.candidates(low, case)
+    try:
+        lib.sp_conv_set_tap_skip(1)
+        on = {k: ce.family(low, k, case.residual)[0] for k in cands}
+        lib.sp_conv_set_tap_skip(0)
+        off = {ce.family(low, k, case.residual)[0] for k in cands}
+    finally:
+        lib.sp_conv_set_tap_skip(1)
+    want = {k: "tapskip" if (case.c_in % 32 == 0 and case.B >= k[0] // 2) else "igemm" for k in cands}
+    assert on == want and off == {"igemm"}, (case.name, on, off)
+    if case.B == 70:
+        assert "tapskip" in on.values() and "igemm" in on.values()          # (256-row tiles: 70 < 128)
+
+
+@pytest.mark.parametrize("case", [c for c in ce.DETECTOR_CASES if c.hardswish], ids=lambda c: c.name)
+def test_a_mutated_hardswish_epilogue_differs_from_the_reference(case):
+    """The negative self-check for the detector's epilogue: the activation applied after the residual, a quotient whose last bit is cut off, and
+    a slice that lands four channels further on each store other bits than the reference, on a share of the outputs that makes the
+    comparison sensitive to it."""
+    d = ce.make(case, "fp32")
+    bits = lambda t: t.float().contiguous().view(torch.int32)
+    m = ce.make(case, "fp32", mutation="trunc_div")
+    share = (bits(m.ref) != bits(d.ref)).double().mean().item()
+    print(case.name, "a truncated quotient moves", share)
+    assert share >= (0.02 if case.residual else 0.05)            # (with a residual, the sum's rounding hides most cut bits)
+    if case.residual:
+        m = ce.make(case, "fp32", mutation="act_after_res")
+        inside = (d.pre.abs() < 3)
+        share = (bits(m.ref) != bits(d.ref))[inside].double().mean().item()
+        print(case.name, "activation after the residual moves", share, "of the outputs with |v| < 3")
+        assert share >= 0.90
+    if case.slice_of:
+        out_c, c0 = case.slice_of
+        by = 4 if c0 + case.c_out + 4 <= out_c else -4                     # (towards the side that has room)
+        y, moved = _interpret(d), _interpret(d, c0_shift=by)
+        assert _same64(y, _full(d)) and not _same64(moved, _full(d))
+        differ = (moved.view(torch.int64) != y.view(torch.int64)).any(0).any(0).any(0)
+        lo, hi = min(c0, c0 + by), max(c0, c0 + by)                        # the four channels that change hands at either end of the slice
+        assert bool(differ[lo:hi].all()) and bool(differ[lo + case.c_out:hi + case.c_out].all())
 
 
 # ---- the method catches what it is for ----------------------------------------------------------------------------------------------------------

@@ -1,6 +1,7 @@
 """Every convolution launcher against an exact integer reference, bit for bit (tests/conv_exact.py): small integer operands make every fp32
 partial sum exact in any order, so a float64 convolution on the CPU predicts every stored bit of every launch - forward through sp_conv2d_fwd /
-sp_conv3x3_direct on every (tile, kernel) the tuner may pick, input and weight gradients through train.ConvT, the grouped launches and the
+sp_conv3x3_direct on every (tile, kernel) the tuner may pick (the detector's hardswish / channel-slice epilogues among them: the activation's
+one division and the residual add round once each on an exact pre-activation, so their bits are unique too), input and weight gradients through train.ConvT, the grouped launches and the
 BatchNorm statistics epilogue.  There is no tolerance in this module: every comparison is torch.equal on the stored bits."""
 import types
 
@@ -91,6 +92,10 @@ class _Sweep:
             _lib.check(fn(P(low.x), P(x), case.B, 3, case.H, case.width(dtype), st), "to_nhwc4")
         want = d.expected()
         n = want.numel()
+        out_c, c0 = case.slice_of or (case.c_out, 0)
+        if case.slice_of:                              # the guarded buffer is the whole out_c-channel tensor; the launch gets channel c0 of it
+            n = n // case.c_out * out_c
+            assert tuple(low.out_shape) == tuple(want.shape[:3]) + (out_c,) and op.c0 == c0
         cands = [only] if only else ce.candidates(low, case)
         assert cands, case.name
         for cand in cands:
@@ -105,9 +110,21 @@ class _Sweep:
                 _lib.check(lib.sp_conv3x3_direct(desc, P(x), P(op.w), P(op.scale), P(op.shift), P(res), P(y), st), what)
             else:
                 desc.tile_m, desc.tile_n, desc.kernel = cand
-                _lib.check(lib.sp_conv2d_fwd(desc, P(x), P(op.w), P(op.scale), P(op.shift), P(res), P(y), st), what)
-            _same_bits(_take(y, n, want.shape, what), want, what)
+                _lib.check(lib.sp_conv2d_fwd(desc, P(x), P(op.w), P(op.scale), P(op.shift), P(res), P(y) + 4 * c0, st), what)
+            if case.slice_of:
+                torch.cuda.synchronize()
+                full = y[:n].view(low.out_shape)
+                outside = torch.cat([full[..., :c0], full[..., c0 + case.c_out:]], -1)
+                prefill = _bits(torch.full((1,), float("nan"), dtype=d.store_dtype, device=DEV))
+                assert bool((_bits(y[n:]) == prefill).all()), f"{what}: stored behind the tensor"
+                assert bool((_bits(outside) == prefill).all()), f"{what}: stored outside channels [{c0}, {c0 + case.c_out})"
+                got = full[..., c0:c0 + case.c_out]
+                assert not bool(torch.isnan(got).any()), f"{what}: elements of the slice left unwritten"
+                _same_bits(got, want, what)
+            else:
+                _same_bits(_take(y, n, want.shape, what), want, what)
             self.seen.add(fam)
+            self.seen |= ce.detector_families(case, fam)
         return len(cands)
 
 
@@ -137,15 +154,41 @@ def test_tap_skipping_on_and_off_store_the_exact_bits(h, w, tile):
     _SWEEP.run(case, "fp32", cand, 0)
 
 
+DETECTOR_3X3 = [c for c in ce.DETECTOR_CASES if c.k == 3]
+
+
+@pytest.mark.parametrize("case", DETECTOR_3X3, ids=lambda c: c.name)
+def test_detector_3x3_tap_skipping_on_and_off_store_the_exact_bits(case):
+    """The detector's 3x3 convolutions (hardswish, residual after it, slice store) on every tile with the tap-skipping kernel allowed and with
+    the full K loop.  The batch-70 cases resolve to conv_igemm_tapskip_kernel on the tiles of up to 128 rows (batch >= tile_m / 2), the
+    Focus conv (c_in = 12 fills no K tile) and the small batches to the plain kernel: asserted on the library's own dispatch."""
+    low = ce.lower(ce.make(case, "fp32"), engine.HipPacker(), DEV)
+    lib = _lib.lib()
+    for cand in ce.candidates(low, case):
+        low.op.desc.tile_m, low.op.desc.tile_n, low.op.desc.kernel = cand
+        lib.sp_conv_set_tap_skip(1)
+        name = _lib.conv_kernel_name(low.op.desc, case.residual)
+        skips = case.c_in % 32 == 0 and case.B >= cand[0] // 2
+        assert name.startswith("conv_igemm_tapskip_kernel<" if skips else "conv_igemm_kernel<"), (cand, name)
+        lib.sp_conv_set_tap_skip(0)
+        assert _lib.conv_kernel_name(low.op.desc, case.residual).startswith("conv_igemm_kernel<")
+    ran = _SWEEP.run(case, "fp32", None, 1), _SWEEP.run(case, "fp32", None, 0)
+    print(f"{case.name}: {ran[0]} launches with tap skipping allowed, {ran[1]} without, all bit-exact")
+
+
 def test_every_kernel_family_ran():
     """The coverage condition: over the whole table each implicit-GEMM tile in both dtypes, the tap-skipping kernel, the three ring kernels, the
-    streaming 1x1 kernel and the direct kernel at 32, 64 and 128 channels stored exact bits (cases that have not run yet run here)."""
+    streaming 1x1 kernel and the direct kernel at 32, 64 and 128 channels stored exact bits, and so did the detector's epilogues on every fp32
+    tile and in the tap-skipping kernel (cases that have not run yet run here)."""
     for case, dtype in PAIRS:
         _SWEEP.run(case, dtype)
     for h, w, tile in TAP_SKIP:
         _SWEEP.run(ce.tap_skip_case(h, w, tile), "fp32", (tile[0], tile[1], _lib.SP_CONV_KERNEL_IGEMM), 1)
+    # the detector's epilogues: every fp32 tile stored exact bits with hardswish, with a slice at c0 > 0 and with hardswish + residual, the
+    # tap-skipping kernel with hardswish and with a slice (conv_exact.required_detector_families)
     missing = ce.missing_families(_SWEEP.seen)
     assert not missing, missing
+    assert ce.required_detector_families() <= _SWEEP.seen
     print(sorted(map(str, _SWEEP.seen)))
 
 
