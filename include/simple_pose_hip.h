@@ -275,7 +275,12 @@ int sp_se_gate_add_relu_nhwc_bf16(const void* x, const void* gate_logits, const 
 /* BasicKeyPointDecoder.heat_map_to_axis (:11-24): coords [B,J,2], max_val [B,J] */
 int sp_heat_map_to_axis(const float* heat_nchw, int batch, int joints, int h, int w, float* coords, float* max_val,
                         void* stream);
-/* GaussTaylorKeyPointDecoder.__call__ (:62-107), kernel_size odd <= 15; trans_inv [B,2,3]; kps [B,J,2]; max_val [B,J] */
+/* GaussTaylorKeyPointDecoder.__call__ (:62-107), kernel_size odd <= 15; trans_inv [B,2,3]; kps [B,J,2]; max_val [B,J].
+ * One workgroup stages a whole map in LDS: with p = kernel_size / 2 and PW = ((ceil(w / 12) * 12 + kernel_size + 6) / 4) * 4 + 4 it needs
+ * ((h + 2 p) * PW + h * w) * 4 B, at most 160 KiB less 32 B (more than 64 KiB is opted in per device on first use).  kernel_size 11:
+ * 64x48 32,416 B, 96x72 (384x288 inputs) 66,656 B, 128x96 113,184 B; 160x120 (172,000 B) is refused with SP_EINVAL and the byte count.
+ * sp_heat_map_to_axis and sp_decode_basic stage h * ceil(w / 4) * 16 B under the same limit.  A NaN tap stays a NaN through the clamp
+ * (torch.clamp), so a map whose maximum is +inf decodes to NaN key points as in the reference. */
 int sp_decode_gauss_taylor(const float* heat_nchw, const float* trans_inv, int batch, int joints, int h, int w,
                            int kernel_size, float* kps, float* max_val, void* stream);
 /* BasicKeyPointDecoder.__call__ (:26-52) */

@@ -10,6 +10,8 @@ is committed - never reference source.  Fixture inventory
   g2_duc_fwd.npz     same for R50-DUC
   g4_decode.npz      decoders (GaussTaylor + Basic + heat_map_to_axis) on: Gaussian maps + noise, noise-like
                      maps, edge cases; identity-scale and random trans_inv
+  g4b_decode_shapes.npz  the same three decoders at eleven other (map size, kernel size) pairs, 1 x 1 to 128 x 96, on hand-built maps
+                     (--only-decode-shapes regenerates this file alone, byte for byte)
   g1s_dconv_se_fwd.npz  ResNet50-DConv + SELayer (reduction=True) eval forward, B=1, + key list
   g3_hrnet_w32_fwd.npz  HRNet-W32 eval forward, B=1, + the reference's state_dict key/shape list
   g7_next.npz        HeatMapAcc values and collate_fn normalisation
@@ -313,8 +315,126 @@ def gen_decode(ns, net_maps):
     print("g4_decode.npz", {k: v.shape for k, v in out.items() if k.endswith("gt_kps")})
 
 
+DECODE_SHAPES = ((96, 72, 11), (72, 96, 11), (128, 96, 11), (96, 72, 15), (80, 56, 13), (32, 24, 1), (17, 13, 3), (40, 52, 7), (5, 4, 3),
+                 (3, 50, 5), (1, 1, 1))
+
+
+def decode_shape_maps(H, W):
+    """Hand-built [N,H,W] maps in the manner of edge_maps() for one heat-map size; a kind the size does not admit is left out.  Bumps are
+    sigma = 2 Gaussians cut to a 13 x 13 window (a full one would not compress: the fixture has to stay small)."""
+    yy, xx = np.mgrid[0:H, 0:W].astype(np.float64)
+
+    def gauss(cx, cy, amp=1.0):
+        g = amp * np.exp(-((xx - cx) ** 2 + (yy - cy) ** 2) / 8.0)
+        g[(np.abs(xx - np.round(cx)) > 6) | (np.abs(yy - np.round(cy)) > 6)] = 0.0
+        return g.astype(np.float32)
+
+    maps, names = [], []
+
+    def add(name, m):
+        maps.append(np.ascontiguousarray(m, np.float32)); names.append(name)
+
+    xm, ym = W // 2, H // 2
+    add("interior_gauss", gauss(0.46 * W + 0.37, 0.52 * H - 0.19, 0.9))
+    add("all_zero", np.zeros((H, W)))
+    add("all_negative", -gauss(0.4 * W + 0.3, 0.6 * H + 0.2) - 0.5)
+    add("constant_positive", np.full((H, W), 0.5))
+    # exact ties, the first index has to win.  d = 2: one float4 of the vector staging loop; 64: two waves of the scalar loop; 256: two
+    # waves of the vector loop / one thread's next iteration in the scalar loop; 1024: one thread's next iteration in the vector loop
+    for d in (2, 64, 256, 1024):
+        first = 4 * ((H * W // 3) // 4)
+        if first + d < H * W:
+            m = np.zeros(H * W); m[first] = 2.0; m[first + d] = 2.0
+            add(f"tie_{d}_apart", m.reshape(H, W))
+    # peaks on both sides of the two refinement guards (Basic: < W - 1, GaussTaylor: < W - 2)
+    for xi in sorted({x for x in (1, 2, W - 3, W - 2) if 0 <= x < W}):
+        add(f"peak_x_{xi}", gauss(xi + 0.2, ym - 0.3))
+    for yi in sorted({y for y in (1, 2, H - 3, H - 2) if 0 <= y < H}):
+        add(f"peak_y_{yi}", gauss(xm - 0.3, yi + 0.2))
+    # edge_maps()'s clamp plateau at this size: the raw maximum sits in a block whose blurred value is negative while the blurred maximum
+    # is positive -> every tap clamps to 1e-10, L is flat, det == 0, no refinement (pose_metrics.py:94)
+    if H >= 40 and W >= 32:
+        yc, xc, y1, x1 = H * 30 // 64, W * 20 // 48, H * 45 // 64, W * 28 // 48
+        m = np.zeros((H, W))
+        m[yc - 6:yc + 7, xc - 6:xc + 7] = -5.0
+        m[yc, xc] = 10.0
+        m[y1:y1 + 15, x1:x1 + 15] = 5.0
+        add("clamp_plateau_det0", m)
+    m = gauss(xm + 0.3, ym + 0.4); m[H // 3, W // 3] = np.nan
+    add("single_nan", m)
+    m = gauss(xm + 0.3, ym + 0.4); m[ym, xm] = np.inf
+    add("inf_at_peak", m)
+    return np.stack(maps), names
+
+
+def _savez_fixed(path, arrays):
+    """np.savez_compressed with every member's time stamp fixed, so that the file regenerates byte for byte."""
+    import io
+    import zipfile
+    with zipfile.ZipFile(path, "w", zipfile.ZIP_DEFLATED, compresslevel=9) as zf:
+        for name in sorted(arrays):
+            buf = io.BytesIO()
+            np.lib.format.write_array(buf, np.asanyarray(arrays[name]), allow_pickle=False)
+            info = zipfile.ZipInfo(name + ".npy", date_time=(1980, 1, 1, 0, 0, 0))
+            info.compress_type = zipfile.ZIP_DEFLATED
+            info.external_attr = 0o644 << 16
+            zf.writestr(info, buf.getvalue(), compresslevel=9)
+
+
+def gen_decode_shapes(ns):
+    """g4b_decode_shapes.npz: the reference's three decoders at other map sizes and kernel sizes than G4's 64 x 48 / 11, on hand-built maps
+    (decode_shape_maps) in batches of B = 2, J = 3.  Stored per size: the maps (padded to a multiple of six with the first map) and their
+    names; per (size, kernel size): heat_map_to_axis, Basic and GaussTaylor outputs under both trans_inv sets.  A map on which the
+    reference raises is left out of the size and listed under `<size>/raised`."""
+    pm = ns.pose_metrics
+    basic = pm.BasicKeyPointDecoder()
+    out = {"shapes": np.array(DECODE_SHAPES, np.int32)}
+    B, J = 2, 3
+    tinvs = (("ident4", synth.trans_inv_batch(B)), ("rand", synth.trans_inv_batch(B, seed=21)))
+
+    def run(maps, ks):
+        res = {}
+        gt = pm.GaussTaylorKeyPointDecoder(kernel_size=ks, num_joints=J)
+        co, mv = pm.BasicKeyPointDecoder.heat_map_to_axis(torch.from_numpy(maps.copy()))
+        res["axis"], res["axis_max"] = co.numpy(), mv.numpy()
+        for tname, tinv in tinvs:
+            hm_t = torch.from_numpy(maps.copy())
+            kps, mv = gt(hm_t, torch.from_numpy(tinv))
+            assert torch.equal(hm_t.view(torch.int32), torch.from_numpy(maps).view(torch.int32)), "decoder mutated its input"
+            res[f"{tname}/gt_kps"], res[f"{tname}/gt_max"] = kps.numpy(), mv.numpy()
+            kps, mv = basic(torch.from_numpy(maps.copy()), torch.from_numpy(tinv))
+            res[f"{tname}/basic_kps"] = kps.numpy()
+        return res
+
+    for H, W, ks in DECODE_SHAPES:
+        size = f"{H}x{W}"
+        em, names = decode_shape_maps(H, W)
+        keep, raised = [], []
+        for i, n in enumerate(names):                        # the reference decides what a NaN / inf map gives; one it raises on leaves
+            try:
+                run(np.repeat(em[i][None], B * J, 0).reshape(B, J, H, W), ks)
+                keep.append(i)
+            except Exception as e:  # noqa: BLE001
+                raised.append(f"{n}@ks{ks}: {type(e).__name__}")
+        assert not raised or all(n.split("@")[0] in ("single_nan", "inf_at_peak") for n in raised), raised
+        em, names = em[keep], [names[i] for i in keep]
+        pad = (-len(em)) % (B * J)
+        em = np.concatenate([em, np.repeat(em[:1], pad, 0)]).reshape(-1, B, J, H, W)
+        if f"{size}/maps" in out:                            # 96 x 72 is decoded at two kernel sizes: one set of maps
+            assert np.array_equal(out[f"{size}/maps"].view(np.int32), em.view(np.int32)) and not raised
+        out[f"{size}/maps"], out[f"{size}/names"] = em, np.array(names)
+        out[f"{size}/raised"] = np.array(raised if raised else [""])
+        for g in range(em.shape[0]):
+            for k, v in run(em[g], ks).items():
+                out[f"{size}/ks{ks}/{g}/{k}"] = v
+    path = os.path.join(GOLD, "g4b_decode_shapes.npz")
+    _savez_fixed(path, out)
+    print("g4b_decode_shapes.npz", os.path.getsize(path), "bytes;", {f"{h}x{w}": out[f"{h}x{w}/maps"].shape[0] for h, w, _ in DECODE_SHAPES},
+          "raised:", [r for h, w, _ in DECODE_SHAPES for r in out[f"{h}x{w}/raised"] if r])
+
+
 def gen_encode(ns):
-    refine = ns.transforms.RefineSimpleTransform.get_heat_map
+    refine =ns.transforms.RefineSimpleTransform.get_heat_map
     basic = ns.transforms.BasicSimpleTransform.get_heat_map
     # heat-map-px joints: interior fractional, out of range, trunc-toward-zero band (-7,-6], vis=0
     special = np.array([
@@ -528,9 +648,13 @@ def main():
     if "--only-train-b8" in sys.argv:      # (round 6 addition)
         gen_train_b8(ns)
         return
+    if "--only-decode-shapes" in sys.argv:
+        gen_decode_shapes(ns)
+        return
     hm = gen_forward(ns)  # returns the DUC maps last; reload dconv maps for the decoder set
     net_maps = np.load(os.path.join(GOLD, "g1_dconv_fwd.npz"))["heat_maps"]
     gen_decode(ns, net_maps)
+    gen_decode_shapes(ns)
     gen_encode(ns)
     gen_hrnet(ns)
     gen_se(ns)

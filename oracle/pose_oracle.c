@@ -85,6 +85,8 @@ static void blur_dense(const float* h, const float* k2d, int ks, int H, int W, f
 }
 
 static inline float log_cr(float v) { return (float)log((double)v); }
+/* torch.clamp(min=lo) (:73): a NaN stays a NaN (fmaxf would return lo), e.g. inf * inf / inf at a map whose maximum is +inf */
+static inline float clamp_min_(float v, float lo) { return isnan(v) ? v : fmaxf(v, lo); }
 
 /* einsum("bcd,bad->bca", [x,y,1], trans_inv[b]) : metrics/pose_metrics.py:50-51,105-106 */
 static inline void affine_out(const float* t /* [2,3] */, float x, float y, float* out2) {
@@ -111,7 +113,7 @@ void sp_oracle_decode_gauss_taylor(const float* heat, const float* trans_inv, in
         int xi = (int)cx, yi = (int)cy;                        /* :76 .long() */
         if (xi > 1 && xi < W - 2 && yi > 1 && yi < H - 2) {    /* :78 */
             /* L(y,x) = log(clamp(hb*ori_max/blur_max, 1e-10))     :73 */
-#define L_(yy, xx) log_cr(fmaxf((hb[(yy) * W + (xx)] * mx) / bmax, 1e-10f))
+#define L_(yy, xx) log_cr(clamp_min_((hb[(yy) * W + (xx)] * mx) / bmax, 1e-10f))
             float c = L_(yi, xi);
             float dx = 0.5f * (L_(yi, xi + 1) - L_(yi, xi - 1));                         /* :80-81 */
             float dy = 0.5f * (L_(yi + 1, xi) - L_(yi - 1, xi));                         /* :82-83 */

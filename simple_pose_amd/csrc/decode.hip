@@ -18,6 +18,7 @@ namespace {
 
 constexpr int MAX_KS = 15;
 constexpr int STRIP = 12;  // blurred outputs per thread per strip
+constexpr size_t STATIC_LDS = 4 * sizeof(float) + 4 * sizeof(int);  // red_v + red_i, next to the dynamic image
 
 struct BlurWeights {
     float k[MAX_KS * MAX_KS];
@@ -36,6 +37,8 @@ struct DecodeArgs {
 };
 
 __device__ __forceinline__ float log_cr(float v) { return (float)log((double)v); }
+// torch.clamp(min=lo): a NaN stays a NaN (fmaxf would return lo) - inf * inf / inf at a map whose maximum is +inf
+__device__ __forceinline__ float clamp_min(float v, float lo) { return (v != v) ? v : fmaxf(v, lo); }
 
 template <int KS>
 __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a, const BlurWeights bw) {
@@ -174,7 +177,7 @@ __global__ __launch_bounds__(256) void decode_kernel(const DecodeArgs a, const B
             cy = cy + sy * 0.25f;
         }
     } else if (xi > 1 && xi < W - 2 && yi > 1 && yi < H - 2) {       // :78
-#define L_(yy, xx) log_cr(fmaxf((hb[(yy) * W + (xx)] * mx) / bmax, 1e-10f))  /* :73 */
+#define L_(yy, xx) log_cr(clamp_min((hb[(yy) * W + (xx)] * mx) / bmax, 1e-10f))  /* :73 */
         const float c = L_(yi, xi);
         const float dx = 0.5f * (L_(yi, xi + 1) - L_(yi, xi - 1));                       // :80-81
         const float dy = 0.5f * (L_(yi + 1, xi) - L_(yi - 1, xi));                       // :82-83
@@ -235,12 +238,18 @@ int launch_decode(const float* heat, const float* trans_inv, int B, int J, int H
         a.PW = ((W + 3) / 4) * 4;
         lds = (size_t)H * a.PW * sizeof(float);
     }
-    SP_REQUIRE(lds <= 64 * 1024, "%s: heat map %dx%d needs %zu B of LDS (> 64 KiB)", who, H, W, lds);
+    // one workgroup holds the whole map: up to the CU's 160 KiB (the kernel's own red_v / red_i take 32 B of it).  GaussTaylor at ks = 11:
+    // 64x48 needs 32,416 B, 96x72 (384x288 inputs) 66,656 B, 128x96 113,184 B; 160x120 (172,000 B) is refused
+    SP_REQUIRE(lds + STATIC_LDS <= 160 * 1024, "%s: heat map %dx%d needs %zu B of LDS (> 160 KiB, one workgroup's limit)", who, H, W, lds);
+    const bool big = lds > 64 * 1024;   // beyond 64 KiB a kernel has to be opted in (per instantiation and device), as the conv launchers do
     const dim3 grid(B * J), block(256);
-    if (mode == MODE_GAUSS_TAYLOR && ks == 11)
+    if (mode == MODE_GAUSS_TAYLOR && ks == 11) {
+        if (big && sp_reserve_lds<&decode_kernel<11>>((int)lds, who)) return SP_ELAUNCH;
         hipLaunchKernelGGL(decode_kernel<11>, grid, block, lds, stream, a, bw);
-    else
+    } else {
+        if (big && sp_reserve_lds<&decode_kernel<0>>((int)lds, who)) return SP_ELAUNCH;
         hipLaunchKernelGGL(decode_kernel<0>, grid, block, lds, stream, a, bw);
+    }
     return sp_check_launch(who);
 }
 
