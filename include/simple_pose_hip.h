@@ -876,6 +876,34 @@ int sp_track_smooth(const double* kps, const float* box, const int32_t* track_id
                     double beta, double d_cutoff, double max_gap, double in_vis_thre, int32_t* s_id, double* s_x, double* s_dx, double* s_t,
                     int32_t* s_n, double* kps_smooth, void* stream);
 
+/* The three tracker entries for `images` (1 .. 256) video streams in ONE call, with a launch count that does not depend on `images`.  (No new
+ * ABI version: these are additions.)  The state is stream-major: every state array of the single-image entry gains a leading [images]
+ * dimension - t_id / t_age / t_miss [images, slots], t_kps [images, slots, joints, 3], t_area / t_conf [images, slots], next_id [images] (ids
+ * start at 1 per stream and are never reused within a stream), similarity [images, slots, slots], s_id [images, slots], s_x / s_dx [images,
+ * slots, joints, 2], s_t / s_n [images, slots, joints], now_dev double [images] (one time per stream, in DEVICE memory).  Image s reads the
+ * rows keep[seg[s] .. seg[s] + n_s) of the shared kps / area / box [rows, ...] - what sp_topdown_plan, sp_pose_rescore and sp_oks_nms leave
+ * behind for a batch - with n_s = keep_count[s] clamped as the single-image entries clamp it (to 0, to `slots`, to rows - seg[s]); keep_count
+ * and seg hold at least `images` entries.  Per stream the arithmetic, the greedy order and the tie rules are the single-image entry's (the
+ * same kernels: the single-image entries are images = 1 calls), so every stream's result equals it bit for bit; streams never read each
+ * other's state.  All are capturable, without copy or synchronisation, and work with zero tracks, zero poses and empty segments.
+ * sp_track_associate_images: track_id int32 [rows] gets the id of every kept row of every image and 0 for every other row; the kept rows of
+ *   different images are distinct rows (sp_oks_nms's are).  Two launches: a grid over (pairs, images), then one workgroup per image.
+ * sp_track_boxes_images: det fp32 [images, max_det, 6] and counts [images] under sp_track_boxes' rules per stream (rows counts[s] .. slots-1
+ *   of block s zeroed, rows from `slots` on untouched); img_w and img_h are shared.  One launch, one workgroup per image.
+ * sp_track_smooth_images: a row is filtered with the state, the tracks (t_id block) and the time of the image that kept it (the lowest such
+ *   image); every other row is the raw row.  One launch, one 64-lane workgroup per row. */
+int sp_track_associate_images(const double* kps, const double* area, const float* box, const int32_t* keep, const int32_t* keep_count,
+                              const int32_t* seg, int images, int rows, int joints, const double* sigmas_host, double match_thre, int max_age,
+                              int slots, int32_t* t_id, int32_t* t_age, int32_t* t_miss, double* t_kps, double* t_area, float* t_conf,
+                              int32_t* next_id, double* similarity, int32_t* track_id, void* stream);
+int sp_track_boxes_images(const int32_t* t_id, const int32_t* t_miss, const double* t_kps, const float* t_conf, int images, int slots, int joints,
+                          float in_vis_thre, float box_expand, float cls, int img_w, int img_h, int max_det, float* det, int32_t* counts,
+                          void* stream);
+int sp_track_smooth_images(const double* kps, const float* box, const int32_t* track_id, const int32_t* keep, const int32_t* keep_count,
+                           const int32_t* seg, int images, int rows, int joints, const int32_t* t_id, int slots, const double* now_dev,
+                           double min_cutoff, double beta, double d_cutoff, double max_gap, double in_vis_thre, int32_t* s_id, double* s_x,
+                           double* s_dx, double* s_t, int32_t* s_n, double* kps_smooth, void* stream);
+
 /* ---- overlay: the kept poses of one image drawn into it - boxes, limbs, joints, coloured by person (track id) or by part ------------------
  * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] in and out, 1 <= h, w <= 16384; it reads exactly what sp_oks_nms (and
  * sp_track_associate) leave behind: rows keep[seg[image] .. seg[image] + keep_count[image]) of kps [rows, joints, 3] / box fp32 [rows, 5] /

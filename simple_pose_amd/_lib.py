@@ -262,6 +262,11 @@ SYMBOLS = {
     "sp_track_boxes": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
     "sp_track_smooth": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, _P, c_int, _P, c_double, c_double, c_double, c_double, c_double, _P, _P, _P,
                                 _P, _P, _P, _P]),
+    "sp_track_associate_images": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, _P, _P, _P, _P, _P,
+                                          _P, _P, _P, _P, _P]),
+    "sp_track_boxes_images": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, c_float, c_int, c_int, c_int, _P, _P, _P]),
+    "sp_track_smooth_images": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, c_int, _P, c_int, _P, c_double, c_double, c_double, c_double, c_double, _P,
+                                       _P, _P, _P, _P, _P, _P]),
     "sp_jpeg_parse": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32]),
     "sp_jpeg_decode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int, _P]),
     "sp_jpeg_parse_scans": (c_int, [_P, c_int64, ctypes.POINTER(JpegDesc), _P, c_int32, ctypes.POINTER(c_int32), _P, c_int32]),

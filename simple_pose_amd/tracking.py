@@ -34,7 +34,10 @@ writes before the launch or the replay (never a kernel argument: a captured grap
 frame index / fps.  The smoothed poses come back in the same packed buffer (`PoseResult.keypoints_smooth`; the confidences are not filtered)
 and are what the estimator's `renderer` draws, inside the same replay.  `keypoints`, `score`, `box`, `track_id`, the association and the
 propagated boxes keep using the raw poses: they are bit for bit what they are without smoothing.  Speeds are measured in body sizes (the
-box's longer side) per second, so the parameters do not depend on the resolution.  OneEuro's defaults are design choices as well."""
+box's longer side) per second, so the parameters do not depend on the resolution.  OneEuro's defaults are design choices as well.
+
+Several streams: `MultiStreamTracker(estimator, streams=S, ...)` tracks S same-sized video streams in ONE call - one frame of batch S, the
+sp_track_*_images entries on stream-major state - with every stream's result bit for bit a PoseTracker's of its own (see the class)."""
 from __future__ import annotations
 
 import ctypes
@@ -78,6 +81,36 @@ class OneEuro(object):
         return f"OneEuro(min_cutoff={self.min_cutoff}, beta={self.beta}, d_cutoff={self.d_cutoff}, max_gap={self.max_gap}, fps={self.fps})"
 
 
+def _tracker_args(estimator, slots, match_thre, max_age, detect_every, box_expand, sigmas, smooth):
+    """What PoseTracker and MultiStreamTracker refuse at construction -> (slots, sigmas) as they are kept."""
+    if not isinstance(estimator, TopDownPoseEstimator):
+        raise TypeError(f"estimator: expected a TopDownPoseEstimator, got {type(estimator).__name__}")
+    if slots is None:
+        slots = estimator.capacity
+    if not isinstance(slots, int) or isinstance(slots, bool) or slots < 1:
+        raise ValueError(f"slots: expected an int in 1..{MAX_SLOTS}, got {slots!r}")
+    if slots > MAX_SLOTS:
+        raise ValueError(f"slots: {slots} exceeds the tracker's limit of {MAX_SLOTS} tracks (one thread per track in the match kernel); "
+                         f"use an estimator with capacity <= {MAX_SLOTS} or pass slots explicitly")
+    if slots < estimator.capacity:
+        raise ValueError(f"slots: {slots} is below the estimator's capacity {estimator.capacity}; every person of a frame needs a slot")
+    if not isinstance(match_thre, (int, float)) or isinstance(match_thre, bool) or not (0.0 < float(match_thre) <= 1.0):
+        raise ValueError(f"match_thre: an OKS in (0, 1], got {match_thre!r}")
+    if not isinstance(max_age, int) or isinstance(max_age, bool) or max_age < 0:
+        raise ValueError(f"max_age: a frame count >= 0, got {max_age!r}")
+    if not isinstance(detect_every, int) or isinstance(detect_every, bool) or detect_every < 1:
+        raise ValueError(f"detect_every: an int >= 1, got {detect_every!r}")
+    if not isinstance(box_expand, (int, float)) or isinstance(box_expand, bool) or not (0.0 < float(box_expand) < float("inf")):
+        raise ValueError(f"box_expand: a positive factor, got {box_expand!r}")
+    if sigmas is not None:
+        sigmas = np.asarray(sigmas, np.float64).reshape(-1)
+        if sigmas.size < 1 or sigmas.size > 64 or not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
+            raise ValueError("sigmas: expected 1..64 positive per-joint values")
+    if smooth is not None and not isinstance(smooth, OneEuro):
+        raise TypeError(f"smooth: expected a simple_pose_amd.tracking.OneEuro or None, got {type(smooth).__name__}")
+    return slots, sigmas
+
+
 class PoseTracker(object):
     """`estimator`: a TopDownPoseEstimator (its `flip_test`, `use_graph`, thresholds and capacity apply unchanged).  `slots`: tracks kept
     at most (capacity .. 256; default: the estimator's capacity, so that every person of a frame finds a slot).  `match_thre`: the least OKS
@@ -90,31 +123,7 @@ class PoseTracker(object):
 
     def __init__(self, estimator, slots=None, match_thre: float = 0.5, max_age: int = 30, detect_every: int = 1, box_expand: float = 1.25,
                  sigmas=None, smooth=None):
-        if not isinstance(estimator, TopDownPoseEstimator):
-            raise TypeError(f"estimator: expected a TopDownPoseEstimator, got {type(estimator).__name__}")
-        if slots is None:
-            slots = estimator.capacity
-        if not isinstance(slots, int) or isinstance(slots, bool) or slots < 1:
-            raise ValueError(f"slots: expected an int in 1..{MAX_SLOTS}, got {slots!r}")
-        if slots > MAX_SLOTS:
-            raise ValueError(f"slots: {slots} exceeds the tracker's limit of {MAX_SLOTS} tracks (one thread per track in the match kernel); "
-                             f"use an estimator with capacity <= {MAX_SLOTS} or pass slots explicitly")
-        if slots < estimator.capacity:
-            raise ValueError(f"slots: {slots} is below the estimator's capacity {estimator.capacity}; every person of a frame needs a slot")
-        if not isinstance(match_thre, (int, float)) or isinstance(match_thre, bool) or not (0.0 < float(match_thre) <= 1.0):
-            raise ValueError(f"match_thre: an OKS in (0, 1], got {match_thre!r}")
-        if not isinstance(max_age, int) or isinstance(max_age, bool) or max_age < 0:
-            raise ValueError(f"max_age: a frame count >= 0, got {max_age!r}")
-        if not isinstance(detect_every, int) or isinstance(detect_every, bool) or detect_every < 1:
-            raise ValueError(f"detect_every: an int >= 1, got {detect_every!r}")
-        if not isinstance(box_expand, (int, float)) or isinstance(box_expand, bool) or not (0.0 < float(box_expand) < float("inf")):
-            raise ValueError(f"box_expand: a positive factor, got {box_expand!r}")
-        if sigmas is not None:
-            sigmas = np.asarray(sigmas, np.float64).reshape(-1)
-            if sigmas.size < 1 or sigmas.size > 64 or not (np.isfinite(sigmas).all() and (sigmas > 0).all()):
-                raise ValueError("sigmas: expected 1..64 positive per-joint values")
-        if smooth is not None and not isinstance(smooth, OneEuro):
-            raise TypeError(f"smooth: expected a simple_pose_amd.tracking.OneEuro or None, got {type(smooth).__name__}")
+        slots, sigmas = _tracker_args(estimator, slots, match_thre, max_age, detect_every, box_expand, sigmas, smooth)
         self.smooth = smooth
         self.smooth_state: Dict[str, torch.Tensor] = {}  # device tensors: id, x, dx, t, n, now (allocated with the first smoothed frame)
         self._frame_index = 0                          # frames since construction or reset(): the clock of an update without a timestamp
@@ -271,5 +280,221 @@ class PoseTracker(object):
         res = est._results(fr, tracked=True, detected=detect)[0]
         self._since_detect = 1 if detect else self._since_detect + 1
         self._prev_n = len(res)
+        self.last_frame_kind = "detector" if detect else "propagated"
+        return res
+
+
+MAX_STREAMS = 256                    # sp_track_*_images: `images` 1 .. 256
+
+
+class MultiStreamTracker(object):
+    """S video streams tracked in ONE call: one detector forward on the S frames (or sp_track_boxes_images in its place), one pose forward
+    on the estimator's `capacity` crops, sp_track_associate_images, sp_track_smooth_images, the overlay, and one device-to-host copy - a
+    launch count that does not grow with S, and with `estimator.use_graph` one graph replay.  Every stream's result is bit for bit what a
+    PoseTracker of its own returns for the same frames under the same frame kinds: the kernels are the same, the state is stream-major
+    (`state[k][s]` is stream s's, ids start at 1 in every stream) and no stream reads another's.
+
+        trk = MultiStreamTracker(estimator, streams=S, slots=None, match_thre=0.5, max_age=30, detect_every=1, box_expand=1.25,
+                                 sigmas=None, smooth=None)
+        results = trk.update(frames, timestamps=None)    # list of S PoseResult
+        trk.reset(stream=None); trk.tracks(stream); trk.last_frame_kind
+
+    The arguments are PoseTracker's.  `slots` is PER STREAM and lies in capacity .. 256 as PoseTracker's does, because one image may take
+    every slot of the capacity; the estimator's `capacity` itself is SHARED by the S images of a call (size it as S x the persons expected
+    per image; detections beyond it are dropped from the end of the (image, detection) order and counted in `PoseResult.dropped`), so an
+    estimator with a capacity above 256 is refused.
+    ONE frame kind per call, chosen on the host from counters and the previous results only.  A call is a detector frame when it is the
+    first call, or the first after reset() of all streams or of any one stream; when `detect_every` calls have passed, counted from the last
+    detector frame; or when the previous call returned no person in EVERY stream.  Every other call is propagated: on it a stream without
+    live tracks (an empty scene at the last detector frame, say) returns no persons until the next detector frame.  With streams=1 the rule
+    is PoseTracker's.  Streams of different sizes, streams that skip a call and a `detect_every` per stream are not supported."""
+
+    MAX_GRAPHS = 8
+
+    def __init__(self, estimator, streams: int, slots=None, match_thre: float = 0.5, max_age: int = 30, detect_every: int = 1,
+                 box_expand: float = 1.25, sigmas=None, smooth=None):
+        if isinstance(estimator, TopDownPoseEstimator) and estimator.capacity > MAX_SLOTS:
+            raise ValueError(f"estimator: capacity {estimator.capacity} exceeds the tracker's limit of {MAX_SLOTS} tracks per stream (one image "
+                             f"may take every slot of the capacity, which the streams of a call share); use an estimator with capacity <= {MAX_SLOTS}")
+        slots, sigmas = _tracker_args(estimator, slots, match_thre, max_age, detect_every, box_expand, sigmas, smooth)
+        if not isinstance(streams, int) or isinstance(streams, bool) or not (1 <= streams <= MAX_STREAMS):
+            raise ValueError(f"streams: expected an int in 1..{MAX_STREAMS}, got {streams!r}")
+        self.estimator, self.streams, self.slots = estimator, streams, slots
+        self.match_thre, self.max_age, self.detect_every, self.box_expand = float(match_thre), max_age, detect_every, float(box_expand)
+        self.sigmas, self.smooth = sigmas, smooth
+        self.state: Dict[str, torch.Tensor] = {}       # device tensors [streams, ...]: id, age, miss, kps, area, conf, next_id
+        self.smooth_state: Dict[str, torch.Tensor] = {}  # device tensors [streams, ...]: id, x, dx, t, n, now
+        self._sim = None
+        self._now_host = None                          # pinned: the S times on their way to smooth_state["now"]
+        self._frame_index = [0] * streams              # per stream, calls since construction or its reset(): the clock without timestamps
+        self._graphs: Dict[tuple, tuple] = {}
+        self._since_detect, self._prev_n, self._fresh = 0, [0] * streams, True
+        self.last_frame_kind = None                    # "detector" / "propagated": what the last update ran
+
+    # -- state --------------------------------------------------------------------------------------------------------------------------
+    def _ensure_state(self, J: int) -> None:
+        if self.sigmas is None and J != 17:
+            raise ValueError(f"sigmas: the default OKS sigmas are COCO's 17; the pose model has {J} joints, pass `sigmas`")
+        if self.sigmas is not None and self.sigmas.size != J:
+            raise ValueError(f"sigmas: {self.sigmas.size} values for a pose model with {J} joints")
+        dev, S, n = self.estimator.device, self.streams, self.slots
+        z = lambda shape, dt: torch.zeros(shape, dtype=dt, device=dev)
+        if self.smooth is not None and not (self.smooth_state and self.smooth_state["n"].shape[2] == J):
+            self.smooth_state = {"id": z((S, n), torch.int32), "x": z((S, n, J, 2), torch.float64), "dx": z((S, n, J, 2), torch.float64),
+                                 "t": z((S, n, J), torch.float64), "n": z((S, n, J), torch.int32), "now": z((S,), torch.float64)}
+            self._now_host = torch.zeros((S,), dtype=torch.float64).pin_memory()
+            self._graphs.clear()
+        if self.state and self.state["kps"].shape[2] == J:
+            return
+        self.state = {"id": z((S, n), torch.int32), "age": z((S, n), torch.int32), "miss": z((S, n), torch.int32),
+                      "kps": z((S, n, J, 3), torch.float64), "area": z((S, n), torch.float64), "conf": z((S, n), torch.float32),
+                      "next_id": z((S,), torch.int32)}
+        self._sim = z((S, n, n), torch.float64)
+        self._sig = None if self.sigmas is None else (ctypes.c_double * J)(*self.sigmas.tolist())
+        self._graphs.clear()
+        self.reset()
+
+    def _check_stream(self, stream) -> int:
+        if not isinstance(stream, int) or isinstance(stream, bool) or not (0 <= stream < self.streams):
+            raise ValueError(f"stream: expected an int in 0..{self.streams - 1}, got {stream!r}")
+        return stream
+
+    def reset(self, stream=None) -> None:
+        """Forget every track of every stream (`stream=None`) or of one stream: its ids restart at 1, its smoother and its clock of
+        updates without timestamps start again, and the next call is a detector frame for all streams (the other streams keep their
+        tracks through it)."""
+        which = range(self.streams) if stream is None else (self._check_stream(stream),)
+        for s in which:
+            for k, t in self.state.items():
+                t[s].fill_(1) if k == "next_id" else t[s].zero_()
+            for t in self.smooth_state.values():
+                t[s].zero_()
+            self._frame_index[s], self._prev_n[s] = 0, 0
+        self._fresh = True
+
+    def tracks(self, stream) -> Dict[str, np.ndarray]:
+        """A host copy of one stream's live tracks (id, age, miss, keypoints, area, conf), in slot order.  For inspection: it synchronises."""
+        s = self._check_stream(stream)
+        if not self.state:
+            return {k: np.zeros(0) for k in ("id", "age", "miss", "keypoints", "area", "conf")}
+        h = {k: v[s].cpu().numpy() for k, v in self.state.items() if k != "next_id"}
+        live = h["id"] != 0
+        return {"id": h["id"][live], "age": h["age"][live], "miss": h["miss"][live], "keypoints": h["kps"][live], "area": h["area"][live],
+                "conf": h["conf"][live]}
+
+    # -- the two frames -----------------------------------------------------------------------------------------------------------------
+    def _boxes(self, fr: _Frame, J: int) -> None:
+        est, st = self.estimator, self.state
+        _lib.check(_lib.lib().sp_track_boxes_images(P(st["id"]), P(st["miss"]), P(st["kps"]), P(st["conf"]), self.streams, self.slots, J,
+                                                    est.in_vis_thre, self.box_expand, float(max(est.person_cls, 0)), fr.W, fr.H, fr.max_det,
+                                                    P(fr.det), P(fr.counts), _lib.current_stream(est.device)), "sp_track_boxes_images")
+
+    def _associate(self, fr: _Frame, J: int) -> None:
+        est, st = self.estimator, self.state
+        _lib.check(_lib.lib().sp_track_associate_images(P(fr.kps64), P(fr.area), P(fr.box), P(fr.keep), P(fr.keep_count), P(fr.seg), self.streams,
+                                                        est.capacity, J, self._sig, self.match_thre, self.max_age, self.slots, P(st["id"]),
+                                                        P(st["age"]), P(st["miss"]), P(st["kps"]), P(st["area"]), P(st["conf"]), P(st["next_id"]),
+                                                        P(self._sim), P(fr.track_id), _lib.current_stream(est.device)),
+                   "sp_track_associate_images")
+
+    def _smooth(self, fr: _Frame, J: int) -> None:
+        """sp_track_smooth_images on what the association just left in the frame; the kernel reads the S times from smooth_state["now"]."""
+        est, sm, ss = self.estimator, self.smooth, self.smooth_state
+        _lib.check(_lib.lib().sp_track_smooth_images(P(fr.kps64), P(fr.box), P(fr.track_id), P(fr.keep), P(fr.keep_count), P(fr.seg), self.streams,
+                                                     est.capacity, J, P(self.state["id"]), self.slots, P(ss["now"]), sm.min_cutoff, sm.beta,
+                                                     sm.d_cutoff, sm.max_gap, est.in_vis_thre, P(ss["id"]), P(ss["x"]), P(ss["dx"]), P(ss["t"]),
+                                                     P(ss["n"]), P(fr.kps_smooth), _lib.current_stream(est.device)), "sp_track_smooth_images")
+
+    def _launch(self, fr: _Frame, detect: bool, det_prog, pose_prog, single_stream: bool) -> None:
+        J = pose_prog.out_shape[0]
+        if detect:
+            self.estimator._detect(fr, det_prog, single_stream)
+        else:
+            self._boxes(fr, J)
+        self.estimator._poses(fr, pose_prog, single_stream)
+        self._associate(fr, J)
+        if self.smooth is not None:
+            self._smooth(fr, J)
+        self.estimator._render(fr, J, tracked=True, kps=None if self.smooth is None else fr.kps_smooth)
+
+    def _params(self, det_prog, pose_prog) -> tuple:
+        return (self.estimator._params(det_prog, pose_prog), self.match_thre, self.max_age, self.box_expand, self.slots, id(self._sim),
+                None if self.smooth is None else self.smooth.key() + (id(self.smooth_state["n"]),))
+
+    def _graph(self, fr: _Frame, detect: bool, det_prog, pose_prog):
+        key = (fr.B, fr.H, fr.W, detect, None if self.smooth is None else self.smooth.key())
+        entry = self._graphs.get(key)
+        params = self._params(det_prog, pose_prog)
+        if entry is not None and entry[0] is fr and entry[2] == params:
+            self._graphs[key] = self._graphs.pop(key)  # most recently used last
+            return entry[1]
+        est, dev = self.estimator, self.estimator.device
+        side = torch.cuda.Stream(device=dev)
+        side.wait_stream(torch.cuda.current_stream(dev))
+        with torch.cuda.stream(side):                # warm-up outside the capture, as PoseTracker's: without the association and the smoother,
+            if detect:                               # which allocate nothing and must advance the tracks once per call
+                est._detect(fr, det_prog, True)
+            est._poses(fr, pose_prog, True)
+            est._render(fr, pose_prog.out_shape[0], tracked=True, kps=None if self.smooth is None else fr.kps_smooth)
+        torch.cuda.current_stream(dev).wait_stream(side)
+        torch.cuda.synchronize(dev)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph):
+            self._launch(fr, detect, det_prog, pose_prog, True)
+        # the nodes hold raw pointers into both programs' activation pools for the batch sizes used: keep them alive
+        keepalive = (det_prog, pose_prog, None if det_prog is None else det_prog.pool_for(fr.B, dev), pose_prog.pool_for(est._pose_batch(), dev),
+                     getattr(fr, "ws", None), self.state, self._sim, self.smooth_state)
+        self._graphs.pop(key, None)
+        if len(self._graphs) >= self.MAX_GRAPHS:
+            self._graphs.pop(next(iter(self._graphs)))
+        self._graphs[key] = (fr, graph, params, keepalive)
+        return graph
+
+    @torch.no_grad()
+    def update(self, frames, timestamps=None):
+        """The next frame of every stream: uint8 BGR [S, H, W, 3] (numpy or CUDA) or a list of S images of one size -> a list of S
+        PoseResult with `track_id` (and `keypoints_smooth`, `image`, `jpeg` as PoseTracker returns them), stream s's in place s.
+        `timestamps`: S finite times in seconds, one per stream, for a tracker that smooths (default: each stream's frame index /
+        `smooth.fps`).  A propagated call does not run the detector (see the class docstring)."""
+        est, S = self.estimator, self.streams
+        times = None
+        if timestamps is not None:
+            if self.smooth is None:
+                raise ValueError("timestamps: this tracker does not smooth (MultiStreamTracker(..., smooth=OneEuro(...))); nothing would read them")
+            times = list(timestamps) if isinstance(timestamps, (list, tuple, np.ndarray)) else None
+            if times is None or len(times) != S:
+                raise ValueError(f"timestamps: expected {S} times in seconds, one per stream, got {timestamps!r}")
+            for t in times:
+                if not isinstance(t, (int, float, np.integer, np.floating)) or isinstance(t, bool) or not (abs(float(t)) < float("inf")):
+                    raise ValueError(f"timestamps: finite times in seconds, got {t!r}")
+        if isinstance(frames, (list, tuple)) and len(frames) != S:
+            raise ValueError(f"frames: this tracker follows {S} streams, got {len(frames)} images")
+        imgs = est._shape_of(frames, batched=True)   # (a list of differently sized images: ValueError; a CPU tensor: HipLibraryError)
+        if imgs.shape[0] != S:
+            raise ValueError(f"frames: this tracker follows {S} streams, got {imgs.shape[0]} images")
+        H, W = imgs.shape[1], imgs.shape[2]
+        detect = self._fresh or self._since_detect >= self.detect_every or not any(self._prev_n)
+        det_prog = None
+        if detect:
+            g = est.detector.transform.geometry(H, W)
+            det_prog = est.detector.program(g["out_h"], g["out_w"])
+        pose_prog = est._pose_program()
+        J = pose_prog.out_shape[0]
+        self._ensure_state(J)
+        fr = est._frame(S, H, W, est.MAX_DET, J, smooth=self.smooth is not None)
+        est._load(fr, imgs)
+        if self.smooth is not None:                  # the S times, on the frame's stream ahead of the launch or replay that reads them
+            for s in range(S):
+                self._now_host[s] = self._frame_index[s] / self.smooth.fps if times is None else float(times[s])
+            self.smooth_state["now"].copy_(self._now_host, non_blocking=True)
+        self._frame_index = [i + 1 for i in self._frame_index]
+        self._prev_n = [0] * S                       # (a call that raises below is followed by a detector frame)
+        if est.use_graph:
+            self._graph(fr, detect, det_prog, pose_prog).replay()
+        else:
+            self._launch(fr, detect, det_prog, pose_prog, False)
+        res = est._results(fr, tracked=True, detected=detect)      # (the fetch also ends the copy out of _now_host)
+        self._since_detect = 1 if detect else self._since_detect + 1
+        self._prev_n, self._fresh = [len(r) for r in res], False
         self.last_frame_kind = "detector" if detect else "propagated"
         return res
