@@ -798,6 +798,46 @@ int sp_yolo_boxes_to_source_images(const float* det_group, const int32_t* counts
 int sp_warp_affine_plan_images_u8c3(const sp_image_ref* images_dev, int batch, const double* m_inv, const int32_t* src_index,
                                     const int32_t* seg, int capacity, unsigned char* dst, int out_h, int out_w, void* stream);
 
+/* ---- tiled detection: the detector on overlapping tiles of large frames, fused on the device ------------------------------------------------
+ * (No new ABI version: these are additions.)  A "pass" is one rectangle of a frame that goes through the detector: the whole frame or one
+ * of its tiles (simple_pose_amd/tiling.py plans them).  sp_tile_ref describes one pass: `data` points at the rectangle's first pixel INSIDE
+ * its frame (uint8 BGR, `pitch` pixels per frame row, pitch >= w), h x w its size, then its letterbox as in sp_image_ref, (x0, y0) its
+ * origin in the frame, `image` the frame's index in the call and `slot` the pass's index within its frame (0 .. passes - 1).  The kernels
+ * read the table from DEVICE memory; the caller fills it on the host, uploads it and guarantees what it holds. */
+typedef struct sp_tile_ref {
+    const unsigned char* data;              /* device pointer: the frame's pixel (y0, x0) */
+    int32_t h, w, pitch;
+    int32_t new_h, new_w, top, left;
+    float ratio;
+    int32_t x0, y0;
+    int32_t image, slot;
+} sp_tile_ref;                              /* 56 bytes */
+#define SP_TILE_MAX_TILES 64                /* tiles per frame */
+#define SP_TILE_MAX_PASSES 65               /* the tiles and the whole frame: 65 x 300 rows stay below SP_YOLO_NMS_MAX_CANDIDATES */
+#define SP_TILE_IOU 0                       /* merge metric: intersection over union (sp_yolo_nms's) */
+#define SP_TILE_IOS 1                       /* intersection over the smaller of the two areas */
+/* sp_yolo_letterbox_images with the row pitch of every source taken from the table: the same pixel function, so pass b's canvas has the
+ * bits of sp_yolo_letterbox run on a contiguous copy of its rectangle.  Both modes; out_h, out_w even. */
+int sp_yolo_letterbox_tiles(const sp_tile_ref* tiles_dev, int batch, int out_h, int out_w, int mode, void* out, void* stream);
+/* One net-shape group of `batch` passes after sp_yolo_nms_device (det_group fp32 [batch, max_det, 6], counts_group / status_group int32
+ * [batch], passes letterboxed to img_h x img_w): rows [0, counts_group[p]) of pass p are clipped and un-letterboxed as
+ * sp_yolo_boxes_to_source does it, then x += x0, y += y0 (one fp32 add per coordinate, no contraction), and written to block
+ * (tiles[p].image, tiles[p].slot) of cand fp32 [frames, passes, max_det, 6]; the block's other rows are written as zeros; cand_counts
+ * int32 [frames, passes] receives the count; the pass's status word is OR-ed into status_frames[image] (the caller zeroes status_frames
+ * before the first group of a call).  cand must not overlap det_group.  One launch. */
+int sp_yolo_boxes_to_frame_tiles(const float* det_group, const int32_t* counts_group, const int32_t* status_group,
+                                 const sp_tile_ref* tiles_dev, int batch, int passes, int max_det, float img_h, float img_w, float* cand,
+                                 int32_t* cand_counts, int32_t* status_frames, void* stream);
+/* The fusion of a frame's passes, per frame: the candidates are the frame's blocks of cand in slot order, rows [0, cand_counts) of each
+ * in their order; a descending score sort whose ties go to the lower candidate index; a greedy scan in which a candidate is kept unless
+ * an already kept candidate of the same class (agnostic: of any class) has metric > thresh - SP_TILE_IOU: sp_yolo_nms's IoU, SP_TILE_IOS:
+ * the same intersection divided by fminf(area_a, area_b); a NaN metric (an empty box) does not suppress.  The kept rows, truncated at
+ * max_det, go to det fp32 [frames, max_det, 6] (rows from the count on are zeros) and counts int32 [frames]: what sp_topdown_plan reads.
+ * passes <= SP_TILE_MAX_PASSES, passes * max_det <= SP_YOLO_NMS_MAX_CANDIDATES, 0 < thresh <= 1; workspace: sp_yolo_nms_workspace(frames).
+ * Deterministic.  Three plain launches: no copy, no synchronisation, safe inside a stream capture. */
+int sp_yolo_merge_passes(const float* cand, const int32_t* cand_counts, int frames, int passes, int max_det, int metric, float thresh,
+                         int agnostic, void* workspace, int64_t workspace_bytes, float* det, int32_t* counts, void* stream);
+
 /* ---- flip test: the mirrored network input and the merge of the two sets of heat maps ----------------------------------------------------
  * sp_mirror_w: dst[r, x] = src[r, w-1-x] over `rows` rows of `w` elements of elem_bytes bytes: 3 = uint8 BGR NHWC crops (rows = N*H),
  * 4 = fp32 NCHW inputs (rows = N*C*H).  Out of place only: dst may be the second half of the allocation that holds src, overlapping ranges

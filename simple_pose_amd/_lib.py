@@ -115,6 +115,16 @@ class ImageRef(ctypes.Structure):
 SP_RENDER_COLOUR_PERSON, SP_RENDER_COLOUR_PART = 0, 1
 SP_RENDER_MAX_EDGES, SP_RENDER_MAX_PALETTE, SP_RENDER_MAX_RADIUS = 64, 32, 1024
 
+class TileRef(ctypes.Structure):
+    """Mirror of `sp_tile_ref` (field order is ABI): one pass of tiled detection, a rectangle of a frame in device memory."""
+    _fields_ = [("data", ctypes.c_uint64), ("h", c_int32), ("w", c_int32), ("pitch", c_int32), ("new_h", c_int32), ("new_w", c_int32),
+                ("top", c_int32), ("left", c_int32), ("ratio", c_float), ("x0", c_int32), ("y0", c_int32), ("image", c_int32),
+                ("slot", c_int32)]
+
+
+SP_TILE_MAX_TILES, SP_TILE_MAX_PASSES = 64, 65
+SP_TILE_IOU, SP_TILE_IOS = 0, 1
+
 # every symbol include/simple_pose_hip.h declares: name -> (restype, argtypes)
 _P = c_void_p
 SYMBOLS = {
@@ -255,6 +265,9 @@ SYMBOLS = {
     "sp_yolo_letterbox_images": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
     "sp_yolo_boxes_to_source_images": (c_int, [_P, _P, _P, _P, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
     "sp_warp_affine_plan_images_u8c3": (c_int, [_P, c_int, _P, _P, _P, c_int, _P, c_int, c_int, _P]),
+    "sp_yolo_letterbox_tiles": (c_int, [_P, c_int, c_int, c_int, c_int, _P, _P]),
+    "sp_yolo_boxes_to_frame_tiles": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_float, c_float, _P, _P, _P, _P]),
+    "sp_yolo_merge_passes": (c_int, [_P, _P, c_int, c_int, c_int, c_int, c_float, c_int, _P, c_int64, _P, _P, _P]),
     "sp_mirror_w": (c_int, [_P, _P, c_int64, c_int, c_int, _P]),
     "sp_heat_map_flip_merge": (c_int, [_P, _P, ctypes.POINTER(c_int32), c_int, c_int, c_int, c_int, c_int, _P, _P]),
     "sp_track_associate": (c_int, [_P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(c_double), c_double, c_int, c_int, _P, _P, _P, _P, _P, _P, _P, _P,

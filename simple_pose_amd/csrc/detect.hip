@@ -1,5 +1,6 @@
 // detect.hip - the YOLOv5 person detector's non-convolution launches (fp32): letterbox + Focus input, SPP, slice-to-slice nearest
-// upsampling, the head decode and the batched YOLO NMS with merge (detector/yolov5_detector.py, detector/nets/{commons,yolov5}.py).
+// upsampling, the head decode and the batched YOLO NMS with merge (detector/yolov5_detector.py, detector/nets/{commons,yolov5}.py), and
+// tiled detection's three launches (tiling.py: the letterbox of rectangles of a frame, the scatter into frame coordinates, the fusion).
 // The convolutions run on the implicit GEMM (conv_igemm.hip: SP_CONV_HARDSWISH, SP_CONV_OUT_SLICE).
 #include "sp_common.h"
 
@@ -26,6 +27,7 @@ __device__ __forceinline__ void lin_coef(int d, double scale, int ssize, int& s0
 struct LbImage {
     const unsigned char* src;
     int sh, sw, nh, nw, top, left;
+    int pitch;          // pixels per source row: sw for a contiguous image, the frame's width for a tile of it
     double sy, sx;      // source / destination size ratios (OpenCV's scale_y / scale_x)
     int kind;           // 0 copy, 1 bilinear, 2 INTER_AREA 2x
 };
@@ -48,21 +50,21 @@ __device__ __forceinline__ void canvas_px(const LbImage& a, int oy, int ox, int 
     if (y < 0 || y >= a.nh || x < 0 || x >= a.nw) { v[0] = v[1] = v[2] = 114; return; }
     const unsigned char* S = a.src;
     if (a.kind == 0) {
-        const unsigned char* p = S + ((size_t)y * a.sw + x) * 3;
+        const unsigned char* p = S + ((size_t)y * a.pitch + x) * 3;
         for (int c = 0; c < 3; ++c) v[c] = p[c];
         return;
     }
     if (a.kind == 2) {
-        const unsigned char* p0 = S + ((size_t)(2 * y) * a.sw + 2 * x) * 3;
-        const unsigned char* p1 = p0 + (size_t)a.sw * 3;
+        const unsigned char* p0 = S + ((size_t)(2 * y) * a.pitch + 2 * x) * 3;
+        const unsigned char* p1 = p0 + (size_t)a.pitch * 3;
         for (int c = 0; c < 3; ++c) v[c] = (p0[c] + p0[3 + c] + p1[c] + p1[3 + c] + 2) >> 2;
         return;
     }
     int x0, x1, ax0, ax1, y0, y1, by0, by1;
     lin_coef(x, a.sx, a.sw, x0, x1, ax0, ax1);
     lin_coef(y, a.sy, a.sh, y0, y1, by0, by1);
-    const unsigned char* R0 = S + (size_t)y0 * a.sw * 3;
-    const unsigned char* R1 = S + (size_t)y1 * a.sw * 3;
+    const unsigned char* R0 = S + (size_t)y0 * a.pitch * 3;
+    const unsigned char* R1 = S + (size_t)y1 * a.pitch * 3;
     for (int c = 0; c < 3; ++c) {
         const int h0 = R0[x0 * 3 + c] * ax0 + R0[x1 * 3 + c] * ax1;
         const int h1 = R1[x0 * 3 + c] * ax0 + R1[x1 * 3 + c] * ax1;
@@ -118,6 +120,22 @@ __global__ void letterbox_images_kernel(const sp_image_ref* __restrict__ images,
     LbImage im;
     im.src = ref.data; im.sh = ref.h; im.sw = ref.w; im.nh = ref.new_h; im.nw = ref.new_w; im.top = ref.top; im.left = ref.left;
     if (!im.src || im.sh <= 0 || im.sw <= 0 || im.nh <= 0 || im.nw <= 0) { im.nh = im.nw = 0; im.sh = im.sw = 1; }
+    im.pitch = im.sw;
+    lb_scales(im);
+    letterbox_store(im, mode, ow, (int)(i - b * per), i, out);
+}
+
+// letterbox_images_kernel for rectangles of larger frames (sp_tile_ref): the row pitch comes from the table, everything else is the same
+__global__ void letterbox_tiles_kernel(const sp_tile_ref* __restrict__ tiles, int B, int oh, int ow, int mode, void* out) {
+    const long long per = mode == SP_LETTERBOX_U8 ? (long long)oh * ow : (long long)(oh / 2) * (ow / 2);
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= B * per) return;
+    const int b = (int)(i / per);
+    const sp_tile_ref ref = tiles[b];
+    LbImage im;
+    im.src = ref.data; im.sh = ref.h; im.sw = ref.w; im.nh = ref.new_h; im.nw = ref.new_w; im.top = ref.top; im.left = ref.left;
+    im.pitch = ref.pitch;
+    if (!im.src || im.sh <= 0 || im.sw <= 0 || im.nh <= 0 || im.nw <= 0 || im.pitch < im.sw) { im.nh = im.nw = 0; im.sh = im.sw = im.pitch = 1; }
     lb_scales(im);
     letterbox_store(im, mode, ow, (int)(i - b * per), i, out);
 }
@@ -469,6 +487,153 @@ __global__ void boxes_to_source_images_kernel(const float* __restrict__ det, con
     if (r == 0) { counts_all[ref.dst_index] = n; status_all[ref.dst_index] = status[b]; }
 }
 
+// ---- tiled detection: the passes of a frame (the whole frame, its overlapping tiles) fused on the device --------------------------------
+// one net-shape group of passes: pass p's NMS rows go, un-letterboxed and moved by the pass's origin, to block (image, slot) of the
+// candidate buffer [frames, passes, max_det, 6]; rows from the count on are written as zeros; the status word is OR-ed into the frame's
+__global__ void boxes_to_frame_tiles_kernel(const float* __restrict__ det, const int* __restrict__ counts, const int* __restrict__ status,
+                                            const sp_tile_ref* __restrict__ tiles, int n, int passes, int max_det, float img_h, float img_w,
+                                            float* __restrict__ cand, int* __restrict__ cand_counts, int* __restrict__ status_frames) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n * max_det) return;
+    const int p = i / max_det, r = i - p * max_det;
+    const sp_tile_ref ref = tiles[p];
+    if (ref.image < 0 || ref.slot < 0 || ref.slot >= passes) return;
+    const int cnt = counts[p];
+    const size_t blk = (size_t)ref.image * passes + ref.slot;
+    const float* s = det + (size_t)i * 6;
+    float* d = cand + (blk * max_det + r) * 6;
+    if (r < cnt) {
+#pragma clang fp contract(off)
+        float v[4];
+        box_to_source(s, v, img_h, img_w, (float)ref.left, (float)ref.top, ref.ratio);
+        const float x0 = (float)ref.x0, y0 = (float)ref.y0;
+        d[0] = v[0] + x0; d[1] = v[1] + y0; d[2] = v[2] + x0; d[3] = v[3] + y0;
+        d[4] = s[4]; d[5] = s[5];
+    } else {
+        for (int k = 0; k < 6; ++k) d[k] = 0.f;
+    }
+    if (r == 0) {
+        cand_counts[blk] = cnt;
+        if (status[p]) atomicOr(status_frames + ref.image, status[p]);
+    }
+}
+
+// the "candidates from rows" front end of the merge: frame blockIdx.x's blocks in slot order, each block's rows [0, count) in their
+// order, packed into the NMS workspace (boxes as they are: the merge compares classes instead of offsetting boxes)
+__global__ __launch_bounds__(NT) void merge_candidates_kernel(const float* __restrict__ cand, const int* __restrict__ cand_counts, int passes,
+                                                              int max_det, NmsWs ws) {
+    __shared__ int start[SP_TILE_MAX_PASSES + 1];
+    const int b = blockIdx.x;
+    if (threadIdx.x == 0) {
+        int acc = 0;
+        for (int p = 0; p < passes; ++p) {
+            start[p] = acc;
+            const int c = cand_counts[(size_t)b * passes + p];
+            acc += c < 0 ? 0 : (c > max_det ? max_det : c);
+        }
+        start[passes] = acc;
+        ws.n_cand[b] = acc;
+    }
+    __syncthreads();
+    float4* box = ws.box + (size_t)b * CAP;
+    float2* sc = ws.sc + (size_t)b * CAP;
+    for (int i = threadIdx.x; i < passes * max_det; i += NT) {
+        const int p = i / max_det, r = i - p * max_det;
+        if (r >= start[p + 1] - start[p]) continue;
+        const float* s = cand + (((size_t)b * passes + p) * max_det + r) * 6;
+        const int k = start[p] + r;                 // < passes * max_det <= CAP (checked on the host)
+        box[k] = make_float4(s[0], s[1], s[2], s[3]);
+        sc[k] = make_float2(s[4], s[5]);
+    }
+}
+
+// box_iou1's intersection over the smaller area (IoS); SP_TILE_IOU is box_iou1 itself
+__device__ __forceinline__ float box_ios1(float4 a, float4 b) {
+#pragma clang fp contract(off)
+    const float area_a = (a.z - a.x) * (a.w - a.y), area_b = (b.z - b.x) * (b.w - b.y);
+    const float w = fmaxf(fminf(a.z, b.z) - fmaxf(a.x, b.x), 0.f), h = fmaxf(fminf(a.w, b.w) - fmaxf(a.y, b.y), 0.f);
+    const float inter = w * h;
+    return inter / fminf(area_a, area_b);
+}
+
+// greedy scan over the ranked candidates, nms_select_kernel's block scheme: a candidate is kept unless an already kept one of its class
+// (any class: agnostic) has metric > thresh (a NaN metric compares false and does not suppress); truncated at max_det, rows past the
+// count written as zeros
+__global__ __launch_bounds__(NT) void merge_select_kernel(NmsWs ws, int metric, float thresh, int agnostic, int max_det, float* __restrict__ out,
+                                                          int* __restrict__ counts) {
+    __shared__ float4 kb[SP_YOLO_NMS_MAX_DET];
+    __shared__ int kcls[SP_YOLO_NMS_MAX_DET];
+    __shared__ int kidx[SP_YOLO_NMS_MAX_DET];
+    __shared__ float4 cb[NT];
+    __shared__ int ccls[NT];
+    __shared__ int alive[NT];
+    __shared__ unsigned long long masks[NT][NT / 64];
+    __shared__ int s_nk;
+    const int b = blockIdx.x, tid = threadIdx.x;
+    const int n = ws.n_cand[b];
+    const float4* box = ws.box + (size_t)b * CAP;
+    const float2* sc = ws.sc + (size_t)b * CAP;
+    const int* order = ws.order + (size_t)b * CAP;
+    auto hits = [&](float4 k, int kc, float4 c, int cc) {
+        if (!agnostic && kc != cc) return false;
+        return (metric == SP_TILE_IOS ? box_ios1(k, c) : box_iou1(k, c)) > thresh;
+    };
+    if (tid == 0) s_nk = 0;
+    __syncthreads();
+    for (int base = 0; base < n; base += NT) {
+        const int nk = s_nk;
+        if (nk >= max_det) break;
+        const int pos = base + tid;
+        int ci = pos < n ? order[pos] : -1;
+        const bool valid = ci >= 0 && ci < n;       // (NaN scores leave holes in the ranking: such a position is skipped, never read through)
+        if (!valid) ci = 0;
+        const float4 bx = valid ? box[ci] : make_float4(0.f, 0.f, 0.f, 0.f);
+        const int cls = valid ? (int)sc[ci].y : -1;
+        bool a = valid;
+        for (int k = 0; k < nk && a; ++k)
+            if (hits(kb[k], kcls[k], bx, cls)) a = false;
+        cb[tid] = bx;
+        ccls[tid] = cls;
+        alive[tid] = a;
+        __syncthreads();
+        unsigned long long m[NT / 64] = {0ull, 0ull, 0ull, 0ull};
+        if (a)
+            for (int s = 0; s < tid; ++s)
+                if (alive[s] && hits(cb[s], ccls[s], bx, cls)) m[s >> 6] |= 1ull << (s & 63);
+#pragma unroll
+        for (int q = 0; q < NT / 64; ++q) masks[tid][q] = m[q];
+        __syncthreads();
+        if (tid == 0) {
+            unsigned long long keep[NT / 64] = {0ull, 0ull, 0ull, 0ull};
+            int k = nk;
+            for (int t = 0; t < NT && k < max_det; ++t) {
+                if (!alive[t]) continue;
+                if ((masks[t][0] & keep[0]) | (masks[t][1] & keep[1]) | (masks[t][2] & keep[2]) | (masks[t][3] & keep[3])) continue;
+                keep[t >> 6] |= 1ull << (t & 63);
+                kb[k] = cb[t];
+                kcls[k] = ccls[t];
+                kidx[k] = order[base + t];
+                ++k;
+            }
+            s_nk = k;
+        }
+        __syncthreads();
+    }
+    const int nk = s_nk;
+    float* O = out + (size_t)b * max_det * 6;
+    for (int r = tid; r < max_det; r += NT) {
+        float* o = O + (size_t)r * 6;
+        if (r < nk) {
+            const int ci = kidx[r];
+            const float4 v = box[ci];
+            o[0] = v.x; o[1] = v.y; o[2] = v.z; o[3] = v.w; o[4] = sc[ci].x; o[5] = sc[ci].y;
+        } else {
+            for (int k = 0; k < 6; ++k) o[k] = 0.f;
+        }
+    }
+    if (tid == 0) counts[b] = nk;
+}
+
 int64_t nms_ws_layout(int B, NmsWs* ws, void* base) {
     char* p = reinterpret_cast<char*>(base);
     int64_t off = 0;
@@ -495,6 +660,7 @@ extern "C" int sp_yolo_letterbox(const unsigned char* src, int batch, int src_h,
                "sp_yolo_letterbox: mode %d (Focus output needs an even canvas)", mode);
     LbArgs a;
     a.im.src = src; a.im.sh = src_h; a.im.sw = src_w; a.im.nh = new_h; a.im.nw = new_w; a.im.top = top; a.im.left = left;
+    a.im.pitch = src_w;
     lb_scales(a.im);
     a.B = batch; a.oh = out_h; a.ow = out_w; a.mode = mode;
     const long long n = mode == SP_LETTERBOX_U8 ? (long long)batch * out_h * out_w : (long long)batch * (out_h / 2) * (out_w / 2);
@@ -655,4 +821,53 @@ extern "C" int sp_yolo_boxes_to_source_images(const float* det_group, const int3
     hipLaunchKernelGGL(boxes_to_source_images_kernel, dim3(sp_ceil_div(batch * max_det, 256)), dim3(256), 0, (hipStream_t)stream, det_group,
                        counts_group, status_group, images_dev, batch, max_det, img_h, img_w, det_all, counts_all, status_all);
     return sp_check_launch("boxes_to_source_images_kernel");
+}
+
+extern "C" int sp_yolo_letterbox_tiles(const sp_tile_ref* tiles_dev, int batch, int out_h, int out_w, int mode, void* out, void* stream) {
+    SP_REQUIRE(tiles_dev && out, "sp_yolo_letterbox_tiles: null pointer");
+    SP_REQUIRE(batch >= 1 && out_h > 0 && out_w > 0 && out_h % 2 == 0 && out_w % 2 == 0 && (long long)batch * out_h * out_w * 12 < (1ll << 31),
+               "sp_yolo_letterbox_tiles: batch %d (>= 1), canvas %dx%d (even sizes)", batch, out_h, out_w);
+    SP_REQUIRE(mode == SP_LETTERBOX_U8 || mode == SP_LETTERBOX_FOCUS, "sp_yolo_letterbox_tiles: mode %d", mode);
+    const long long n = mode == SP_LETTERBOX_U8 ? (long long)batch * out_h * out_w : (long long)batch * (out_h / 2) * (out_w / 2);
+    hipLaunchKernelGGL(letterbox_tiles_kernel, dim3(sp_ceil_div(n, 256)), dim3(256), 0, (hipStream_t)stream, tiles_dev, batch, out_h, out_w, mode,
+                       out);
+    return sp_check_launch("letterbox_tiles_kernel");
+}
+
+extern "C" int sp_yolo_boxes_to_frame_tiles(const float* det_group, const int32_t* counts_group, const int32_t* status_group,
+                                            const sp_tile_ref* tiles_dev, int batch, int passes, int max_det, float img_h, float img_w,
+                                            float* cand, int32_t* cand_counts, int32_t* status_frames, void* stream) {
+    SP_REQUIRE(det_group && counts_group && status_group && tiles_dev && cand && cand_counts && status_frames,
+               "sp_yolo_boxes_to_frame_tiles: null pointer");
+    SP_REQUIRE(batch >= 1 && passes >= 1 && passes <= SP_TILE_MAX_PASSES && max_det > 0 && max_det <= SP_YOLO_NMS_MAX_DET && img_h > 0.f &&
+                   img_w > 0.f && (long long)batch * max_det < (1ll << 31) / 6,
+               "sp_yolo_boxes_to_frame_tiles: batch %d (>= 1), passes %d (1..%d), max_det %d (1..%d)", batch, passes, SP_TILE_MAX_PASSES, max_det,
+               SP_YOLO_NMS_MAX_DET);
+    hipLaunchKernelGGL(boxes_to_frame_tiles_kernel, dim3(sp_ceil_div(batch * max_det, 256)), dim3(256), 0, (hipStream_t)stream, det_group,
+                       counts_group, status_group, tiles_dev, batch, passes, max_det, img_h, img_w, cand, cand_counts, status_frames);
+    return sp_check_launch("boxes_to_frame_tiles_kernel");
+}
+
+extern "C" int sp_yolo_merge_passes(const float* cand, const int32_t* cand_counts, int frames, int passes, int max_det, int metric, float thresh,
+                                    int agnostic, void* workspace, int64_t workspace_bytes, float* det, int32_t* counts, void* stream) {
+    SP_REQUIRE(cand && cand_counts && workspace && det && counts, "sp_yolo_merge_passes: null pointer");
+    SP_REQUIRE(frames >= 1 && passes >= 1 && passes <= SP_TILE_MAX_PASSES && max_det > 0 && max_det <= SP_YOLO_NMS_MAX_DET &&
+                   passes * max_det <= CAP,
+               "sp_yolo_merge_passes: frames %d (>= 1), passes %d (1..%d), max_det %d (1..%d), passes * max_det <= %d", frames, passes,
+               SP_TILE_MAX_PASSES, max_det, SP_YOLO_NMS_MAX_DET, CAP);
+    SP_REQUIRE((metric == SP_TILE_IOU || metric == SP_TILE_IOS) && thresh > 0.f && thresh <= 1.f,
+               "sp_yolo_merge_passes: metric %d (SP_TILE_IOU, SP_TILE_IOS), thresh %g (0 < thresh <= 1)", metric, (double)thresh);
+    NmsWs ws;
+    const int64_t need = nms_ws_layout(frames, &ws, workspace);
+    SP_REQUIRE(workspace_bytes >= need, "sp_yolo_merge_passes: workspace %lld bytes, need %lld (sp_yolo_nms_workspace)", (long long)workspace_bytes,
+               (long long)need);
+    hipStream_t s = (hipStream_t)stream;
+    hipLaunchKernelGGL(merge_candidates_kernel, dim3(frames), dim3(NT), 0, s, cand, cand_counts, passes, max_det, ws);
+    int rc = sp_check_launch("merge_candidates_kernel");
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(nms_rank_kernel, dim3(sp_ceil_div(passes * max_det, NT), frames), dim3(NT), 0, s, ws);    // blocks beyond n_cand[b] return at once
+    rc = sp_check_launch("nms_rank_kernel");
+    if (rc != SP_OK) return rc;
+    hipLaunchKernelGGL(merge_select_kernel, dim3(frames), dim3(NT), 0, s, ws, metric, thresh, agnostic ? 1 : 0, max_det, det, counts);
+    return sp_check_launch("merge_select_kernel");
 }

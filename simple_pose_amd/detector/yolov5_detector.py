@@ -212,3 +212,78 @@ class YOLOv5Detector(object):
             for i, box in zip(members, dets):
                 out[i] = self._finish([box], mb.geoms[i])[0]
         return out
+
+    # -- tiled detection (tiling.py): the passes of large frames in one forward per net shape, fused on the device -------------------------
+    TILE_CHUNK = 32                      # passes per forward at the most: bounds the activation pool; no bit depends on it
+
+    def tile_programs(self, tp) -> tuple:
+        """The programs of a TilePlan's groups, in group order."""
+        return tuple(self.program(out_h, out_w) for (out_h, out_w), _, _ in tp.groups)
+
+    def detect_tiled(self, tp, progs, det: torch.Tensor, counts: torch.Tensor, status: torch.Tensor, max_det: int, tiling,
+                     single_stream: bool = False) -> None:
+        """Every launch between the frames a TilePlan points into and their fused detections: per net-shape group (in chunks of
+        TILE_CHUNK passes) letterbox through the table + network + head decode, sp_yolo_nms_device and the scatter into the frames'
+        candidate blocks, then one sp_yolo_merge_passes into det [B, max_det, 6] / counts [B]; status [B] receives the OR of the
+        passes' NMS status words.  Plain launches on the current stream (`single_stream`: the programs' too, as a capture needs it)."""
+        lib, P = _lib.lib(), _lib.ptr
+        stream = _lib.current_stream(self.device)
+        keep = []
+        status.zero_()
+        for k, ((out_h, out_w), _, n) in enumerate(tp.groups):
+            prog, first = progs[k], tp.groups[k][1]
+            for lo in range(0, n, self.TILE_CHUNK):
+                hi = min(n, lo + self.TILE_CHUNK)
+                table = tp.group_table(k, lo, hi)
+                engine.set_letterbox_tiles(prog)
+                was = prog.multi_stream
+                if single_stream:
+                    prog.multi_stream = False
+                try:
+                    pred = prog.run(table)
+                finally:
+                    prog.multi_stream = was
+                m, N, no = pred.shape
+                ws = _workspace(m, pred.device)
+                a, b = first + lo, first + hi
+                _lib.check(lib.sp_yolo_nms_device(P(pred), m, N, no, float(self.conf_thresh), float(self.iou_thresh), 1, 1, 0, max_det, P(ws),
+                                                  ws.numel(), P(tp.det[a:b]), P(tp.counts[a:b]), P(tp.status[a:b]), stream), "sp_yolo_nms_device")
+                _lib.check(lib.sp_yolo_boxes_to_frame_tiles(P(tp.det[a:b]), P(tp.counts[a:b]), P(tp.status[a:b]), P(table), m, tp.P, max_det,
+                                                            float(out_h), float(out_w), P(tp.cand), P(tp.cand_counts), P(status), stream),
+                           "sp_yolo_boxes_to_frame_tiles")
+                keep += [prog, prog.pool_for(m, pred.device), ws, pred]
+        ws = _workspace(tp.B, self.device)
+        _lib.check(lib.sp_yolo_merge_passes(P(tp.cand), P(tp.cand_counts), tp.B, tp.P, max_det, tiling.metric_code, tiling.thresh,
+                                            int(tiling.agnostic), P(ws), ws.numel(), P(det), P(counts), stream), "sp_yolo_merge_passes")
+        tp.keepalive = keep + [ws]                   # a captured graph holds their pointers
+
+    @torch.no_grad()
+    def predict_tiled(self, img, tiling, max_det: int = 300) -> list:
+        """Tiled detection of one image [H, W, 3] or a same-sized batch [B, H, W, 3] (uint8 BGR, numpy or CUDA; a list of same-sized
+        arrays is stacked): the detector runs on the passes `tiling` plans (tiling.Tiling: overlapping tiles at their native resolution,
+        and the whole frame), one forward per net shape, and the passes' boxes are fused on the device.  Per image CUDA fp32 [n, 6]
+        (x1, y1, x2, y2, score, cls) in source pixels, or [] when nothing is found; a single image gives its result, a batch a list."""
+        from ..tiling import TilePlan, Tiling
+        if not isinstance(tiling, Tiling):
+            raise TypeError(f"tiling: expected a simple_pose_amd.tiling.Tiling, got {type(tiling).__name__}")
+        if isinstance(img, (list, tuple)):
+            if len(img) == 0 or len({tuple(np.shape(i)) for i in img}) != 1:
+                raise ValueError("predict_tiled takes images of one size (tiling differently sized images is not supported)")
+            img = torch.stack(list(img)) if isinstance(img[0], torch.Tensor) else np.stack([np.asarray(i) for i in img])
+        src = _as_cuda_u8(img, self.device)
+        single = src.dim() == 3
+        if single:
+            src = src[None]
+        if 0 in tuple(src.shape):
+            raise ValueError(f"expected uint8 BGR [H, W, 3] or [B, H, W, 3], got {tuple(src.shape)}")
+        tp = TilePlan(tiling, self.transform, src, max_det)          # every check before the first launch
+        B = src.shape[0]
+        det = torch.empty((B, max_det, 6), dtype=torch.float32, device=src.device)
+        cs = torch.empty((2, B), dtype=torch.int32, device=src.device)           # counts, status
+        self.detect_tiled(tp, self.tile_programs(tp), det, cs[0], cs[1], max_det, tiling)
+        h = cs.cpu().numpy()
+        if (h[1] & 1).any():
+            raise HipLibraryError(f"image {int(np.nonzero(h[1] & 1)[0][0])}: a pass has more than {_lib.SP_YOLO_NMS_MAX_CANDIDATES} detector "
+                                  "candidates after the multi-label expansion (raise conf_thresh)")
+        out = [det[b, :int(h[0][b])] if h[0][b] > 0 else [] for b in range(B)]
+        return out[0] if single else out

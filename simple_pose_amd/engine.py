@@ -321,6 +321,12 @@ class Program:
             if not g:
                 raise ValueError("letterbox: set the source geometry first (engine.set_letterbox)")
             H, W, _ = self.shapes[op.dst]
+            if g.get("tiles"):                     # the input is a table of sp_tile_ref, one per pass (set_letterbox_tiles)
+                table = bufs[op.src]
+                if table.dtype != torch.uint8 or tuple(table.shape) != (B, ctypes.sizeof(_lib.TileRef)) or not table.is_contiguous():
+                    raise ValueError(f"letterbox: expected a contiguous uint8 [{B}, {ctypes.sizeof(_lib.TileRef)}] table of sp_tile_ref")
+                _lib.check(lib.sp_yolo_letterbox_tiles(P(table), B, 2 * H, 2 * W, _lib.SP_LETTERBOX_FOCUS, P(bufs[op.dst]), stream), op.name)
+                return
             if g.get("images"):                    # the input is a table of sp_image_ref, one per image (set_letterbox_images)
                 table = bufs[op.src]
                 if table.dtype != torch.uint8 or tuple(table.shape) != (B, ctypes.sizeof(_lib.ImageRef)) or not table.is_contiguous():
@@ -1527,5 +1533,18 @@ def set_letterbox_images(prog: Program) -> None:
         if op.kind == "letterbox":
             op.args[0].clear()
             op.args[0].update(images=True)
+            return
+    raise ValueError("program has no letterbox launch (source='u8')")
+
+
+def set_letterbox_tiles(prog: Program) -> None:
+    """A third source form of a yolov5_program(source="u8"): the next run's input is a table of `sp_tile_ref` (_lib.TileRef) in device
+    memory, a contiguous uint8 tensor [B, sizeof(sp_tile_ref)]: every entry is a rectangle of a larger frame with the frame's row pitch
+    (sp_yolo_letterbox_tiles; tiling.py packs the table).  The caller guarantees what the table holds and keeps the frames alive until
+    the run has finished.  set_letterbox switches back."""
+    for op in prog.ops:
+        if op.kind == "letterbox":
+            op.args[0].clear()
+            op.args[0].update(tiles=True)
             return
     raise ValueError("program has no letterbox launch (source='u8')")

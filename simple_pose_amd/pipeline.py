@@ -6,6 +6,7 @@
     res = est.estimate_batch([img_a, img_b, ...]) # differently sized images (numpy or CUDA) -> list of PoseResult, caller's order
     res = est.estimate_files(jpeg_files)          # JpegDecoder.decode, then that batch on the decoder's device tensors
     res = est.estimate_boxes(imgs, det, counts)   # caller-supplied detections (the reference's predicts_by_pred path)
+    est = TopDownPoseEstimator(..., tiling=Tiling())   # large frames: the detector on overlapping tiles, fused on the device
 
 The reference runs the three stages as three offline scripts joined by JSON files (eval.py: gen_data_by_detector, predicts_by_pred,
 temp_read_in_and_filter).  Here a frame is one stream of launches: letterbox + YOLOv5 + decode, sp_yolo_nms_device, sp_yolo_boxes_to_source,
@@ -25,7 +26,12 @@ A list of differently sized images is one call too (mixed_batch.py): the images 
 detector forward whose letterbox launch reads every image's own geometry from a table of sp_image_ref in device memory
 (sp_yolo_letterbox_images), sp_yolo_boxes_to_source_images scatters the groups' detections into the caller's order, and from
 sp_topdown_plan on there is one of everything for the whole batch, the crops by sp_warp_affine_plan_images_u8c3.  Eager: the table upload
-is not capturable."""
+is not capturable.
+With `tiling=Tiling(...)` (tiling.py) the detector half of `estimate` and same-sized `estimate_batch` runs on overlapping tiles of the
+frame at their native resolution, and on the whole frame: a table of sp_tile_ref points into the frame's static source, the passes of one
+net shape are one detector forward whose letterbox launch reads them through the table (sp_yolo_letterbox_tiles), sp_yolo_nms_device and
+sp_yolo_boxes_to_frame_tiles bring every pass's boxes into frame coordinates, and sp_yolo_merge_passes fuses them into the `det` /
+`counts` that sp_topdown_plan reads.  The table is built and uploaded once per frame shape, so `estimate` stays ONE graph."""
 from __future__ import annotations
 
 import ctypes
@@ -41,6 +47,7 @@ from ._lib import HipLibraryError
 from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
 from .datasets.jpeg import JpegDecoder, JpegEncoder
 from .mixed_batch import MixedBatch, check_det_counts, check_images
+from .tiling import TilePlan, Tiling, plan_pass_groups
 from .visualize import PoseRenderer
 
 P = _lib.ptr
@@ -116,6 +123,7 @@ class _Frame:
         self.graph = None
         self.params = None
         self.keepalive = None
+        self.tiles = None                # tiling.TilePlan: built with the first tiled detector frame of this shape
         self.canvas = None               # [B, H, W, 3] and the primitive array: allocated with the first frame of an estimator that has a renderer
         self.render_ws = None
 
@@ -139,14 +147,17 @@ class TopDownPoseEstimator(object):
     `use_graph`: `estimate` (batch 1) replays one captured graph per source shape (an LRU of MAX_GRAPHS shapes); False launches eagerly.
     `flip_test`: every crop also goes through the pose network mirrored (one forward on 2 x capacity crops) and the two sets of heat maps
     are merged before the decode (metrics.flip); `joint_pairs`: the left/right joints that swap (default: COCO's eight pairs);
-    `shift_heatmap`: Simple-Baselines' SHIFT_HEATMAP on the un-mirrored maps.  `estimate`, `estimate_batch` and `estimate_boxes` honour it."""
+    `shift_heatmap`: Simple-Baselines' SHIFT_HEATMAP on the un-mirrored maps.  `estimate`, `estimate_batch` and `estimate_boxes` honour it.
+    `tiling`: a `tiling.Tiling` - the detector runs on overlapping tiles of every frame (and on the whole frame) and the boxes are fused
+    on the device, so that small persons in large frames are found; `estimate`, same-sized `estimate_batch` and the trackers' detector
+    frames honour it, a list of differently sized images together with it is refused, `estimate_boxes` has no detector to tile."""
 
     MAX_GRAPHS = 8
     MAX_DET = 300                    # non_max_suppression's default, what single_predict uses
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
                  in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
-                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None):
+                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None, tiling=None):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -177,6 +188,9 @@ class TopDownPoseEstimator(object):
         if encoder is not None and encoder.device != torch.device(detector.device):
             raise HipLibraryError(f"encoder: on {encoder.device}, the detector on {detector.device}")
         self.encoder = encoder
+        if tiling is not None and not isinstance(tiling, Tiling):
+            raise TypeError(f"tiling: expected a simple_pose_amd.tiling.Tiling or None, got {type(tiling).__name__}")
+        self.tiling = tiling
         self._perm = None
         self.detector, self.pose_model, self.decoder = detector, pose_model, decoder
         self.capacity, self.person_cls, self.min_box_score = capacity, person_cls, float(min_box_score)
@@ -259,12 +273,43 @@ class TopDownPoseEstimator(object):
     # -- the frame: every launch between the source image and the packed result -------------------------------------------------------
     def _params(self, det_prog, pose_prog) -> tuple:
         d = self.detector
+        det_id = tuple(id(p) for p in det_prog) if isinstance(det_prog, tuple) else id(det_prog)
         return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
-                id(det_prog), id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap,
-                None if self.renderer is None else self.renderer.key())
+                det_id, id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap,
+                None if self.renderer is None else self.renderer.key(), None if self.tiling is None else self.tiling.key())
+
+    def _det_program(self, B: int, H: int, W: int):
+        """What `_detect` runs on B frames of H x W: the detector program of their letterboxed shape, or, with a tiling, the programs of
+        the passes' net-shape groups (a tuple, in group order).  Raises before any launch what the tiling refuses for this shape."""
+        d = self.detector
+        if self.tiling is None:
+            g = d.transform.geometry(H, W)
+            return d.program(g["out_h"], g["out_w"])
+        _, groups = plan_pass_groups(self.tiling.plan_call(B, H, W), d.transform)
+        return tuple(d.program(out_h, out_w) for (out_h, out_w), _ in groups)
+
+    def _det_keepalive(self, fr: _Frame, det_prog) -> tuple:
+        """What a captured detector half points into: the programs, their activation pools and the NMS workspaces."""
+        if det_prog is None:
+            return (None, None, None)
+        if isinstance(det_prog, tuple):
+            return (det_prog, fr.tiles, tuple(fr.tiles.keepalive))
+        return (det_prog, det_prog.pool_for(fr.B, self.device), getattr(fr, "ws", None))
+
+    def _detect_tiled(self, fr: _Frame, det_progs: tuple, single_stream: bool) -> None:
+        """_detect with a tiling: detector.detect_tiled over the table that points into the frame's static source.  The table is built
+        and uploaded with the first call of a frame shape (never inside a capture: every capture here is preceded by a warm-up run)."""
+        d = self.detector
+        if fr.tiles is None or fr.tiles.key != TilePlan.key_of(self.tiling, d.transform, fr.src, fr.max_det):
+            if torch.cuda.is_current_stream_capturing():
+                raise HipLibraryError("tiled detection: the table of passes cannot be uploaded inside a stream capture")
+            fr.tiles = TilePlan(self.tiling, d.transform, fr.src, fr.max_det)
+        d.detect_tiled(fr.tiles, det_progs, fr.det, fr.counts, fr.status, fr.max_det, self.tiling, single_stream)
 
     def _detect(self, fr: _Frame, det_prog, single_stream: bool = False) -> None:
         """letterbox + network + head decode, NMS and the un-letterbox, all on the device (what single_predict / predict compute)."""
+        if isinstance(det_prog, tuple):              # the programs of a tiling's groups (_det_program)
+            return self._detect_tiled(fr, det_prog, single_stream)
         lib, d = _lib.lib(), self.detector
         from .detector.yolov5_detector import _workspace
         g = d.transform.geometry(fr.H, fr.W)
@@ -339,7 +384,7 @@ class TopDownPoseEstimator(object):
             self._render(fr, pose_prog.out_shape[0])
         fr.graph, fr.params = graph, self._params(det_prog, pose_prog)
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
-        fr.keepalive = (det_prog, pose_prog, det_prog.pool_for(fr.B, dev), pose_prog.pool_for(self._pose_batch(), dev), fr.ws)
+        fr.keepalive = (pose_prog, pose_prog.pool_for(self._pose_batch(), dev)) + self._det_keepalive(fr, det_prog)
 
     def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
         """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
@@ -368,9 +413,7 @@ class TopDownPoseEstimator(object):
         # call, replays included.  It is what notices in-place weight updates (and forces the re-capture); it is also host time that a
         # replay does not get back, one reason the graphed frame is no faster than the eager one while the GPU is the longer side.
         B, H, W = imgs.shape[0], imgs.shape[1], imgs.shape[2]
-        d = self.detector
-        g = d.transform.geometry(H, W)
-        det_prog = d.program(g["out_h"], g["out_w"])
+        det_prog = self._det_program(B, H, W)
         pose_prog = self._pose_program()
         fr = self._frame(B, H, W, self.MAX_DET, pose_prog.out_shape[0])
         self._load(fr, imgs)
@@ -429,6 +472,8 @@ class TopDownPoseEstimator(object):
     def _run_mixed(self, imgs, det=None, counts=None) -> List[PoseResult]:
         """estimate_batch / estimate_boxes on a list of differently sized images.  Eager: the table upload is not capturable."""
         n = len(check_images(imgs))                  # every check before the first launch
+        if det is None and self.tiling is not None:
+            raise ValueError("tiling: the images of one call share one size (tiled detection of differently sized images is not supported)")
         M = self.MAX_DET if det is None else check_det_counts(n, det, counts)
         if getattr(self.detector, "transform", None) is None:
             # without the detector's letterbox the images cannot be grouped by net shape: the dense path's rule is all that is left

@@ -236,8 +236,8 @@ class PoseTracker(object):
         graph = torch.cuda.CUDAGraph()
         with torch.cuda.graph(graph):
             self._launch(fr, detect, det_prog, pose_prog, True)
-        keepalive = (det_prog, pose_prog, None if det_prog is None else det_prog.pool_for(1, dev), pose_prog.pool_for(est._pose_batch(), dev),
-                     getattr(fr, "ws", None), self.state, self._sim, self.smooth_state)
+        keepalive = (pose_prog, pose_prog.pool_for(est._pose_batch(), dev), self.state, self._sim, self.smooth_state) + \
+            est._det_keepalive(fr, det_prog)
         self._graphs.pop(key, None)
         if len(self._graphs) >= self.MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
@@ -262,8 +262,7 @@ class PoseTracker(object):
         detect = self._prev_n == 0 or self._since_detect >= self.detect_every
         det_prog = None
         if detect:
-            g = est.detector.transform.geometry(H, W)
-            det_prog = est.detector.program(g["out_h"], g["out_w"])
+            det_prog = est._det_program(1, H, W)
         pose_prog = est._pose_program()
         J = pose_prog.out_shape[0]
         self._ensure_state(J)
@@ -442,8 +441,8 @@ class MultiStreamTracker(object):
         with torch.cuda.graph(graph):
             self._launch(fr, detect, det_prog, pose_prog, True)
         # the nodes hold raw pointers into both programs' activation pools for the batch sizes used: keep them alive
-        keepalive = (det_prog, pose_prog, None if det_prog is None else det_prog.pool_for(fr.B, dev), pose_prog.pool_for(est._pose_batch(), dev),
-                     getattr(fr, "ws", None), self.state, self._sim, self.smooth_state)
+        keepalive = (pose_prog, pose_prog.pool_for(est._pose_batch(), dev), self.state, self._sim, self.smooth_state) + \
+            est._det_keepalive(fr, det_prog)
         self._graphs.pop(key, None)
         if len(self._graphs) >= self.MAX_GRAPHS:
             self._graphs.pop(next(iter(self._graphs)))
@@ -476,8 +475,7 @@ class MultiStreamTracker(object):
         detect = self._fresh or self._since_detect >= self.detect_every or not any(self._prev_n)
         det_prog = None
         if detect:
-            g = est.detector.transform.geometry(H, W)
-            det_prog = est.detector.program(g["out_h"], g["out_w"])
+            det_prog = est._det_program(S, H, W)
         pose_prog = est._pose_program()
         J = pose_prog.out_shape[0]
         self._ensure_state(J)

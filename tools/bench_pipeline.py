@@ -23,6 +23,11 @@ the key "flip_test"; the other keys of the file stay.
 8 and 32, in images per second, into profiles/pipeline_mixed_bench.json under "mixed".  --mixed-baseline runs the one-by-one variants only
 and writes them under "baseline_one_by_one": that half uses nothing newer than `estimate`, so the same file can be run from the tree of an
 older commit to measure it there on the same box.
+
+--tiled measures tiled detection (simple_pose_amd/tiling.py) on a seeded 3840x2160 frame with the default `Tiling` (the frame and 8 x 4
+tiles of 640x640), in ms per `estimate`: untiled, tiled (eager and one graph), and the staged equivalent - single_predict on the frame,
+predict on contiguous copies of the tiles, the shift and the merge in numpy, then estimate_boxes - into
+profiles/pipeline_tiled_bench.json.
 """
 from __future__ import annotations
 
@@ -241,8 +246,73 @@ def mixed_bench(args, det, decoder):
     print("wrote", args.out)
 
 
+def tiled_bench(args, det, decoder):
+    """ms per frame on one seeded 3840x2160 frame, fp32 DConv, capacity 32, the variants alternated:
+      untiled_graph            `estimate` without a tiling (one graph): what the frame cost before, finding no small person
+      tiled_graph / _eager     `estimate` with the default Tiling: 33 passes, two detector forwards, the fusion on the device
+      staged                   the same result from public calls through the host (its numpy merge alone: staged_merge_ms)
+      tiled_graph2             tiled_graph again: the measurement's own spread"""
+    from simple_pose_amd.tiling import Tiling
+    from tests import tiled_ref
+    H, W = 2160, 3840
+    img = np.random.default_rng(0).integers(0, 256, (H, W, 3), dtype=np.uint8)
+    tiling = Tiling()
+    passes = tiling.plan(H, W)
+    model = pose_model("dconv", "fp32")
+    plain = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY)
+    tiled = TopDownPoseEstimator(det, model, decoder=decoder, capacity=CAPACITY, tiling=tiling)
+    merge_ms = []
+
+    def staged():
+        whole = det.single_predict(img)
+        tiles = det.predict([np.ascontiguousarray(img[y:y + h, x:x + w]) for y, x, h, w in passes[1:]])
+        rows = []
+        for (y0, x0, _, _), r in zip(passes, [whole] + tiles):
+            r = np.zeros((0, 6), np.float32) if isinstance(r, list) else r.cpu().numpy()
+            r[:, 0] += np.float32(x0); r[:, 2] += np.float32(x0); r[:, 1] += np.float32(y0); r[:, 3] += np.float32(y0)
+            rows.append(r)
+        cat = np.concatenate(rows, 0)
+        t0 = time.perf_counter()
+        keep = tiled_ref.merge_rows_np(cat, tiling.metric, tiling.thresh, tiling.agnostic, plain.MAX_DET)
+        merge_ms.append((time.perf_counter() - t0) * 1e3)
+        if len(keep) == 0:
+            return plain.estimate_boxes(img, np.zeros((1, 6), np.float32), [0])[0], int(cat.shape[0])
+        return plain.estimate_boxes(img, cat[keep])[0], int(cat.shape[0])
+
+    frame = lambda est, graph: (setattr(est, "use_graph", graph), est.estimate(img))[1]
+    variants = {"untiled_graph": lambda: frame(plain, True), "tiled_graph": lambda: frame(tiled, True), "tiled_eager": lambda: frame(tiled, False),
+                "staged": lambda: staged()[0], "tiled_graph2": lambda: frame(tiled, True)}
+    first = {k: fn() for k, fn in variants.items()}
+    n_cand = staged()[1]
+    reps, warm = (3, 1) if args.quick else (15, 3)
+    merge_ms.clear()
+    times = {k: [] for k in variants}
+    for r in range(warm + reps):
+        for k, fn in variants.items():
+            t = wall_ms(fn)
+            if r >= warm:
+                times[k].append(t)
+    res = {"device": torch.cuda.get_device_name(0), "commit": args.commit or git_commit(), "source": [H, W], "tiling": list(tiling.key()),
+           "passes": len(passes), "detector": "s fp32", "pose": "resnet50-dconv fp32", "pose_autotune": False, "capacity": CAPACITY, "reps": reps,
+           "candidates_before_merge": n_cand, "poses_kept": {k: len(v) for k, v in first.items()},
+           "tiled_equals_staged": bool(first["tiled_graph"].coco(0) == first["staged"].coco(0) == first["tiled_eager"].coco(0)),
+           "one_graph": bool(len(tiled._frames) == 1 and next(iter(tiled._frames.values())).graph is not None)}
+    res.update({k: summary(v) for k, v in times.items()})
+    res["staged_merge_ms"] = float(np.median(merge_ms))
+    res["tiled_graph_self_spread_ms"] = abs(res["tiled_graph"]["median_ms"] - res["tiled_graph2"]["median_ms"])
+    res["staged_over_tiled_graph"] = res["staged"]["median_ms"] / res["tiled_graph"]["median_ms"]
+    res["tiled_graph_over_untiled_graph"] = res["tiled_graph"]["median_ms"] / res["untiled_graph"]["median_ms"]
+    print(json.dumps(res), flush=True)
+    if not args.quick:
+        with open(args.out, "w") as fh:
+            json.dump({"tiled": res}, fh, indent=1)
+        print("wrote", args.out)
+
+
 def main():
     ap = argparse.ArgumentParser()
+    ap.add_argument("--tiled", action="store_true", help="tiled detection on a 3840x2160 frame: untiled vs tiled vs the staged equivalent "
+                    "(default --out: profiles/pipeline_tiled_bench.json)")
     ap.add_argument("--mixed", action="store_true", help="a seeded set of differently sized images: estimate one by one vs estimate_batch on "
                     "lists of 8 and 32 (default --out: profiles/pipeline_mixed_bench.json)")
     ap.add_argument("--mixed-baseline", action="store_true", help="--mixed, the one-by-one variants only (runs on commits without mixed batches)")
@@ -253,12 +323,15 @@ def main():
     args = ap.parse_args()
     args.mixed = args.mixed or args.mixed_baseline
     if args.out is None:
-        args.out = os.path.join(ROOT, "profiles", "pipeline_mixed_bench.json" if args.mixed else "pipeline_bench.json")
+        args.out = os.path.join(ROOT, "profiles", "pipeline_tiled_bench.json" if args.tiled else
+                                "pipeline_mixed_bench.json" if args.mixed else "pipeline_bench.json")
     reps, warm = (5, 2) if args.quick else (40, 5)
     det = YOLOv5Detector(num_cls=80, scale_name="s", device=DEV, slice_idx=0, state_dict=detector_state_dict(YOLOv5(scale_name="s", num_cls=80), 14))
     det.conf_thresh, det.iou_thresh = 0.02, 0.45
     if args.mixed:
         return mixed_bench(args, det, GaussTaylorKeyPointDecoder())
+    if args.tiled:
+        return tiled_bench(args, det, GaussTaylorKeyPointDecoder())
     img = np.random.default_rng(0).integers(0, 256, (640, 640, 3), dtype=np.uint8)
     dev_img = torch.from_numpy(img).to(DEV)
     found = det.single_predict(img)
