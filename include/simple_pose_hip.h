@@ -1202,6 +1202,58 @@ int sp_jpeg_enc_plan(int width, int height, int subsampling, int quality, int re
 int sp_jpeg_encode_batch(const sp_jpeg_enc_desc* descs_host, const sp_jpeg_enc_desc* descs_dev, int count, void* workspace, int64_t workspace_size,
                          uint8_t* out, int64_t out_size, int32_t* length, int32_t* status, int stages, void* stream);
 
+/* ---- video frames: YUV 4:2:0 (NV12 / I420) <-> packed BGR on the device ------------------------------------------------------------------------
+ * (No new ABI version: these are additions.)  What decoders hand out and encoders take: h x w luma samples (1 <= h, w <= 32767, odd sizes
+ * legal) and ch x cw chroma samples, ch = (h + 1) / 2, cw = (w + 1) / 2.
+ *   SP_YUV_NV12   a Y plane of pitch_y bytes per row and a UV plane of pitch_c bytes per row holding U, V byte pairs (`u` = the UV plane);
+ *   SP_YUV_I420   Y, U and V planes; U and V share pitch_c.
+ * Pitches are in bytes and may exceed the row (pitch_y >= w; pitch_c >= 2 * cw for NV12, >= cw for I420; pitch_bgr >= 3 * w); neither base
+ * pointers nor pitches need any alignment.  The arithmetic is libjpeg's 16.16 fixed point, int32, `>>` arithmetic, clamp8 = clamp to 0..255:
+ *   YUV -> BGR, pixel (r, c) with the chroma sample (r >> 1, c >> 1) (replication):  yy = Y - yoff, uu = U - 128, vv = V - 128,
+ *       R = clamp8((ay*yy + rv*vv + 32768) >> 16)   G = clamp8((ay*yy - gu*uu - gv*vv + 32768) >> 16)   B = clamp8((ay*yy + bu*uu + 32768) >> 16)
+ *   BGR -> YUV, per pixel  Yp = (yr*R + yg*G + yb*B + (yoff << 16) + 32768) >> 16,  Up = (ur*R + ug*G + ub*B + (128 << 16) + 32767) >> 16,
+ *       Vp likewise with vr, vg, vb; chroma sample (i, j) = (sum of Up + 2) >> 2 over the pixels (min(2i + a, h - 1), min(2j + b, w - 1)),
+ *       a, b in {0, 1} (an edge pixel counts twice at an odd size).  No clamp: Y 0..255 / 16..235, U and V 0..255 / 16..240 (full / limited).
+ *   matrix / range    yoff    ay     rv      bu     gu     gv     yr     yg    yb     ur      ug     ub     vr      vg     vb
+ *   BT.601 full          0  65536  91881  116130  22554  46802  19595  38470  7471  -11059  -21709  32768  32768  -27439  -5329
+ *   BT.601 limited      16  76309 104597  132201  25675  53279  16829  33039  6416   -9714  -19071  28784  28784  -24103  -4681
+ *   BT.709 full          0  65536 103206  121609  12276  30679  13933  46871  4732   -7509  -25259  32768  32768  -29763  -3005
+ *   BT.709 limited      16  76309 117489  138438  13975  34925  11966  40254  4064   -6596  -22189  28784  28784  -26145  -2639
+ * (round(c * 65536) of the ITU definitions; BT.601 full range keeps libjpeg's table, so it equals the JPEG decoder's and encoder's colour
+ * functions bit for bit.)  Every channel is within 1 level of the float64 definition rounded half up.
+ * Each call is ONE launch and nothing synchronises.  A thread owns 2-row x 16-column patches, so chroma is read (or averaged) once and no
+ * thread needs another's pixels; only bytes inside [row * pitch, row * pitch + row bytes) are written, pitch padding stays untouched.
+ * A frame whose plane pointers, BGR pointer and three pitches are ALL multiples of 16 takes 16-byte accesses on its full patches
+ * (sp_yuv420_wide_path says so); its tail columns, the last row of an odd height, and every other frame go byte by byte: same bits. */
+#define SP_YUV_NV12 0
+#define SP_YUV_I420 1
+#define SP_YUV_BT601 0
+#define SP_YUV_BT709 1
+#define SP_YUV_LIMITED 0
+#define SP_YUV_FULL 1
+typedef struct sp_yuv_ref {                 /* one frame; read from DEVICE memory by the _images entry points */
+    unsigned char *y, *u, *v;               /* device pointers; NV12: u = the UV plane, v unused */
+    unsigned char* bgr;                     /* [h, w, 3], pitch_bgr bytes per row */
+    int32_t h, w, pitch_y, pitch_c, pitch_bgr;
+    int32_t format, matrix, range;
+} sp_yuv_ref;                               /* 64 bytes */
+/* One frame, planes -> bgr.  Checked on the host (SP_EINVAL and a message, nothing launched): sizes, pitches below the row, the format /
+ * matrix / range codes, NULL planes (v may be NULL for NV12), and bgr overlapping a plane. */
+int sp_yuv420_to_bgr_u8c3(const unsigned char* y, const unsigned char* u, const unsigned char* v, int h, int w, int pitch_y, int pitch_c,
+                          int format, int matrix, int range, unsigned char* bgr, int pitch_bgr, void* stream);
+/* One frame, bgr -> planes; the same checks, with the planes as the outputs (they must not overlap bgr or each other). */
+int sp_bgr_to_yuv420_u8c3(const unsigned char* bgr, int pitch_bgr, int h, int w, int format, int matrix, int range, unsigned char* y,
+                          unsigned char* u, unsigned char* v, int pitch_y, int pitch_c, void* stream);
+/* `count` frames of any sizes, formats and modes in one launch (count <= 65535; count == 0 launches nothing): frame i as frames_dev[i]
+ * describes it, with the bits of the single-frame call on that frame (the same device functions).  max_h, max_w (1 .. 32767): bounds of the
+ * frames' sizes, which size the grid.  The table's contents cannot be checked on the host: the caller guarantees valid pointers and what
+ * the single-frame calls check; a frame whose sizes, pitches or codes those calls would refuse, or with a NULL plane, is skipped. */
+int sp_yuv420_to_bgr_images_u8c3(const sp_yuv_ref* frames_dev, int count, int max_h, int max_w, void* stream);
+int sp_bgr_to_yuv420_images_u8c3(const sp_yuv_ref* frames_dev, int count, int max_h, int max_w, void* stream);
+/* 1 when a frame with these pointers and pitches takes the 16-byte path on its full patches, 0 when it goes byte by byte (the predicate
+ * the kernels evaluate; v is not looked at for NV12).  Launches nothing. */
+int sp_yuv420_wide_path(const void* y, const void* u, const void* v, const void* bgr, int pitch_y, int pitch_c, int pitch_bgr, int format);
+
 #ifdef __cplusplus
 }
 #endif

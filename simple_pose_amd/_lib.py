@@ -123,6 +123,19 @@ class TileRef(ctypes.Structure):
 
 
 SP_TILE_MAX_TILES, SP_TILE_MAX_PASSES = 64, 65
+
+
+class YuvRef(ctypes.Structure):
+    """Mirror of `sp_yuv_ref` (field order is ABI): one YUV 4:2:0 frame and its BGR image, all device pointers, pitches in bytes.  An array of
+    them is built on the host and uploaded; the `_images` kernels read it from device memory."""
+    _fields_ = [("y", ctypes.c_uint64), ("u", ctypes.c_uint64), ("v", ctypes.c_uint64), ("bgr", ctypes.c_uint64), ("h", c_int32), ("w", c_int32),
+                ("pitch_y", c_int32), ("pitch_c", c_int32), ("pitch_bgr", c_int32), ("format", c_int32), ("matrix", c_int32), ("range", c_int32)]
+
+
+assert ctypes.sizeof(YuvRef) == 64
+SP_YUV_NV12, SP_YUV_I420 = 0, 1
+SP_YUV_BT601, SP_YUV_BT709 = 0, 1
+SP_YUV_LIMITED, SP_YUV_FULL = 0, 1
 SP_TILE_IOU, SP_TILE_IOS = 0, 1
 
 # every symbol include/simple_pose_hip.h declares: name -> (restype, argtypes)
@@ -288,6 +301,11 @@ SYMBOLS = {
     "sp_jpeg_encode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int, _P]),
     "sp_render_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
     "sp_render_poses_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RenderStyle), _P, _P]),
+    "sp_yuv420_to_bgr_u8c3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
+    "sp_bgr_to_yuv420_u8c3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P]),
+    "sp_yuv420_to_bgr_images_u8c3": (c_int, [_P, c_int, c_int, c_int, _P]),
+    "sp_bgr_to_yuv420_images_u8c3": (c_int, [_P, c_int, c_int, c_int, _P]),
+    "sp_yuv420_wide_path": (c_int, [_P, _P, _P, _P, c_int, c_int, c_int, c_int]),
 }
 
 _lib = None

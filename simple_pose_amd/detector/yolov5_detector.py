@@ -14,6 +14,7 @@ import torch
 
 from .. import _lib, engine
 from .._lib import HipLibraryError
+from ..video import YuvFrame, to_bgr
 from .nets.yolov5 import YOLOv5
 
 _WS: Dict[Tuple[str, int], torch.Tensor] = {}
@@ -171,7 +172,10 @@ class YOLOv5Detector(object):
 
     @torch.no_grad()
     def single_predict(self, img):
-        """uint8 BGR [H, W, 3] (numpy or CUDA) -> CUDA fp32 [n, 6] (x1, y1, x2, y2, score, cls) in source pixels, or [] when nothing is found."""
+        """uint8 BGR [H, W, 3] (numpy or CUDA), or a video.YuvFrame -> CUDA fp32 [n, 6] (x1, y1, x2, y2, score, cls) in source pixels, or []
+        when nothing is found."""
+        if isinstance(img, YuvFrame):                # a video frame: converted on the device (one launch), then as a CUDA image
+            img = to_bgr(img, device=self.device)
         src = _as_cuda_u8(img, self.device)
         if src.dim() != 3:
             raise ValueError("single_predict takes one image [H, W, 3]")
@@ -184,13 +188,16 @@ class YOLOv5Detector(object):
     def predict(self, imgs: Union[torch.Tensor, Sequence[np.ndarray]]) -> list:
         """A batch of same-sized uint8 BGR images (CUDA [B, H, W, 3], or a list of [H, W, 3] arrays) in one forward and one NMS launch
         sequence; per image what single_predict returns.  A list of differently sized images (numpy or CUDA) is grouped by letterboxed
-        net shape: one forward and one NMS sequence per group, every image letterboxed as single_predict letterboxes it alone."""
+        net shape: one forward and one NMS sequence per group, every image letterboxed as single_predict letterboxes it alone.  A list
+        may hold video.YuvFrames (or be one): it goes the grouped way, its frames converted to BGR on the device by one launch first."""
         if isinstance(imgs, torch.Tensor):
             src = _as_cuda_u8(imgs, self.device)
             if src.dim() != 4:
                 raise ValueError("predict takes a batch [B, H, W, 3]")
         else:
-            if len({tuple(np.shape(i)) for i in imgs}) != 1 or any(isinstance(i, torch.Tensor) for i in imgs):
+            if isinstance(imgs, YuvFrame):
+                imgs = [imgs]
+            if len({tuple(np.shape(i)) for i in imgs}) != 1 or any(isinstance(i, (torch.Tensor, YuvFrame)) for i in imgs):
                 return self._predict_mixed(imgs)
             src = _as_cuda_u8(np.stack([np.asarray(i) for i in imgs]), self.device)
         g = self.transform.geometry(src.shape[1], src.shape[2])
@@ -266,6 +273,8 @@ class YOLOv5Detector(object):
         from ..tiling import TilePlan, Tiling
         if not isinstance(tiling, Tiling):
             raise TypeError(f"tiling: expected a simple_pose_amd.tiling.Tiling, got {type(tiling).__name__}")
+        if isinstance(img, YuvFrame):                # a video frame: converted on the device (one launch), then as a CUDA image
+            img = to_bgr(img, device=self.device)
         if isinstance(img, (list, tuple)):
             if len(img) == 0 or len({tuple(np.shape(i)) for i in img}) != 1:
                 raise ValueError("predict_tiled takes images of one size (tiling differently sized images is not supported)")

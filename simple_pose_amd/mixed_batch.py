@@ -18,6 +18,7 @@ import numpy as np
 import torch
 
 from ._lib import HipLibraryError, ImageRef, _device_index
+from .video import YuvFrame, resolve
 
 MAX_SIDE = 32767                     # the warp's fixed-point sample position holds source coordinates in a short
 REF_BYTES = ctypes.sizeof(ImageRef)
@@ -25,13 +26,17 @@ REF_BYTES = ctypes.sizeof(ImageRef)
 
 def check_images(imgs) -> List[Tuple[int, int]]:
     """A list of uint8 BGR images [H_i, W_i, 3], numpy or CUDA -> their (h, w).  Raises before anything is launched: ValueError for an empty
-    list and a bad or zero-sized shape, TypeError for another dtype, HipLibraryError for a CPU tensor."""
+    list and a bad or zero-sized shape, TypeError for another dtype, HipLibraryError for a CPU tensor.  A video.YuvFrame (checked when it
+    was made) stands for the BGR image it converts to."""
     if not isinstance(imgs, (list, tuple)):
         raise TypeError(f"expected a list of uint8 BGR images, got {type(imgs).__name__}")
     if len(imgs) == 0:
         raise ValueError("an empty list of images")
     shapes = []
     for i, im in enumerate(imgs):
+        if isinstance(im, YuvFrame):
+            shapes.append((im.height, im.width))
+            continue
         if isinstance(im, torch.Tensor):
             if not im.is_cuda:
                 raise HipLibraryError(f"image {i}: tensor is on {im.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
@@ -102,7 +107,8 @@ def pack_image_refs(ptrs: Sequence[int], shapes, geoms, groups):
 
 class MixedBatch(object):
     """One call's images on the device and their table.  CUDA inputs are referenced in place (a non-contiguous one is made contiguous);
-    numpy inputs and the table share one pinned staging buffer and reach the device in one copy on the current stream.  `stage`: a dict
+    numpy inputs and the table share one pinned staging buffer and reach the device in one copy on the current stream.  YuvFrames among
+    the inputs are converted to BGR CUDA tensors first, all of them by one table launch (video.resolve), and then are CUDA inputs.  `stage`: a dict
     the owner keeps between calls, so that the pinned buffer and the device arena are allocated once and grown on demand; the owner
     synchronises with the stream before it starts the next call (every public call here ends in a fetch or a synchronous NMS).
       srcs          the B images as CUDA tensors [H_i, W_i, 3] (this object keeps them, and the arena, alive)
@@ -115,15 +121,18 @@ class MixedBatch(object):
         for i, im in enumerate(imgs):
             if isinstance(im, torch.Tensor) and im.device != device:
                 raise HipLibraryError(f"image {i}: on {im.device}, the detector on {device}")
+            if isinstance(im, YuvFrame) and not im.is_host and im.device != device:
+                raise HipLibraryError(f"image {i}: on {im.device}, the detector on {device}")
+        stage = {} if stage is None else stage
         self.B = B = len(imgs)
         self.geoms, self.groups = plan_groups(self.shapes, transform)
+        imgs = resolve(imgs, device, stage.setdefault("yuv", {}))
         align = lambda n: (n + 255) // 256 * 256
         off, where = align(2 * B * REF_BYTES), {}
         for i, im in enumerate(imgs):
             if isinstance(im, np.ndarray):
                 where[i] = off
                 off += align(im.size)
-        stage = {} if stage is None else stage
         if stage.get("host") is None or stage["host"].numel() < off or stage["dev"].device != device:
             stage["host"] = torch.empty(off, dtype=torch.uint8, pin_memory=True)
             stage["dev"] = torch.empty(off, dtype=torch.uint8, device=device)

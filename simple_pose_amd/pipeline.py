@@ -6,6 +6,7 @@
     res = est.estimate_batch([img_a, img_b, ...]) # differently sized images (numpy or CUDA) -> list of PoseResult, caller's order
     res = est.estimate_files(jpeg_files)          # JpegDecoder.decode, then that batch on the decoder's device tensors
     res = est.estimate_boxes(imgs, det, counts)   # caller-supplied detections (the reference's predicts_by_pred path)
+    res = est.estimate(YuvFrame(...))             # a video frame (video.py: NV12 / I420 planes) wherever an image is taken
     est = TopDownPoseEstimator(..., tiling=Tiling())   # large frames: the detector on overlapping tiles, fused on the device
 
 The reference runs the three stages as three offline scripts joined by JSON files (eval.py: gen_data_by_detector, predicts_by_pred,
@@ -48,6 +49,7 @@ from .metrics.flip import COCO_JOINT_PAIRS, check_joint_pairs, pairs_to_perm
 from .datasets.jpeg import JpegDecoder, JpegEncoder
 from .mixed_batch import MixedBatch, check_det_counts, check_images
 from .tiling import TilePlan, Tiling, plan_pass_groups
+from .video import YuvBatch, YuvFrame, convert_into, resolve
 from .visualize import PoseRenderer
 
 P = _lib.ptr
@@ -238,7 +240,14 @@ class TopDownPoseEstimator(object):
         return fr
 
     def _load(self, fr: _Frame, imgs) -> None:
-        """The images into the frame's static source buffer (host -> device, or a device copy)."""
+        """The images into the frame's static source buffer (host -> device, or a device copy; video frames by one conversion launch in
+        place of the copy: sp_yuv420_to_bgr_u8c3, or the table launch for several frames or host planes)."""
+        if isinstance(imgs, YuvBatch):
+            for i, f in enumerate(imgs.frames):
+                if not f.is_host and f.device != fr.src.device:
+                    raise HipLibraryError(f"image {i}: on {f.device}, the detector on {fr.src.device}")
+            convert_into(imgs.frames, list(fr.src), self._stage.setdefault("yuv", {}), dense=fr.src)
+            return
         if isinstance(imgs, np.ndarray):
             if imgs.dtype != np.uint8:
                 raise TypeError(f"expected a uint8 BGR image, got {imgs.dtype}")
@@ -251,12 +260,21 @@ class TopDownPoseEstimator(object):
 
     @staticmethod
     def _shape_of(imgs, batched: bool):
+        """The image or batch as the frame takes it.  A video.YuvFrame passes as the [H, W, 3] image it stands for (`frame[None]` is its
+        batch of one), same-sized frames as a YuvBatch; they were checked when they were made."""
+        if isinstance(imgs, YuvFrame) and not batched:
+            return imgs
+        if isinstance(imgs, YuvBatch) and batched:
+            return imgs
         if isinstance(imgs, (list, tuple)):
             if not batched:
                 raise ValueError("estimate takes one image [H, W, 3]")
             shapes = {tuple(np.shape(i)) for i in imgs}
             if len(shapes) != 1:
                 raise ValueError("the images of one batch share one size")
+            if all(isinstance(i, YuvFrame) for i in imgs):
+                return YuvBatch(imgs)
+            imgs = resolve(imgs)                     # frames next to BGR images: converted, then stacked with them
             if any(isinstance(i, torch.Tensor) for i in imgs):
                 imgs = torch.stack(list(imgs))
             else:
@@ -429,15 +447,18 @@ class TopDownPoseEstimator(object):
 
     @torch.no_grad()
     def estimate(self, img) -> PoseResult:
-        """One uint8 BGR image [H, W, 3] (numpy or CUDA) -> the persons in it."""
+        """One uint8 BGR image [H, W, 3] (numpy or CUDA), or one video.YuvFrame (NV12 / I420 planes) -> the persons in it."""
         img = self._shape_of(img, batched=False)
         return self._run(img[None], self.use_graph)[0]
 
     # -- differently sized images ---------------------------------------------------------------------------------------------------------
     def _is_mixed(self, imgs) -> bool:
-        """A list whose images differ in size (or any list, with the tests' private switch); an empty list fails in check_images."""
+        """A list whose images differ in size (or any list, with the tests' private switch); an empty list fails in check_images.  A list
+        in which video frames stand next to BGR images goes this way too: its frames become BGR tensors by one table launch."""
         if not isinstance(imgs, (list, tuple)):
             return False
+        if len({isinstance(i, YuvFrame) for i in imgs}) == 2:
+            return True
         return self._force_mixed or len({tuple(np.shape(i)) for i in imgs}) != 1
 
     def _mixed_frame(self, mb: MixedBatch, max_det: int, J: int) -> _Frame:
@@ -499,7 +520,8 @@ class TopDownPoseEstimator(object):
         """A batch of images -> one PoseResult per image, in the caller's order.  Same-sized ([B, H, W, 3], or a list of [H, W, 3]): one
         forward of the detector on B images.  A list of differently sized images (numpy or CUDA): one detector forward per letterboxed net
         shape, every image letterboxed as `estimate` letterboxes it alone.  Either way one pose forward on the `capacity` slots the images
-        share and one device-to-host transfer."""
+        share and one device-to-host transfer.  video.YuvFrames stand where images stand: same-sized frames are converted into the static
+        source by one launch, a list of other sizes (or of frames next to BGR images) has its frames converted by one launch first."""
         if self._is_mixed(imgs):
             return self._run_mixed(imgs)
         return self._run(self._shape_of(imgs, batched=True), False)

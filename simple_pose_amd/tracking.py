@@ -246,7 +246,8 @@ class PoseTracker(object):
 
     @torch.no_grad()
     def update(self, img, timestamp=None) -> PoseResult:
-        """One uint8 BGR image [H, W, 3] (numpy or CUDA), the next frame of the stream -> the persons in it with their `track_id`s.
+        """One uint8 BGR image [H, W, 3] (numpy or CUDA) or one video.YuvFrame, the next frame of the stream -> the persons in it with
+        their `track_id`s.
         A propagated frame (see the module docstring) does not run the detector: new persons appear at the next detector frame.
         `timestamp`: the frame's time in seconds, for a tracker that smooths (default: frame index / `smooth.fps`, the index counted from
         the first frame after construction or reset()).  A time that does not advance is not an error: the filter starts again."""
@@ -451,7 +452,7 @@ class MultiStreamTracker(object):
 
     @torch.no_grad()
     def update(self, frames, timestamps=None):
-        """The next frame of every stream: uint8 BGR [S, H, W, 3] (numpy or CUDA) or a list of S images of one size -> a list of S
+        """The next frame of every stream: uint8 BGR [S, H, W, 3] (numpy or CUDA) or a list of S images (or S video.YuvFrames) of one size -> a list of S
         PoseResult with `track_id` (and `keypoints_smooth`, `image`, `jpeg` as PoseTracker returns them), stream s's in place s.
         `timestamps`: S finite times in seconds, one per stream, for a tracker that smooths (default: each stream's frame index /
         `smooth.fps`).  A propagated call does not run the detector (see the class docstring)."""
