@@ -243,13 +243,7 @@ class YOLOv5Detector(object):
                 hi = min(n, lo + self.TILE_CHUNK)
                 table = tp.group_table(k, lo, hi)
                 engine.set_letterbox_tiles(prog)
-                was = prog.multi_stream
-                if single_stream:
-                    prog.multi_stream = False
-                try:
-                    pred = prog.run(table)
-                finally:
-                    prog.multi_stream = was
+                pred = prog.run_on_stream(table, single_stream)
                 m, N, no = pred.shape
                 ws = _workspace(m, pred.device)
                 a, b = first + lo, first + hi

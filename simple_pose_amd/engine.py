@@ -351,6 +351,17 @@ class Program:
         else:
             raise ValueError(op.kind)
 
+    def run_on_stream(self, x: torch.Tensor, single_stream: bool = True) -> torch.Tensor:
+        """run(x); `single_stream`: every launch on the caller's stream whatever `multi_stream` says, as a stream capture needs it
+        (hipStreamEndCapture of ROCm 7.2 crashed on the forked multi-stream HRNet schedule)."""
+        keep = self.multi_stream
+        if single_stream:
+            self.multi_stream = False
+        try:
+            return self.run(x)
+        finally:
+            self.multi_stream = keep
+
     def run(self, x: torch.Tensor, out: Optional[torch.Tensor] = None, slot: int = 0) -> torch.Tensor:
         """`out`: optional preallocated fp32 [B,J,H/4,W/4] result (a steady-state caller reuses one; default: a fresh tensor per call,
         which the caller may keep - torch's caching allocator makes that a pointer bump, no hipMalloc).
@@ -669,12 +680,7 @@ class GraphedForward:
         self._pool = prog.pool_for(x.shape[0], x.device)
 
     def _body(self):
-        # one stream inside the capture: hipStreamEndCapture of ROCm 7.2 crashed on the forked multi-stream HRNet schedule
-        keep, self.prog.multi_stream = self.prog.multi_stream, False
-        try:
-            hm = self.prog.run(self.static_input)
-        finally:
-            self.prog.multi_stream = keep
+        hm = self.prog.run_on_stream(self.static_input)         # one stream inside the capture
         if self.decoder is None:
             return hm
         kps, mv = self.decoder(hm, self.static_trans_inv)

@@ -80,16 +80,19 @@ class PoseResult:
                 for k, s in zip(self.keypoints, self.score)]
 
 
-def _run_program(prog: engine.Program, x: torch.Tensor, single_stream: bool) -> torch.Tensor:
-    """Program.run; `single_stream`: every launch on the caller's stream, as inside a capture (stream capture crashes on forked
-    schedules: engine.GraphedForward does the same)."""
-    keep = prog.multi_stream
-    if single_stream:
-        prog.multi_stream = False
-    try:
-        return prog.run(x)
-    finally:
-        prog.multi_stream = keep
+def capture_graph(device, warm_up, body) -> torch.cuda.CUDAGraph:
+    """`body()` recorded as one graph.  `warm_up()` runs first, on a side stream outside the capture: the activation pools and workspaces
+    the launches need get allocated there (a capture cannot allocate them), and the device is idle when the capture begins."""
+    side = torch.cuda.Stream(device=device)
+    side.wait_stream(torch.cuda.current_stream(device))
+    with torch.cuda.stream(side):
+        warm_up()
+    torch.cuda.current_stream(device).wait_stream(side)
+    torch.cuda.synchronize(device)
+    graph = torch.cuda.CUDAGraph()
+    with torch.cuda.graph(graph):
+        body()
+    return graph
 
 
 class _Frame:
@@ -332,7 +335,7 @@ class TopDownPoseEstimator(object):
         from .detector.yolov5_detector import _workspace
         g = d.transform.geometry(fr.H, fr.W)
         engine.set_letterbox(det_prog, fr.H, fr.W, g["new_h"], g["new_w"], g["top"], g["left"])
-        pred = _run_program(det_prog, fr.src, single_stream)
+        pred = det_prog.run_on_stream(fr.src, single_stream)
         B, N, no = pred.shape
         ws = _workspace(B, pred.device)
         stream = _lib.current_stream(self.device)
@@ -364,7 +367,7 @@ class TopDownPoseEstimator(object):
         if self.flip_test:
             half = fr.crops[:cap]
             _lib.check(lib.sp_mirror_w(P(half), P(fr.crops[cap:]), cap * ih, iw, 3, stream), "sp_mirror_w")     # dead slots: zeros mirror to zeros
-        hm = _run_program(pose_prog, fr.crops, single_stream)
+        hm = pose_prog.run_on_stream(fr.crops, single_stream)
         if self.flip_test:
             hm = hm[:cap]                            # merged in place; the decode sees the first `capacity` maps only
             _lib.check(lib.sp_heat_map_flip_merge(P(hm), P(hm) + hm.numel() * 4, self._perm, cap, J, oh, ow, int(self.shift_heatmap), P(hm),
@@ -385,24 +388,17 @@ class TopDownPoseEstimator(object):
             self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
                                  fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws)
 
+    def _issue(self, fr: _Frame, det_prog, pose_prog, single_stream: bool) -> None:
+        """The frame's launches: detector, poses, overlay."""
+        self._detect(fr, det_prog, single_stream)
+        self._poses(fr, pose_prog, single_stream)
+        self._render(fr, pose_prog.out_shape[0])
+
     def _capture(self, fr: _Frame, det_prog, pose_prog) -> None:
-        dev = self.device
-        side = torch.cuda.Stream(device=dev)
-        side.wait_stream(torch.cuda.current_stream(dev))
-        with torch.cuda.stream(side):                # warm-up outside the capture: activation pools and workspaces get allocated here
-            self._detect(fr, det_prog, True)
-            self._poses(fr, pose_prog, True)
-            self._render(fr, pose_prog.out_shape[0])
-        torch.cuda.current_stream(dev).wait_stream(side)
-        torch.cuda.synchronize(dev)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph):
-            self._detect(fr, det_prog, True)
-            self._poses(fr, pose_prog, True)
-            self._render(fr, pose_prog.out_shape[0])
-        fr.graph, fr.params = graph, self._params(det_prog, pose_prog)
+        issue = lambda: self._issue(fr, det_prog, pose_prog, True)
+        fr.graph, fr.params = capture_graph(self.device, issue, issue), self._params(det_prog, pose_prog)
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
-        fr.keepalive = (pose_prog, pose_prog.pool_for(self._pose_batch(), dev)) + self._det_keepalive(fr, det_prog)
+        fr.keepalive = (pose_prog, pose_prog.pool_for(self._pose_batch(), self.device)) + self._det_keepalive(fr, det_prog)
 
     def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
         """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
@@ -440,9 +436,7 @@ class TopDownPoseEstimator(object):
                 self._capture(fr, det_prog, pose_prog)
             fr.graph.replay()
         else:
-            self._detect(fr, det_prog)
-            self._poses(fr, pose_prog, False)
-            self._render(fr, pose_prog.out_shape[0])
+            self._issue(fr, det_prog, pose_prog, False)
         return self._results(fr)
 
     @torch.no_grad()
@@ -480,7 +474,7 @@ class TopDownPoseEstimator(object):
             prog = d.program(out_h, out_w)
             engine.set_letterbox_images(prog)
             table = mb.group_table(k)
-            pred = _run_program(prog, table, False)
+            pred = prog.run_on_stream(table, False)
             n, N, no = pred.shape
             ws = _workspace(n, pred.device)
             det = torch.empty((n, fr.max_det, 6), dtype=torch.float32, device=pred.device)

@@ -535,15 +535,25 @@ def test_a_call_without_persons_in_any_stream_is_followed_by_a_detector_call(at_
 
 
 def test_one_stream_equals_the_single_tracker(at_036, est, images):
+    """PoseTracker is the one-stream MultiStreamTracker, so the two sides are one implementation: each of them is also held, frame by
+    frame, to the staged chain under multitrack_ref's rule, which shares no code with either."""
     multi, one = MultiStreamTracker(est, streams=1, detect_every=2), PoseTracker(est, detect_every=2)
+    ref, rule = Staged(est), multitrack_ref.FrameKinds(1, 2)
     kinds = []
     for f, c in enumerate("aabaa"):
+        detect = rule.next()
+        res, ids = ref.update(images[c], detect)
         got, want = multi.update(images[c][None])[0], one.update(images[c])
-        assert multi.last_frame_kind == one.last_frame_kind, f
+        assert multi.last_frame_kind == one.last_frame_kind == rule.name(detect), f
         kinds.append(multi.last_frame_kind)
         _same(got, want, f"frame {f}")
+        assert res is not None, f                                                # (every propagated frame here follows a frame with persons)
+        _same(got, res, f"frame {f} against the staged chain", ids)
+        _same(want, res, f"frame {f}, PoseTracker against the staged chain", ids)
+        rule.done(detect, [len(res)])
     assert kinds == ["detector", "propagated", "detector", "detector", "propagated"]
     _states_match(multi, [one])
+    _states_match_refs(multi, [ref])
 
 
 def test_reset_of_one_stream_restarts_its_ids_and_forces_a_detector_call(at_036, est, images):

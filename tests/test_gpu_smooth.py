@@ -174,4 +174,4 @@ def test_reset_restarts_the_filter_and_the_default_clock(golden, est):
         assert ref.state.events["update"] > 0 and any((o.keypoints_smooth != o.keypoints).any() for o in outs[1:])
         assert int(trk.smooth_state["n"].max()) >= 2
         trk.reset()
-        assert all(int(v.abs().max()) == 0 for v in trk.smooth_state.values()) and trk._frame_index == 0
+        assert all(int(v.abs().max()) == 0 for v in trk.smooth_state.values()) and trk._frame_index == [0]

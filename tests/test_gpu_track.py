@@ -12,7 +12,7 @@ from simple_pose_amd.commons.joint_utils import box_to_center_scale
 from simple_pose_amd.detector.nets.yolov5 import YOLOv5
 from simple_pose_amd.detector.yolov5_detector import YOLOv5Detector
 from simple_pose_amd.pipeline import TopDownPoseEstimator
-from simple_pose_amd.tracking import PoseTracker
+from simple_pose_amd.tracking import OneEuro, PoseTracker
 from tests import track_ref
 from tests.detector_ref import detector_state_dict
 
@@ -391,3 +391,29 @@ def test_graph_replays_equal_eager_frames(golden, est):
     assert 2 <= len(trk._graphs) <= 4 and not eager_trk._graphs                  # one graph per (source shape, frame kind), replayed
     for k in ("id", "age", "miss", "next_id", "kps"):
         assert torch.equal(trk.state[k], eager_trk.state[k]), k
+
+
+def test_state_and_smooth_state_are_unbatched_views_of_the_live_memory(golden, est):
+    """PoseTracker shows its tracks and its smoother's state without the stream axis, and what it shows is the memory the kernels use."""
+    a = golden(G)["sp_a_image"]
+    n, J = 256, 17
+    trk = PoseTracker(est, slots=n, smooth=OneEuro())
+    assert trk.state == {} and trk.smooth_state == {}                            # nothing before the first frame
+    first, _ = trk.update(a), trk.update(a)
+    assert len(first) >= 1
+    shapes = lambda d: {k: (tuple(v.shape), v.dtype) for k, v in d.items()}
+    i32, f32, f64 = torch.int32, torch.float32, torch.float64
+    assert shapes(trk.state) == {"id": ((n,), i32), "age": ((n,), i32), "miss": ((n,), i32), "kps": ((n, J, 3), f64), "area": ((n,), f64),
+                                 "conf": ((n,), f32), "next_id": ((1,), i32)}
+    assert shapes(trk.smooth_state) == {"id": ((n,), i32), "x": ((n, J, 2), f64), "dx": ((n, J, 2), f64), "t": ((n, J), f64),
+                                        "n": ((n, J), i32), "now": ((1,), f64)}
+    assert int(trk.state["next_id"][0]) == len(first) + 1 and int((trk.state["id"] != 0).sum()) == len(first)
+    assert float(trk.smooth_state["now"].item()) == 1 / 30.0                     # the second frame's default time: index 1 / fps
+    trk.reset()
+    for name, d in (("state", trk.state), ("smooth_state", trk.smooth_state)):
+        for k, v in d.items():
+            want = 1 if k == "next_id" else 0
+            assert bool((v == want).all()), (name, k)
+    third = trk.update(a)
+    assert sorted(trk.state["id"][trk.state["id"] != 0].tolist()) == third.track_id.tolist() == list(range(1, len(first) + 1))
+    assert int(trk.state["next_id"][0]) == len(first) + 1

@@ -178,3 +178,51 @@ def test_frame_kind_rule_with_several_streams():
     assert seq == ["detector", "propagated", "propagated", "detector", "propagated", "detector", "propagated"]
     k.reset(stream=1)
     assert k.next()
+
+
+@pytest.mark.parametrize("detect_every", [1, 2, 3, 5])
+def test_the_trackers_own_frame_kind_methods_with_one_stream(detect_every):
+    """The rule as the trackers run it (MultiStreamTracker._next_is_detector / _ran, host counters only), for a one-stream
+    MultiStreamTracker and a PoseTracker, against both restatements; the resets and person counts of the test above."""
+    from simple_pose_amd.tracking import MultiStreamTracker, PoseTracker
+    rng = np.random.default_rng(detect_every)
+    est = _estimator()
+    multi, single = MultiStreamTracker(est, streams=1, detect_every=detect_every), PoseTracker(est, detect_every=detect_every)
+    ref_multi, ref_single = multitrack_ref.FrameKinds(1, detect_every), multitrack_ref.SingleKinds(detect_every)
+    kinds = []
+    for call in range(400):
+        if rng.random() < 0.03:
+            stream = None if rng.random() < 0.5 else 0
+            multi.reset(stream)
+            ref_multi.reset(stream)
+            single.reset()
+            ref_single.reset()
+        want = ref_multi.next()
+        assert ref_single.next() == want, call
+        assert multi._next_is_detector() is want and single._next_is_detector() is want, call
+        n = int(rng.integers(0, 4)) * int(rng.random() < 0.8)                    # person counts, a fifth of them zero
+        multi._ran(want, [n])
+        single._ran(want, [n])
+        ref_multi.done(want, [n])
+        ref_single.done(want, n)
+        assert multi.last_frame_kind == single.last_frame_kind == multitrack_ref.FrameKinds.name(want), call
+        kinds.append(want)
+    assert kinds[0] and (False in kinds) == (detect_every > 1)
+    assert not multi.state and not multi.smooth_state and not single.state and not single.smooth_state     # nothing was allocated
+
+
+def test_the_trackers_own_frame_kind_methods_with_three_streams():
+    from simple_pose_amd.tracking import MultiStreamTracker
+    trk, k = MultiStreamTracker(_estimator(), streams=3, detect_every=3), multitrack_ref.FrameKinds(3, 3)
+    seq = []
+    for counts in ([2, 0, 2], [2, 0, 2], [0, 1, 0], [2, 2, 2], [0, 0, 0], [1, 1, 1], [1, 1, 1]):
+        d = k.next()
+        assert trk._next_is_detector() is d
+        trk._ran(d, counts)
+        k.done(d, counts)
+        seq.append(trk.last_frame_kind)
+    assert seq == ["detector", "propagated", "propagated", "detector", "propagated", "detector", "propagated"]
+    assert not k.next() and not trk._next_is_detector()                          # (two of three calls since the detector: propagated, but for ...)
+    trk.reset(stream=1)
+    k.reset(stream=1)
+    assert k.next() and trk._next_is_detector() is True and not trk.state
