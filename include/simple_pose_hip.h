@@ -994,6 +994,77 @@ int sp_render_poses_u8c3(const unsigned char* src, unsigned char* dst, int h, in
                          const int32_t* track_id /* may be NULL */, const int32_t* keep, const int32_t* keep_count, const int32_t* seg,
                          int image, int rows, int joints, const sp_render_style* style_host, void* workspace, void* stream);
 
+/* ---- overlay text: one label per kept person (track id, scores) and one caption per image, formatted and rasterised on the device ------------
+ * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] IN PLACE, 1 <= h, w <= 16384, behind sp_render_poses_u8c3 on the same
+ * stream; it reads the same rows (kept count n and pick order as above) plus score fp64 [rows].  The rules (simple_pose_amd/csrc/sp_label.h
+ * states them once for the device and the host; all integer but the two conversions marked (*)):
+ *   font         sp_font.h: 5 x 7 pixels per glyph, the 95 printable ASCII characters 0x20 .. 0x7E; a glyph is 7 bytes, one per row from the
+ *                top, bit 4 the leftmost column.  A character cell is 6 x 8 font pixels (an empty column right, an empty row below).
+ *   template     up to 32 bytes: printable ASCII is literal, bytes 0x01 .. 0x05 are fields, anything else is refused.
+ *                  0x01 {id}     label    track_id[row] in decimal when track_id is given and the id is > 0, else pick position + 1
+ *                  0x02 {score}  label    score[row] (double)
+ *                  0x03 {conf}   label    box[row][4] (float, widened to double)
+ *                  0x04 {n}      caption  the image's kept count n
+ *                  0x05 {image}  caption  the image index
+ *                A label template holds label fields only (a caption field in it is refused).  The caption's text is DEVICE memory, row
+ *                `image` of caption uint8 [images][64], ending at the first NUL or at byte 64: a printable byte is literal, 0x04 / 0x05
+ *                are its fields, any other byte (a label field too) prints '?'.
+ *   numbers      {score}, {conf}: a value that is not finite or is < 0 prints "?"; otherwise c = (int64) rint(min(v, 99.99) * 100.0) (*: one
+ *                double product, ties to even) and the text is c / 100 in decimal, '.', c % 100 as two digits.
+ *   truncation   formatted text longer than 24 characters (label) or 64 (caption) is cut there.  Empty text draws nothing.
+ *   plate        text of L characters at scale s (1 .. 8): (6L + 1) * s wide, 9 * s high, its corner at (x0, y0).  Font pixel (col, row) of
+ *                character i covers the s x s image pixels from (x0 + (1 + 6i + col) * s, y0 + (1 + row) * s).
+ *   label at     bx = q(x1) >> 4, by = q(y1) >> 4 of the box's first corner (q as above (*), arithmetic shift; a coordinate q rejects draws
+ *                no label).  y0 = by - 9s; if y0 < 0: y0 = by (inside the box).  x0 = bx; if x0 + width > w: x0 = w - width; if x0 < 0:
+ *                x0 = 0.  Then the plate is clipped to the image.
+ *   caption at   a corner, s pixels from both edges: x0 = s (left) or w - s - width (right), y0 = s (top) or h - s - height (bottom); then
+ *                clipped to the image.
+ *   colours      label plate: the person colour of SP_RENDER_COLOUR_PERSON (whatever the overlay's colour_by); its text black when
+ *                29 * B + 150 * G + 77 * R >= 32768, white otherwise.  Caption: black plate, white text.
+ *   blend        a = 16 * opacity (sixteenths, 0 .. 16); per channel out = (in * (256 - a) + c * a + 128) >> 8 with c the text colour
+ *                where a glyph bit is set and the plate colour elsewhere on the plate.  One blend per label per pixel; a later label
+ *                blends on the earlier result.
+ *   order        record p < rows is person slot p = the pose at pick position n - 1 - p (empty for p >= n), applied in ascending order:
+ *                the best pose's label lies on top.  The caption is the last record.  All of it after all capsules. */
+#define SP_LABEL_MAX_TEMPLATE 32
+#define SP_LABEL_MAX_CHARS 24
+#define SP_LABEL_CAPTION_BYTES 64
+#define SP_LABEL_MAX_SCALE 8
+#define SP_LABEL_FIELD_ID 1
+#define SP_LABEL_FIELD_SCORE 2
+#define SP_LABEL_FIELD_CONF 3
+#define SP_LABEL_FIELD_N 4
+#define SP_LABEL_FIELD_IMAGE 5
+#define SP_LABEL_CORNER_TL 0
+#define SP_LABEL_CORNER_TR 1
+#define SP_LABEL_CORNER_BL 2
+#define SP_LABEL_CORNER_BR 3
+typedef struct sp_label_style {
+    int32_t template_len;                               /* 0 .. 32; 0: no labels */
+    unsigned char label_template[SP_LABEL_MAX_TEMPLATE];
+    int32_t label_scale, label_opacity;                 /* 1 .. 8; sixteenths, 0 .. 16 */
+    int32_t caption_scale, caption_opacity;
+    int32_t caption_corner;                             /* SP_LABEL_CORNER_* */
+    int32_t palette_n;                                  /* 1 .. 32 */
+    unsigned char palette[SP_RENDER_MAX_PALETTE][3];    /* BGR: the overlay's */
+} sp_label_style;
+/* HOST function: the 7 row bytes of character ch (0x20 .. 0x7E); -1 with sp_last_error() for any other ch or a null pointer */
+int sp_render_font_glyph(int ch, unsigned char rows7[7]);
+/* bytes of the record array for `rows` person slots (0 .. 2048) and the caption */
+int sp_render_labels_workspace_bytes(int rows, int64_t* bytes);
+/* Two launches (label_format_kernel: one thread per person slot and one for the caption formats the text and writes a record - clipped and
+ * unclipped rectangle, two colours, alpha, scale, length, characters; no compaction.  label_tile_kernel: one 256-thread workgroup per
+ * 64 x 16 pixel tile scans the records in chunks of 256, lists in index order those whose plate meets the tile and applies them to pixels
+ * held in registers, the font in LDS; a tile nothing touches is neither read nor written).  No copy, no synchronisation, capturable.
+ * 4-byte accesses when w % 4 == 0 and img is 4-byte aligned, bytes otherwise.  template_len == 0 draws no labels, caption_dev == NULL no
+ * caption; neither, or rows == 0 without a caption, is a no-op.  style_host is HOST memory, validated (scales, opacities, corner,
+ * palette_n, every template byte) and copied into the kernel arguments.  workspace: sp_render_labels_workspace_bytes, 4-byte aligned
+ * device memory, overwritten by every call.  Every pointer but track_id and caption_dev is required (a null one is refused). */
+int sp_render_labels_u8c3(unsigned char* img, int h, int w, const float* box, const double* score,
+                          const int32_t* track_id /* may be NULL */, const int32_t* keep, const int32_t* keep_count, const int32_t* seg,
+                          int image, int rows, const sp_label_style* style_host, const unsigned char* caption_dev /* may be NULL */,
+                          void* workspace, void* stream);
+
 /* ---- baseline JPEG decoding: file bytes in, uint8 BGR [H,W,3] images out ---------------------------------------------------------------------
  * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
  * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF

@@ -115,6 +115,18 @@ class ImageRef(ctypes.Structure):
 SP_RENDER_COLOUR_PERSON, SP_RENDER_COLOUR_PART = 0, 1
 SP_RENDER_MAX_EDGES, SP_RENDER_MAX_PALETTE, SP_RENDER_MAX_RADIUS = 64, 32, 1024
 
+
+class LabelStyle(ctypes.Structure):
+    """Mirror of `sp_label_style` (field order is ABI): host memory, copied into the kernel arguments by sp_render_labels_u8c3."""
+    _fields_ = [("template_len", c_int32), ("label_template", ctypes.c_uint8 * 32), ("label_scale", c_int32), ("label_opacity", c_int32),
+                ("caption_scale", c_int32), ("caption_opacity", c_int32), ("caption_corner", c_int32), ("palette_n", c_int32),
+                ("palette", (ctypes.c_uint8 * 3) * 32)]
+
+
+SP_LABEL_MAX_TEMPLATE, SP_LABEL_MAX_CHARS, SP_LABEL_CAPTION_BYTES, SP_LABEL_MAX_SCALE = 32, 24, 64, 8
+SP_LABEL_FIELDS = {"id": 1, "score": 2, "conf": 3, "n": 4, "image": 5}        # field name -> template byte; {n}, {image}: captions only
+SP_LABEL_CORNERS = {"tl": 0, "tr": 1, "bl": 2, "br": 3}
+
 class TileRef(ctypes.Structure):
     """Mirror of `sp_tile_ref` (field order is ABI): one pass of tiled detection, a rectangle of a frame in device memory."""
     _fields_ = [("data", ctypes.c_uint64), ("h", c_int32), ("w", c_int32), ("pitch", c_int32), ("new_h", c_int32), ("new_w", c_int32),
@@ -301,6 +313,9 @@ SYMBOLS = {
     "sp_jpeg_encode_batch": (c_int, [_P, _P, c_int, _P, c_int64, _P, c_int64, _P, _P, c_int, _P]),
     "sp_render_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
     "sp_render_poses_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RenderStyle), _P, _P]),
+    "sp_render_font_glyph": (c_int, [c_int, _P]),
+    "sp_render_labels_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_int64)]),
+    "sp_render_labels_u8c3": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(LabelStyle), _P, _P, _P]),
     "sp_yuv420_to_bgr_u8c3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "sp_bgr_to_yuv420_u8c3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P]),
     "sp_yuv420_to_bgr_images_u8c3": (c_int, [_P, c_int, c_int, c_int, _P]),

@@ -20,6 +20,8 @@ With `flip_test=True` the crops are mirrored into a second half of the crop buff
 on the same stream, still one graph.
 With `renderer=PoseRenderer(...)` (visualize.py) the kept poses are drawn into a copy of the source image, `PoseResult.image`, by two more
 launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched.
+A renderer with a `label` or a `caption` adds two more (sp_render_labels_u8c3: ids, scores and the kept count formatted on the device); the
+caption's bytes are staged into the frame ahead of the launches or the replay (_stage_caption), so a captured frame shows a new caption.
 With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer, the source - is encoded to a baseline JPEG file
 after the frame on the same stream (sp_jpeg_encode_batch, outside the graph: it uploads its descriptors), and `PoseResult.jpeg` holds the
 file's bytes; without one nothing is allocated or launched.
@@ -131,6 +133,9 @@ class _Frame:
         self.tiles = None                # tiling.TilePlan: built with the first tiled detector frame of this shape
         self.canvas = None               # [B, H, W, 3] and the primitive array: allocated with the first frame of an estimator that has a renderer
         self.render_ws = None
+        self.label_ws = None             # the record array, the captions [B, 64] and their pinned twin: allocated with the first frame of an
+        self.caption = None              # estimator whose renderer draws text
+        self.caption_host = None
 
     def fetch(self) -> Dict[str, np.ndarray]:
         """The call's one device-to-host transfer (and its one synchronisation)."""
@@ -240,7 +245,21 @@ class TopDownPoseEstimator(object):
         if self.renderer is not None and fr.canvas is None:
             fr.canvas = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=self.device)
             fr.render_ws = PoseRenderer.workspace(self.capacity, J, self.device)
+        if self.renderer is not None and self.renderer.has_text and fr.label_ws is None:
+            fr.label_ws = PoseRenderer.label_workspace(self.capacity, self.device)
+            fr.caption = torch.zeros((B, _lib.SP_LABEL_CAPTION_BYTES), dtype=torch.uint8, device=self.device)
+            fr.caption_host = torch.zeros((B, _lib.SP_LABEL_CAPTION_BYTES), dtype=torch.uint8).pin_memory()
         return fr
+
+    def _stage_caption(self, fr: _Frame) -> None:
+        """`renderer.caption` as it reads now into the frame's caption buffer: through the pinned twin, by a copy on the frame's stream
+        ahead of the launches or the replay that read it, never inside a capture (as a tracker stages its times) - so a captured frame
+        shows a reassigned caption with its next replay.  A list of another length than the frame has images: ValueError, before any
+        launch.  Nothing without a caption."""
+        if self.renderer is None or self.renderer.caption is None:
+            return
+        fr.caption_host.copy_(torch.from_numpy(self.renderer.caption_rows(fr.B)))
+        fr.caption.copy_(fr.caption_host, non_blocking=True)
 
     def _load(self, fr: _Frame, imgs) -> None:
         """The images into the frame's static source buffer (host -> device, or a device copy; video frames by one conversion launch in
@@ -381,12 +400,14 @@ class TopDownPoseEstimator(object):
     def _render(self, fr: _Frame, J: int, tracked: bool = False, kps: torch.Tensor = None) -> None:
         """The overlay of every image's kept poses into the frame's canvas: one sp_render_poses_u8c3 (two launches) per image index, reading
         the buffers sp_oks_nms (and, `tracked`, sp_track_associate) just wrote; `kps`: the poses to draw instead of the frame's own (a
-        smoothing tracker's kps_smooth).  Nothing without a renderer."""
+        smoothing tracker's kps_smooth).  A renderer with text then labels the canvas (sp_render_labels_u8c3, two more launches) from the
+        frame's scores, ids and staged captions (_stage_caption, which the caller ran outside any capture).  Nothing without a renderer."""
         if self.renderer is None:
             return
         for b in range(fr.B):
             self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
-                                 fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws)
+                                 fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws, score=fr.score, caption=fr.caption,
+                                 label_workspace=fr.label_ws)
 
     def _issue(self, fr: _Frame, det_prog, pose_prog, single_stream: bool) -> None:
         """The frame's launches: detector, poses, overlay."""
@@ -430,6 +451,7 @@ class TopDownPoseEstimator(object):
         det_prog = self._det_program(B, H, W)
         pose_prog = self._pose_program()
         fr = self._frame(B, H, W, self.MAX_DET, pose_prog.out_shape[0])
+        self._stage_caption(fr)
         self._load(fr, imgs)
         if graph:
             if fr.graph is None or fr.params != self._params(det_prog, pose_prog):
@@ -499,6 +521,7 @@ class TopDownPoseEstimator(object):
         pose_prog = self._pose_program()
         mb = MixedBatch(imgs, self.detector.transform, self.device, self._stage)
         fr = self._mixed_frame(mb, M, pose_prog.out_shape[0])
+        self._stage_caption(fr)
         if det is None:
             self._detect_mixed(fr, mb)
         else:
@@ -555,6 +578,7 @@ class TopDownPoseEstimator(object):
         M = det.shape[1]
         pose_prog = self._pose_program()
         fr = self._frame(B, H, W, M, pose_prog.out_shape[0])
+        self._stage_caption(fr)
         self._load(fr, imgs)
         fr.det.copy_(det)
         fr.counts.copy_(cnt)

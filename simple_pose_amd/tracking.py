@@ -338,6 +338,7 @@ class MultiStreamTracker(object):
         J = pose_prog.out_shape[0]
         self._ensure_state(J)
         fr = est._frame(S, H, W, est.MAX_DET, J, smooth=self.smooth is not None)
+        est._stage_caption(fr)                       # (nothing without a caption) ahead of the launch or replay that reads it, as the times below
         est._load(fr, imgs)
         if self.smooth is not None:                  # the S times, on the frame's stream ahead of the launch or replay that reads them
             for s in range(S):

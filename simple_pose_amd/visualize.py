@@ -1,7 +1,8 @@
 """Poses drawn into frames on the device: skeleton limbs, joints and boxes, coloured by person (track id) or by part.
 
     r = PoseRenderer(skeleton=COCO_SKELETON, joint_radius=3.0, limb_width=2.0, box_width=1.0, opacity=1.0, in_vis_thre=0.2,
-                     colour_by="person", palette=None)
+                     colour_by="person", palette=None, label=None, label_scale=2, label_opacity=1.0,
+                     caption=None, caption_scale=2, caption_corner="tl", caption_opacity=0.75)
     out = r.render(img, result)                                   # uint8 BGR [H,W,3] (numpy or CUDA) + a PoseResult -> CUDA uint8 [H,W,3]
     est = TopDownPoseEstimator(detector, pose_model, renderer=r)  # in the frame: PoseResult.image, drawn inside the frame's own graph
 
@@ -9,7 +10,15 @@ The rasteriser is sp_render_poses_u8c3 (csrc/render.hip, the pixel rules in csrc
 primitive is a capsule in 1/16 px, covered pixels are blended by 16 samples each, persons are painted in reverse pick order so that the
 best pose lies on top.  Inside an estimator or a tracker the two launches follow sp_oks_nms / sp_track_associate on the same stream and
 read the frame's buffers directly; the person count never reaches the host.  `render` is the same kernels on the rows of a PoseResult that
-is already on the host.  There is no CPU fallback and no text."""
+is already on the host.  There is no CPU fallback.
+
+Text is sp_render_labels_u8c3 (csrc/labels.hip, the rules in csrc/sp_label.h, the 5 x 7 font in csrc/sp_font.h), two more launches behind
+the overlay's, in place on the canvas.  `label="#{id} {score}"` puts a plate in the person's colour at the first corner of every kept
+person's box: `{id}` is the track id (the pick position + 1 without a tracker), `{score}` the pose score, `{conf}` the detector's
+confidence, formatted on the device from the frame's buffers.  `caption="cam 3: {n} persons"` (one string, or one per image) puts a black
+plate into a corner of the frame: `{n}` is the image's kept count, `{image}` its index.  `{{` and `}}` are literal braces.  The caption
+can be reassigned at any time (`renderer.caption = ...`): an estimator stages its bytes through a pinned buffer ahead of the launches or
+the replay, so a captured frame shows the new text without being captured again.  The font is ASCII only."""
 from __future__ import annotations
 
 import ctypes
@@ -31,6 +40,44 @@ DEFAULT_PALETTE = ((56, 56, 255), (31, 112, 255), (29, 178, 255), (49, 210, 207)
 MAX_RADIUS_PX = _lib.SP_RENDER_MAX_RADIUS / 16.0
 
 
+LABEL_FIELDS = ("id", "score", "conf")       # what a label may hold; a caption holds the other two
+CAPTION_FIELDS = ("n", "image")
+
+
+def parse_template(text, fields, limit: int, what: str) -> bytes:
+    """"#{id} {score}" -> the bytes sp_render_labels_u8c3 takes: printable ASCII stays, `{name}` becomes the field's byte (0x01 .. 0x05),
+    `{{` and `}}` are literal braces.  ValueError for a field that is not in `fields`, a lone brace, a character outside printable ASCII or
+    more than `limit` bytes."""
+    if not isinstance(text, str):
+        raise ValueError(f"{what}: expected a string, got {type(text).__name__}")
+    out, i = bytearray(), 0
+    while i < len(text):
+        c = text[i]
+        if c in "{}" and text[i:i + 2] == c + c:
+            out.append(ord(c))
+            i += 2
+        elif c == "{":
+            j = text.find("}", i)
+            name = text[i + 1:j] if j > 0 else None
+            if name is None or name not in _lib.SP_LABEL_FIELDS:
+                raise ValueError(f"{what}: unknown field {text[i:j + 1] if j > 0 else text[i:]!r} in {text!r} (fields: "
+                                 f"{', '.join('{' + f + '}' for f in fields)}; a literal brace is doubled)")
+            if name not in fields:
+                raise ValueError(f"{what}: {{{name}}} is not a field of this text (fields: {', '.join('{' + f + '}' for f in fields)})")
+            out.append(_lib.SP_LABEL_FIELDS[name])
+            i = j + 1
+        elif c == "}":
+            raise ValueError(f"{what}: a lone '}}' in {text!r} (a literal brace is doubled)")
+        elif not (0x20 <= ord(c) <= 0x7E):
+            raise ValueError(f"{what}: {c!r} in {text!r} is not printable ASCII (the built-in font has nothing else)")
+        else:
+            out.append(ord(c))
+            i += 1
+    if len(out) > limit:
+        raise ValueError(f"{what}: {len(out)} bytes, at most {limit} (a field counts as one)")
+    return bytes(out)
+
+
 def _number(name, v, lo, hi, what):
     if not isinstance(v, (int, float)) or isinstance(v, bool) or not (lo <= float(v) <= hi):
         raise ValueError(f"{name}: {what}, got {v!r}")
@@ -42,10 +89,17 @@ class PoseRenderer(object):
     (radius 0 .. 64, widths 0 .. 128), quantised to 1/16 px (a limb or box edge is a capsule of half the width); `box_width=0` draws no
     boxes.  `opacity`: 0 .. 1, quantised to 1/16.  `in_vis_thre`: a joint is drawn when its max_val exceeds it, a limb when both ends do.
     `colour_by`: "person" (the track id's palette entry, the pick position's without ids) or "part" (one entry per limb / joint; boxes keep
-    the person's).  `palette`: up to 32 BGR triples (default: 20 colours)."""
+    the person's).  `palette`: up to 32 BGR triples (default: 20 colours).
+
+    `label`: None (no labels) or a template of at most 32 bytes, printable ASCII with the fields {id}, {score}, {conf} (a field is one
+    byte; `{{` / `}}` are literal braces); the formatted text is cut at 24 characters.  `label_scale`, `caption_scale`: 1 .. 8 image pixels
+    per font pixel.  `label_opacity`, `caption_opacity`: 0 .. 1, quantised to 1/16.  `caption`: None, a string or a list with one string
+    per image, each at most 64 bytes with the fields {n} and {image}; `caption_corner`: "tl", "tr", "bl" or "br".  With `label` and
+    `caption` both None nothing is allocated or launched for text."""
 
     def __init__(self, skeleton=COCO_SKELETON, joint_radius: float = 3.0, limb_width: float = 2.0, box_width: float = 1.0, opacity: float = 1.0,
-                 in_vis_thre: float = 0.2, colour_by: str = "person", palette=None):
+                 in_vis_thre: float = 0.2, colour_by: str = "person", palette=None, label=None, label_scale: int = 2,
+                 label_opacity: float = 1.0, caption=None, caption_scale: int = 2, caption_corner: str = "tl", caption_opacity: float = 0.75):
         try:
             sk = [(int(a), int(b)) for a, b in skeleton]
             ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for e in skeleton for v in e)
@@ -81,10 +135,71 @@ class PoseRenderer(object):
         for i, c in enumerate(self.palette.tolist()):
             st.palette[i][0], st.palette[i][1], st.palette[i][2] = c
         self._style = st
+        # ---- text
+        self.label = None if label is None else parse_template(label, LABEL_FIELDS, _lib.SP_LABEL_MAX_TEMPLATE, "label")
+        for name, v in (("label_scale", label_scale), ("caption_scale", caption_scale)):
+            if not isinstance(v, (int, np.integer)) or isinstance(v, bool) or not (1 <= v <= _lib.SP_LABEL_MAX_SCALE):
+                raise ValueError(f"{name}: an integer in 1..{_lib.SP_LABEL_MAX_SCALE} (image pixels per font pixel), got {v!r}")
+        lo = _number("label_opacity", label_opacity, 0.0, 1.0, "a value in 0..1")
+        co = _number("caption_opacity", caption_opacity, 0.0, 1.0, "a value in 0..1")
+        if caption_corner not in _lib.SP_LABEL_CORNERS:
+            raise ValueError(f"caption_corner: 'tl', 'tr', 'bl' or 'br', got {caption_corner!r}")
+        self.label_scale, self.caption_scale, self.caption_corner = int(label_scale), int(caption_scale), caption_corner
+        self.label_opacity16, self.caption_opacity16 = int(round(lo * 16)), int(round(co * 16))
+        self.caption = caption
+        ls = _lib.LabelStyle()
+        ls.template_len = len(self.label or b"")
+        for i, c in enumerate(self.label or b""):
+            ls.label_template[i] = c
+        ls.label_scale, ls.label_opacity = self.label_scale, self.label_opacity16
+        ls.caption_scale, ls.caption_opacity = self.caption_scale, self.caption_opacity16
+        ls.caption_corner = _lib.SP_LABEL_CORNERS[caption_corner]
+        ls.palette_n = st.palette_n
+        for i, c in enumerate(self.palette.tolist()):
+            ls.palette[i][0], ls.palette[i][1], ls.palette[i][2] = c
+        self._label_style = ls
+
+    @property
+    def caption(self):
+        """None, a string, or a list with one string per image; assign at any time (the text is checked at once)."""
+        return self._caption
+
+    @caption.setter
+    def caption(self, value) -> None:
+        if value is None:
+            self._caption, self._caption_bytes = None, None
+            return
+        texts = list(value) if isinstance(value, (list, tuple)) else [value]
+        if len(texts) == 0:
+            raise ValueError("caption: a string, or a list with one string per image; got an empty list")
+        parsed = [parse_template(t, CAPTION_FIELDS, _lib.SP_LABEL_CAPTION_BYTES, "caption") for t in texts]
+        self._caption = list(value) if isinstance(value, (list, tuple)) else value
+        self._caption_bytes = parsed if isinstance(value, (list, tuple)) else parsed[0]
+
+    @property
+    def has_text(self) -> bool:
+        return self.label is not None or self._caption is not None
+
+    def caption_rows(self, images: int) -> np.ndarray:
+        """The captions of `images` images as sp_render_labels_u8c3 reads them: uint8 [images, 64], NUL padded.  A list of another
+        length: ValueError."""
+        cb = self._caption_bytes
+        if cb is None:
+            raise ValueError("caption: this renderer has none")
+        if isinstance(cb, list) and len(cb) != images:
+            raise ValueError(f"caption: a list of {len(cb)} strings for {images} image{'s' if images != 1 else ''} (one per image)")
+        out = np.zeros((images, _lib.SP_LABEL_CAPTION_BYTES), np.uint8)
+        for b in range(images):
+            t = cb[b] if isinstance(cb, list) else cb
+            out[b, :len(t)] = list(t)
+        return out
 
     def key(self) -> tuple:
-        """Everything the launches depend on: two renderers with equal keys draw the same pixels (a captured graph is reused only then)."""
-        return (self.skeleton, self.joint_r, self.limb_r, self.box_r, self.opacity16, self.in_vis_thre, self.colour_by, self.palette.tobytes())
+        """Everything the launches depend on: two renderers with equal keys draw the same pixels (a captured graph is reused only then) -
+        but for the caption's text, which the launches read from device memory: only whether there is one is part of the key."""
+        return (self.skeleton, self.joint_r, self.limb_r, self.box_r, self.opacity16, self.in_vis_thre, self.colour_by, self.palette.tobytes(),
+                self.label, self.label_scale, self.label_opacity16, self._caption is not None, self.caption_scale, self.caption_corner,
+                self.caption_opacity16)
 
     @staticmethod
     def workspace(rows: int, joints: int, device) -> torch.Tensor:
@@ -93,18 +208,47 @@ class PoseRenderer(object):
         _lib.check(_lib.lib().sp_render_workspace_bytes(rows, joints, _lib.SP_RENDER_MAX_EDGES, ctypes.byref(n)), "sp_render_workspace_bytes")
         return torch.zeros((max(int(n.value), 8),), dtype=torch.uint8, device=device)
 
-    def launch(self, src, dst, kps, box, track_id, keep, keep_count, seg, image: int, rows: int, joints: int, workspace) -> None:
-        """sp_render_poses_u8c3 on the current stream of src's device; every argument a CUDA tensor (track_id may be None)."""
+    @staticmethod
+    def label_workspace(rows: int, device) -> torch.Tensor:
+        """The record array of `rows` person slots and the caption."""
+        n = ctypes.c_int64()
+        _lib.check(_lib.lib().sp_render_labels_workspace_bytes(rows, ctypes.byref(n)), "sp_render_labels_workspace_bytes")
+        return torch.zeros((int(n.value),), dtype=torch.uint8, device=device)
+
+    def launch(self, src, dst, kps, box, track_id, keep, keep_count, seg, image: int, rows: int, joints: int, workspace, score=None,
+               caption=None, label_workspace=None) -> None:
+        """sp_render_poses_u8c3 on the current stream of src's device; every argument a CUDA tensor (track_id may be None).  A renderer with
+        text then issues sp_render_labels_u8c3 on `dst`: `score` fp64 [rows] (needed with a `label`), `caption` uint8 [images, 64] on the
+        device (needed with a caption: `caption_rows` uploaded by the caller), `label_workspace` from `label_workspace(rows, device)`."""
         h, w = int(src.shape[0]), int(src.shape[1])
         _lib.check(_lib.lib().sp_render_poses_u8c3(P(src), P(dst), h, w, P(kps), P(box), P(track_id), P(keep), P(keep_count), P(seg), image, rows,
                                                    joints, ctypes.byref(self._style), P(workspace), _lib.current_stream(src.device)),
                    "sp_render_poses_u8c3")
+        if self.has_text:
+            self.launch_labels(dst, box, score, track_id, keep, keep_count, seg, image, rows, caption, label_workspace)
+
+    def launch_labels(self, img, box, score, track_id, keep, keep_count, seg, image: int, rows: int, caption, label_workspace) -> None:
+        """sp_render_labels_u8c3 on `img` in place, on the current stream of its device."""
+        if self.label is not None and rows > 0 and score is None:
+            raise ValueError("launch: this renderer has a label, which needs score= (fp64 [rows] on the device)")
+        if self._caption is not None and caption is None:
+            raise ValueError("launch: this renderer has a caption, which needs caption= (caption_rows(images) on the device)")
+        if label_workspace is None:
+            raise ValueError("launch: this renderer draws text, which needs label_workspace= (PoseRenderer.label_workspace(rows, device))")
+        h, w = int(img.shape[0]), int(img.shape[1])
+        _lib.check(_lib.lib().sp_render_labels_u8c3(P(img), h, w, P(box), P(score), P(track_id), P(keep), P(keep_count), P(seg), image, rows,
+                                                    ctypes.byref(self._label_style), P(caption) if self._caption is not None else None,
+                                                    P(label_workspace), _lib.current_stream(img.device)), "sp_render_labels_u8c3")
 
     @torch.no_grad()
-    def render(self, img, result, out=None) -> torch.Tensor:
+    def render(self, img, result, out=None, image: int = 0) -> torch.Tensor:
         """`img`: uint8 BGR [H, W, 3], numpy or CUDA; `result`: a PoseResult (its track_id colours the persons when present).  Returns a
         CUDA uint8 [H, W, 3]: `out` when given (contiguous; it may be `img` itself when that is a contiguous CUDA tensor, drawn in
-        place), a new tensor otherwise.  A non-contiguous `img` is copied first, so it cannot also be `out`."""
+        place), a new tensor otherwise.  A non-contiguous `img` is copied first, so it cannot also be `out`.  Labels take `result.score`
+        and `result.track_id`; `image`: the index {image} prints and, with a list of captions, the one that is drawn."""
+        if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
+            raise ValueError(f"image: an image index in 0..4095, got {image!r}")
+        image = int(image)
         if isinstance(img, np.ndarray):
             if img.dtype != np.uint8:
                 raise TypeError(f"expected a uint8 BGR image, got {img.dtype}")
@@ -126,21 +270,37 @@ class PoseRenderer(object):
         kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
         n = int(kps.shape[0])
         J = int(kps.shape[1]) if kps.ndim == 3 else 0
+        dev = img.device
+        up = lambda a: torch.from_numpy(a).to(dev)
+        cap = None
+        if self._caption is not None:
+            cb = self._caption_bytes
+            if isinstance(cb, list) and image >= len(cb):
+                raise ValueError(f"caption: a list of {len(cb)} strings has none for image {image}")
+            cap = up(self.caption_rows(len(cb) if isinstance(cb, list) else image + 1))
+        # the frame's bookkeeping for one image at index `image`: its keep list is rows 0 .. n
+        counts, segs = np.zeros(image + 1, np.int32), np.zeros(image + 2, np.int32)
+        counts[image], segs[image + 1:] = n, n
         if n == 0:
             if out.data_ptr() != img.data_ptr():
                 out.copy_(img)
+            if cap is not None:
+                with torch.cuda.device(dev):
+                    self.launch_labels(out, None, None, None, None, up(counts), up(segs), image, 0, cap, self.label_workspace(0, dev))
             return out
         if kps.ndim != 3 or kps.shape[2] != 3 or not (1 <= J <= 64):
             raise ValueError(f"result.keypoints: expected [n, J <= 64, 3], got {tuple(kps.shape)}")
         box = np.ascontiguousarray(result.box, dtype=np.float32)
         if box.shape != (n, 5):
             raise ValueError(f"result.box: expected [{n}, 5], got {tuple(box.shape)}")
-        dev = img.device
-        up = lambda a: torch.from_numpy(a).to(dev)
         tid = None if result.track_id is None else up(np.ascontiguousarray(result.track_id, dtype=np.int32).reshape(n))
         d_kps, d_box = up(kps), up(box)
-        keep, keep_count, seg = up(np.arange(n, dtype=np.int32)), up(np.array([n], np.int32)), up(np.array([0, n], np.int32))
+        keep, keep_count, seg = up(np.arange(n, dtype=np.int32)), up(counts), up(segs)
         ws = self.workspace(n, J, dev)
+        score = lws = None
+        if self.has_text:
+            score = up(np.ascontiguousarray(result.score, dtype=np.float64).reshape(n))
+            lws = self.label_workspace(n, dev)
         with torch.cuda.device(dev):
-            self.launch(img, out, d_kps, d_box, tid, keep, keep_count, seg, 0, n, J, ws)
+            self.launch(img, out, d_kps, d_box, tid, keep, keep_count, seg, image, n, J, ws, score=score, caption=cap, label_workspace=lws)
         return out
