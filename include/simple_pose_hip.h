@@ -1065,6 +1065,69 @@ int sp_render_labels_u8c3(unsigned char* img, int h, int w, const float* box, co
                           int image, int rows, const sp_label_style* style_host, const unsigned char* caption_dev /* may be NULL */,
                           void* workspace, void* stream);
 
+/* ---- redaction: the heads or the whole persons of one image hidden behind a mosaic or a constant colour ------------------------------------
+ * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] in and out, 1 <= h, w <= 16384; it reads the rows the overlay reads:
+ * keep[seg[image] .. seg[image] + keep_count[image]) of kps fp64 [rows, joints, 3] / box fp32 [rows, 5], the count clamped as above.  The
+ * rules (simple_pose_amd/csrc/sp_redact.h states them once for the device and the host; all integer but q, the overlay's quantisation
+ * q(v) = (int32) rint(v * 16.0), which rejects a value that is not finite or has |v| > 32768):
+ *   cells        the frame is cut into cell x cell pixel cells on a grid anchored at (0, 0), cell one of 4, 8, 16, 32, 64; the cells of the
+ *                last column / row are clipped to the image.  A cell is redacted as a whole or left alone: no partial cells, no blending,
+ *                so no original pixel of a redacted cell survives and the order of the persons does not matter.
+ *   modes        SP_REDACT_MOSAIC: every pixel of a redacted cell becomes, per channel, (sum + n / 2) / n, the sum over the n pixels of
+ *                the clipped cell in the SOURCE image (never the canvas: a cell two persons hit is the cell one person hits).
+ *                SP_REDACT_FILL: every pixel of a redacted cell becomes the constant BGR colour `fill`.
+ *   regions      one per kept person, in 1/16 px: a disc {cx, cy, r} or a rectangle {ax, ay, bx, by} (ax <= bx, ay <= by), or empty.  An
+ *                empty slot stays in the array: no compaction.  "The box" below is (q(x1), q(y1), q(x2), q(y2)) of the person's box with
+ *                both axes ordered by min / max; q rejecting any of the four rejects the box.
+ *     SP_REDACT_PERSON   the rectangle of the box; empty when the box is rejected.
+ *     SP_REDACT_HEAD     head joint head_joint[i], i < head_joints (1 .. 8 of them), is visible iff its c > in_vis_thre (a NaN c is not)
+ *                and q accepts both of its coordinates.  With at least one visible head joint the region is a disc: (minx, maxx, miny,
+ *                maxy) the bounding box of the visible head joints' quantised coordinates; cx = (minx + maxx) >> 1, cy = (miny + maxy) >> 1;
+ *                e = max(maxx - minx, maxy - miny); s = the longer side of the box, 0 when the box is rejected;
+ *                r0 = max(e >> 1, (s * head_min) >> 8); r = min((r0 * expand) >> 4, 1 << 20).  head_min: 1/256 of the box side, 0 .. 256;
+ *                expand: sixteenths, 16 .. 64.  r == 0 is still a point: the cell that holds it is redacted.
+ *                With no visible head joint, `fallback`: SP_REDACT_FALLBACK_BOX_TOP the rectangle with the box's x range and y from y1 to
+ *                y1 + (((y2 - y1) * top_frac) >> 8) (top_frac: 1/256, 0 .. 256; empty when the box is rejected);
+ *                SP_REDACT_FALLBACK_BOX the person rectangle; SP_REDACT_FALLBACK_NONE empty.
+ *   hit          a cell is redacted iff its closed rectangle [16 X0, 16 X1 + 15] x [16 Y0, 16 Y1 + 15] (X0 .. X1, Y0 .. Y1 its clipped pixel
+ *                range) meets a region.  Rectangle: the intervals overlap on both axes.  Disc: dx = max(lo - cx, 0, cx - hi) on x, dy
+ *                likewise on y, and dx * dx + dy * dy <= r * r in int64.
+ * style_host is HOST memory, validated and copied into the kernel arguments (no host-to-device copy: capturable). */
+#define SP_REDACT_HEAD 0
+#define SP_REDACT_PERSON 1
+#define SP_REDACT_MOSAIC 0
+#define SP_REDACT_FILL 1
+#define SP_REDACT_FALLBACK_BOX_TOP 0
+#define SP_REDACT_FALLBACK_BOX 1
+#define SP_REDACT_FALLBACK_NONE 2
+#define SP_REDACT_MAX_HEAD_JOINTS 8
+#define SP_REDACT_MAX_RADIUS (1 << 20) /* 1/16 px */
+typedef struct sp_redact_style {
+    int32_t region;                                     /* SP_REDACT_HEAD / SP_REDACT_PERSON */
+    int32_t mode;                                       /* SP_REDACT_MOSAIC / SP_REDACT_FILL */
+    int32_t cell;                                       /* 4, 8, 16, 32 or 64 pixels */
+    int32_t expand;                                     /* sixteenths, 16 .. 64 */
+    int32_t head_min;                                   /* 1/256 of the box's longer side, 0 .. 256 */
+    int32_t head_joints;                                /* 1 .. 8 */
+    int32_t head_joint[SP_REDACT_MAX_HEAD_JOINTS];      /* joint indices, each < joints (read for SP_REDACT_HEAD only) */
+    int32_t fallback;                                   /* SP_REDACT_FALLBACK_* */
+    int32_t top_frac;                                   /* 1/256 of the box's height, 0 .. 256 */
+    double in_vis_thre;
+    unsigned char fill[3];                              /* BGR */
+} sp_redact_style;
+/* bytes of the region array for `rows` person slots (0 .. 2048) */
+int sp_redact_workspace_bytes(int rows, int64_t* bytes);
+/* Two launches (redact_regions_kernel: one thread per person slot writes a region record with its pixel bounding box; redact_tile_kernel:
+ * one 256-thread workgroup per tile of 64 x max(16, cell) pixels scans the records in chunks of 256, marks the tile's hit cells, and only
+ * if one is hit reads the tile's source pixels once, reduces the cell sums - shuffles inside a wave, LDS between waves - and writes the
+ * tile once); no copy, no synchronisation, capturable.  dst == src (in place) is allowed: a tile nothing touches is then neither read nor
+ * written; any other overlap of src and dst is refused; out of place, untouched tiles are copied.  4-byte accesses when w % 4 == 0 and
+ * both pointers are 4-byte aligned, bytes otherwise.  rows == 0 is a no-op in place and a copy out of place (kps .. workspace are not
+ * read).  workspace: sp_redact_workspace_bytes, 4-byte aligned device memory, overwritten by every call; kps 8-byte aligned. */
+int sp_redact_u8c3(const unsigned char* src, unsigned char* dst, int h, int w, const double* kps, const float* box, const int32_t* keep,
+                   const int32_t* keep_count, const int32_t* seg, int image, int rows, int joints, const sp_redact_style* style_host,
+                   void* workspace, void* stream);
+
 /* ---- baseline JPEG decoding: file bytes in, uint8 BGR [H,W,3] images out ---------------------------------------------------------------------
  * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
  * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF

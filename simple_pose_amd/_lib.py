@@ -127,6 +127,20 @@ SP_LABEL_MAX_TEMPLATE, SP_LABEL_MAX_CHARS, SP_LABEL_CAPTION_BYTES, SP_LABEL_MAX_
 SP_LABEL_FIELDS = {"id": 1, "score": 2, "conf": 3, "n": 4, "image": 5}        # field name -> template byte; {n}, {image}: captions only
 SP_LABEL_CORNERS = {"tl": 0, "tr": 1, "bl": 2, "br": 3}
 
+
+class RedactStyle(ctypes.Structure):
+    """Mirror of `sp_redact_style` (field order is ABI): host memory, copied into the kernel arguments by sp_redact_u8c3."""
+    _fields_ = [("region", c_int32), ("mode", c_int32), ("cell", c_int32), ("expand", c_int32), ("head_min", c_int32), ("head_joints", c_int32),
+                ("head_joint", c_int32 * 8), ("fallback", c_int32), ("top_frac", c_int32), ("in_vis_thre", c_double),
+                ("fill", ctypes.c_uint8 * 3)]
+
+
+SP_REDACT_REGIONS = {"head": 0, "person": 1}
+SP_REDACT_MODES = {"mosaic": 0, "fill": 1}
+SP_REDACT_FALLBACKS = {"box_top": 0, "box": 1, "none": 2}
+SP_REDACT_CELLS = (4, 8, 16, 32, 64)
+SP_REDACT_MAX_HEAD_JOINTS = 8
+
 class TileRef(ctypes.Structure):
     """Mirror of `sp_tile_ref` (field order is ABI): one pass of tiled detection, a rectangle of a frame in device memory."""
     _fields_ = [("data", ctypes.c_uint64), ("h", c_int32), ("w", c_int32), ("pitch", c_int32), ("new_h", c_int32), ("new_w", c_int32),
@@ -316,6 +330,8 @@ SYMBOLS = {
     "sp_render_font_glyph": (c_int, [c_int, _P]),
     "sp_render_labels_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_int64)]),
     "sp_render_labels_u8c3": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(LabelStyle), _P, _P, _P]),
+    "sp_redact_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_int64)]),
+    "sp_redact_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RedactStyle), _P, _P]),
     "sp_yuv420_to_bgr_u8c3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "sp_bgr_to_yuv420_u8c3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P]),
     "sp_yuv420_to_bgr_images_u8c3": (c_int, [_P, c_int, c_int, c_int, _P]),

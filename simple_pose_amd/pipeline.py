@@ -22,7 +22,11 @@ With `renderer=PoseRenderer(...)` (visualize.py) the kept poses are drawn into a
 launches (sp_render_poses_u8c3) after sp_oks_nms, on the same stream and inside the same graph; without one nothing is allocated or launched.
 A renderer with a `label` or a `caption` adds two more (sp_render_labels_u8c3: ids, scores and the kept count formatted on the device); the
 caption's bytes are staged into the frame ahead of the launches or the replay (_stage_caption), so a captured frame shows a new caption.
-With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer, the source - is encoded to a baseline JPEG file
+With `redactor=Redactor(...)` (visualize.py) the canvas is produced from the source by sp_redact_u8c3 (two launches, out of place): the kept
+persons' heads, or the whole persons, behind a mosaic or a constant colour, from this frame's raw key points and boxes.  The renderer's
+launches, if there is one, then run in place on that canvas - redaction, then capsules, then text - and `PoseResult.image` exists with a
+redactor or a renderer; the poses themselves are bit for bit what they are without one.
+With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer or a redactor, the source - is encoded to a baseline JPEG file
 after the frame on the same stream (sp_jpeg_encode_batch, outside the graph: it uploads its descriptors), and `PoseResult.jpeg` holds the
 file's bytes; without one nothing is allocated or launched.
 A list of differently sized images is one call too (mixed_batch.py): the images are grouped by letterboxed net shape, each group is one
@@ -52,7 +56,7 @@ from .datasets.jpeg import JpegDecoder, JpegEncoder
 from .mixed_batch import MixedBatch, check_det_counts, check_images
 from .tiling import TilePlan, Tiling, plan_pass_groups
 from .video import YuvBatch, YuvFrame, convert_into, resolve
-from .visualize import PoseRenderer
+from .visualize import PoseRenderer, Redactor
 
 P = _lib.ptr
 MAX_CAPACITY = 2048                  # the OKS-NMS group limit (sp_oks_nms)
@@ -66,10 +70,11 @@ class PoseResult:
     box: np.ndarray                  # float32 [n, 5]: x1, y1, x2, y2, detector confidence
     dropped: int = 0                 # selected detections of this image that did not fit `capacity`
     track_id: np.ndarray = None      # int32 [n]: the persons' identities (tracking.PoseTracker.update only; None from estimate*)
-    image: torch.Tensor = None       # uint8 BGR [H, W, 3] on the device, the poses drawn in (estimators with a `renderer` only): a VIEW of the
-                                     # frame's canvas, valid until the next call with the same source shape - .clone() it to keep it
-    jpeg: bytes = None               # the frame (the canvas, or the source without a renderer) as a baseline JPEG file (estimators with an
-                                     # `encoder` only)
+    image: torch.Tensor = None       # uint8 BGR [H, W, 3] on the device: the source redacted (estimators with a `redactor`), then the poses
+                                     # drawn in (estimators with a `renderer`); None without both.  A VIEW of the frame's canvas, valid until
+                                     # the next call with the same source shape - .clone() it to keep it
+    jpeg: bytes = None               # the frame (the canvas, or the source without a renderer and a redactor) as a baseline JPEG file
+                                     # (estimators with an `encoder` only)
     keypoints_smooth: np.ndarray = None     # float64 [n, J, 3]: `keypoints` through the tracker's One-Euro filter, c unfiltered
                                      # (tracking.PoseTracker(smooth=...).update only)
 
@@ -131,8 +136,9 @@ class _Frame:
         self.params = None
         self.keepalive = None
         self.tiles = None                # tiling.TilePlan: built with the first tiled detector frame of this shape
-        self.canvas = None               # [B, H, W, 3] and the primitive array: allocated with the first frame of an estimator that has a renderer
-        self.render_ws = None
+        self.canvas = None               # [B, H, W, 3]: allocated with the first frame of an estimator that has a renderer or a redactor
+        self.render_ws = None            # the primitive array (a renderer's) and the region array (a redactor's), allocated likewise
+        self.redact_ws = None
         self.label_ws = None             # the record array, the captions [B, 64] and their pinned twin: allocated with the first frame of an
         self.caption = None              # estimator whose renderer draws text
         self.caption_host = None
@@ -160,14 +166,17 @@ class TopDownPoseEstimator(object):
     `shift_heatmap`: Simple-Baselines' SHIFT_HEATMAP on the un-mirrored maps.  `estimate`, `estimate_batch` and `estimate_boxes` honour it.
     `tiling`: a `tiling.Tiling` - the detector runs on overlapping tiles of every frame (and on the whole frame) and the boxes are fused
     on the device, so that small persons in large frames are found; `estimate`, same-sized `estimate_batch` and the trackers' detector
-    frames honour it, a list of differently sized images together with it is refused, `estimate_boxes` has no detector to tile."""
+    frames honour it, a list of differently sized images together with it is refused, `estimate_boxes` has no detector to tile.
+    `renderer`: a `visualize.PoseRenderer` - the kept poses drawn into `PoseResult.image`; `redactor`: a `visualize.Redactor` - the kept
+    persons' heads (or the persons) hidden in `PoseResult.image`, before anything is drawn; `encoder`: a `datasets.jpeg.JpegEncoder` -
+    `PoseResult.jpeg`.  Every entry point and the trackers honour the three."""
 
     MAX_GRAPHS = 8
     MAX_DET = 300                    # non_max_suppression's default, what single_predict uses
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
                  in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
-                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None, tiling=None):
+                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None, tiling=None, redactor=None):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -193,6 +202,9 @@ class TopDownPoseEstimator(object):
         if renderer is not None and not isinstance(renderer, PoseRenderer):
             raise TypeError(f"renderer: expected a simple_pose_amd.visualize.PoseRenderer or None, got {type(renderer).__name__}")
         self.renderer = renderer
+        if redactor is not None and not isinstance(redactor, Redactor):
+            raise TypeError(f"redactor: expected a simple_pose_amd.visualize.Redactor or None, got {type(redactor).__name__}")
+        self.redactor = redactor
         if encoder is not None and not isinstance(encoder, JpegEncoder):
             raise TypeError(f"encoder: expected a simple_pose_amd.datasets.jpeg.JpegEncoder or None, got {type(encoder).__name__}")
         if encoder is not None and encoder.device != torch.device(detector.device):
@@ -242,9 +254,12 @@ class TopDownPoseEstimator(object):
         else:
             self._frames.pop(key)                # most recently used last
         self._frames[key] = fr
-        if self.renderer is not None and fr.canvas is None:
+        if (self.renderer is not None or self.redactor is not None) and fr.canvas is None:
             fr.canvas = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=self.device)
+        if self.renderer is not None and fr.render_ws is None:
             fr.render_ws = PoseRenderer.workspace(self.capacity, J, self.device)
+        if self.redactor is not None and fr.redact_ws is None:
+            fr.redact_ws = Redactor.workspace(self.capacity, self.device)
         if self.renderer is not None and self.renderer.has_text and fr.label_ws is None:
             fr.label_ws = PoseRenderer.label_workspace(self.capacity, self.device)
             fr.caption = torch.zeros((B, _lib.SP_LABEL_CAPTION_BYTES), dtype=torch.uint8, device=self.device)
@@ -316,7 +331,8 @@ class TopDownPoseEstimator(object):
         det_id = tuple(id(p) for p in det_prog) if isinstance(det_prog, tuple) else id(det_prog)
         return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
                 det_id, id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap,
-                None if self.renderer is None else self.renderer.key(), None if self.tiling is None else self.tiling.key())
+                None if self.renderer is None else self.renderer.key(), None if self.tiling is None else self.tiling.key(),
+                None if self.redactor is None else self.redactor.key())
 
     def _det_program(self, B: int, H: int, W: int):
         """What `_detect` runs on B frames of H x W: the detector program of their letterboxed shape, or, with a tiling, the programs of
@@ -401,16 +417,23 @@ class TopDownPoseEstimator(object):
         """The overlay of every image's kept poses into the frame's canvas: one sp_render_poses_u8c3 (two launches) per image index, reading
         the buffers sp_oks_nms (and, `tracked`, sp_track_associate) just wrote; `kps`: the poses to draw instead of the frame's own (a
         smoothing tracker's kps_smooth).  A renderer with text then labels the canvas (sp_render_labels_u8c3, two more launches) from the
-        frame's scores, ids and staged captions (_stage_caption, which the caller ran outside any capture).  Nothing without a renderer."""
-        if self.renderer is None:
+        frame's scores, ids and staged captions (_stage_caption, which the caller ran outside any capture).  With a redactor the canvas
+        comes from sp_redact_u8c3 first (two launches, source -> canvas, always from the frame's raw kps64) and the renderer then draws in
+        place on it.  Nothing without a renderer and a redactor."""
+        if self.renderer is None and self.redactor is None:
             return
         for b in range(fr.B):
-            self.renderer.launch(fr.src[b], fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
-                                 fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws, score=fr.score, caption=fr.caption,
-                                 label_workspace=fr.label_ws)
+            src = fr.src[b]
+            if self.redactor is not None:
+                self.redactor.launch(src, fr.canvas[b], fr.kps64, fr.box, fr.keep, fr.keep_count, fr.seg, b, self.capacity, J, fr.redact_ws)
+                src = fr.canvas[b]
+            if self.renderer is not None:
+                self.renderer.launch(src, fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
+                                     fr.keep_count, fr.seg, b, self.capacity, J, fr.render_ws, score=fr.score, caption=fr.caption,
+                                     label_workspace=fr.label_ws)
 
     def _issue(self, fr: _Frame, det_prog, pose_prog, single_stream: bool) -> None:
-        """The frame's launches: detector, poses, overlay."""
+        """The frame's launches: detector, poses, redaction and overlay."""
         self._detect(fr, det_prog, single_stream)
         self._poses(fr, pose_prog, single_stream)
         self._render(fr, pose_prog.out_shape[0])
@@ -424,7 +447,8 @@ class TopDownPoseEstimator(object):
     def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
         """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
         # the frames as JPEG files: launched behind the frame on its stream, before the fetch that waits for both
-        enc = None if self.encoder is None else self.encoder.encode_device(fr.src if self.renderer is None else fr.canvas)
+        drawn = self.renderer is not None or self.redactor is not None
+        enc = None if self.encoder is None else self.encoder.encode_device(fr.canvas if drawn else fr.src)
         h = fr.fetch()
         files = [None] * fr.B if enc is None else self.encoder.collect(*enc)
         if detected and (h["status"] & 1).any():
@@ -438,7 +462,7 @@ class TopDownPoseEstimator(object):
                 raise HipLibraryError(f"image {b}: more than {MAX_CAPACITY} persons")
             rows = h["keep"][lo:lo + n]
             out.append(PoseResult(h["kps64"][rows], h["score"][rows], h["box"][rows], int(h["dropped"][b]),
-                                  h["track_id"][rows] if tracked else None, None if self.renderer is None else fr.canvas[b], files[b],
+                                  h["track_id"][rows] if tracked else None, fr.canvas[b] if drawn else None, files[b],
                                   h["kps_smooth"][rows] if tracked and "kps_smooth" in h else None))
         return out
 
@@ -482,7 +506,7 @@ class TopDownPoseEstimator(object):
         and `canvas` a list of per-image canvases, which _render, the encoder and _results index like the dense blocks."""
         fr = self._frame(mb.B, 0, 0, max_det, J)
         fr.src = mb.srcs
-        if self.renderer is not None:
+        if self.renderer is not None or self.redactor is not None:
             fr.canvas = [torch.empty_like(s) for s in mb.srcs]
         return fr
 

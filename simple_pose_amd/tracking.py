@@ -11,7 +11,8 @@ with the tracks by OKS (the similarity OKS-NMS uses, the same device function), 
 tracks (ids 1, 2, ... never reused), tracks unseen for more than `max_age` frames are freed.  The track state is device memory owned by
 the tracker; the ids come back in the frame's packed buffer, so a tracked frame still ends in ONE device-to-host copy, and with
 `estimator.use_graph` it is ONE graph replay.  There is no CPU fallback.  An estimator built with a `renderer` also draws the frame
-(`PoseResult.image`, the persons coloured by track id), inside the same replay.
+(`PoseResult.image`, the persons coloured by track id), inside the same replay; one built with a `redactor` hides the heads or the
+persons in that image first (sp_redact_u8c3, from the frame's raw key points), on detector and propagated frames alike.
 
 Two kinds of frame, chosen by the host alone (from its own counters and the previous result, no extra synchronisation):
   detector frame    _detect -> _poses -> sp_track_associate_images: the first frame, the first after reset(), every `detect_every`-th frame (counted
@@ -32,7 +33,8 @@ motion is steadied and fast motion is not lagged) per track and joint on the fra
 the tracks', keyed by slot, and a slot handed to another id starts again.  The frame's time is one double in device memory that the host
 writes before the launch or the replay, through a pinned buffer and a copy on the frame's stream (never a kernel argument: a captured graph
 freezes those), `timestamp` in seconds or, without one, frame index / fps.  The smoothed poses come back in the same packed buffer (`PoseResult.keypoints_smooth`; the confidences are not filtered)
-and are what the estimator's `renderer` draws, inside the same replay.  `keypoints`, `score`, `box`, `track_id`, the association and the
+and are what the estimator's `renderer` draws, inside the same replay (its `redactor` keeps reading the raw poses: the face is where this
+frame's decode put it, not where the filter lags to).  `keypoints`, `score`, `box`, `track_id`, the association and the
 propagated boxes keep using the raw poses: they are bit for bit what they are without smoothing.  Speeds are measured in body sizes (the
 box's longer side) per second, so the parameters do not depend on the resolution.  OneEuro's defaults are design choices as well.
 
@@ -275,7 +277,8 @@ class MultiStreamTracker(object):
             self._associate(fr, J)
             if self.smooth is not None:
                 self._smooth(fr, J)
-        # (nothing without estimator.renderer) the frame's ids colour the persons; a smoothing tracker draws the smoothed poses
+        # (nothing without estimator.renderer / .redactor) the frame's ids colour the persons; a smoothing tracker draws the smoothed
+        # poses, while a redactor always hides what this frame's raw key points say
         est._render(fr, J, tracked=True, kps=None if self.smooth is None else fr.kps_smooth)
 
     def _params(self, det_prog, pose_prog) -> tuple:

@@ -18,7 +18,16 @@ person's box: `{id}` is the track id (the pick position + 1 without a tracker), 
 confidence, formatted on the device from the frame's buffers.  `caption="cam 3: {n} persons"` (one string, or one per image) puts a black
 plate into a corner of the frame: `{n}` is the image's kept count, `{image}` its index.  `{{` and `}}` are literal braces.  The caption
 can be reassigned at any time (`renderer.caption = ...`): an estimator stages its bytes through a pinned buffer ahead of the launches or
-the replay, so a captured frame shows the new text without being captured again.  The font is ASCII only."""
+the replay, so a captured frame shows the new text without being captured again.  The font is ASCII only.
+
+    x = Redactor(region="head", mode="mosaic", cell=16)            # or region="person", mode="fill", fill=(0, 0, 0)
+    out = x.redact(img, result)                                   # the heads of the result's persons behind a mosaic
+    est = TopDownPoseEstimator(detector, pose_model, redactor=x)  # in the frame: PoseResult.image is redacted before anything is drawn
+
+Redaction is sp_redact_u8c3 (csrc/redact.hip, the rules in csrc/sp_redact.h and include/simple_pose_hip.h), two launches: the frame is cut
+into `cell` x `cell` pixel cells, and every cell that a person's region meets - a disc around the visible head joints, or the box - becomes
+the mean of its source pixels (mosaic) or a constant colour (fill), as a whole.  Inside an estimator or a tracker it produces the canvas
+from the source ahead of the renderer's launches, from the RAW key points of this frame (under a smoothing tracker as well)."""
 from __future__ import annotations
 
 import ctypes
@@ -82,6 +91,29 @@ def _number(name, v, lo, hi, what):
     if not isinstance(v, (int, float)) or isinstance(v, bool) or not (lo <= float(v) <= hi):
         raise ValueError(f"{name}: {what}, got {v!r}")
     return float(v)
+
+
+def _image_and_out(img, out):
+    """`img` (uint8 BGR [H, W, 3], numpy or CUDA) as a contiguous CUDA tensor, and `out` checked against it (a new tensor when None)."""
+    if isinstance(img, np.ndarray):
+        if img.dtype != np.uint8:
+            raise TypeError(f"expected a uint8 BGR image, got {img.dtype}")
+        img = torch.from_numpy(np.ascontiguousarray(img)).to("cuda")
+    if not isinstance(img, torch.Tensor):
+        raise TypeError(f"expected a uint8 BGR image (numpy or CUDA), got {type(img).__name__}")
+    if not img.is_cuda:
+        raise HipLibraryError(f"image tensor is on {img.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
+    if img.dtype != torch.uint8:
+        raise TypeError(f"expected a uint8 BGR image, got {img.dtype}")
+    if img.dim() != 3 or img.shape[2] != 3 or 0 in tuple(img.shape):
+        raise ValueError(f"expected uint8 BGR [H, W, 3], got {tuple(img.shape)}")
+    img = img.contiguous()
+    if out is None:
+        out = torch.empty_like(img)
+    elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous()
+              and out.device == img.device):
+        raise ValueError(f"out: expected a contiguous CUDA uint8 tensor {tuple(img.shape)} on {img.device}")
+    return img, out
 
 
 class PoseRenderer(object):
@@ -249,24 +281,7 @@ class PoseRenderer(object):
         if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
             raise ValueError(f"image: an image index in 0..4095, got {image!r}")
         image = int(image)
-        if isinstance(img, np.ndarray):
-            if img.dtype != np.uint8:
-                raise TypeError(f"expected a uint8 BGR image, got {img.dtype}")
-            img = torch.from_numpy(np.ascontiguousarray(img)).to("cuda")
-        if not isinstance(img, torch.Tensor):
-            raise TypeError(f"expected a uint8 BGR image (numpy or CUDA), got {type(img).__name__}")
-        if not img.is_cuda:
-            raise HipLibraryError(f"image tensor is on {img.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
-        if img.dtype != torch.uint8:
-            raise TypeError(f"expected a uint8 BGR image, got {img.dtype}")
-        if img.dim() != 3 or img.shape[2] != 3 or 0 in tuple(img.shape):
-            raise ValueError(f"expected uint8 BGR [H, W, 3], got {tuple(img.shape)}")
-        img = img.contiguous()
-        if out is None:
-            out = torch.empty_like(img)
-        elif not (isinstance(out, torch.Tensor) and out.is_cuda and out.dtype == torch.uint8 and out.shape == img.shape and out.is_contiguous()
-                  and out.device == img.device):
-            raise ValueError(f"out: expected a contiguous CUDA uint8 tensor {tuple(img.shape)} on {img.device}")
+        img, out = _image_and_out(img, out)
         kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
         n = int(kps.shape[0])
         J = int(kps.shape[1]) if kps.ndim == 3 else 0
@@ -303,4 +318,104 @@ class PoseRenderer(object):
             lws = self.label_workspace(n, dev)
         with torch.cuda.device(dev):
             self.launch(img, out, d_kps, d_box, tid, keep, keep_count, seg, image, n, J, ws, score=score, caption=cap, label_workspace=lws)
+        return out
+
+
+class Redactor(object):
+    """`region`: "head" (a disc around the visible head joints) or "person" (the box).  `mode`: "mosaic" (a redacted cell becomes the mean
+    of its source pixels) or "fill" (the constant BGR colour `fill`).  `cell`: 4, 8, 16, 32 or 64 pixels; a cell is redacted as a whole or
+    left alone.  Head regions: `head_joints`: 1 .. 8 joint indices (default COCO's nose, eyes and ears); a head joint counts when its
+    max_val exceeds `in_vis_thre`; the disc's radius is half the longer side of the visible head joints' bounding box, at least `head_min`
+    (0 .. 1, quantised to 1/256) of the box's longer side, times `expand` (1 .. 4, quantised to 1/16).  `fallback`: what hides a person
+    without a visible head joint - "box_top" (the top `top_frac`, 0 .. 1 quantised to 1/256, of the box: the default fails closed), "box"
+    (the whole box) or "none"."""
+
+    def __init__(self, region: str = "head", mode: str = "mosaic", cell: int = 16, expand: float = 1.5, head_min: float = 20 / 256,
+                 head_joints=(0, 1, 2, 3, 4), fallback: str = "box_top", top_frac: float = 0.25, in_vis_thre: float = 0.2, fill=(0, 0, 0)):
+        if region not in _lib.SP_REDACT_REGIONS:
+            raise ValueError(f"region: 'head' or 'person', got {region!r}")
+        if mode not in _lib.SP_REDACT_MODES:
+            raise ValueError(f"mode: 'mosaic' or 'fill', got {mode!r}")
+        if not isinstance(cell, (int, np.integer)) or isinstance(cell, bool) or cell not in _lib.SP_REDACT_CELLS:
+            raise ValueError(f"cell: one of {', '.join(str(c) for c in _lib.SP_REDACT_CELLS)} pixels, got {cell!r}")
+        ex = _number("expand", expand, 1.0, 4.0, "a factor in 1..4")
+        hm = _number("head_min", head_min, 0.0, 1.0, "a fraction of the box side in 0..1")
+        tf = _number("top_frac", top_frac, 0.0, 1.0, "a fraction of the box height in 0..1")
+        try:
+            hj = [int(j) for j in head_joints]
+            ok = all(isinstance(j, (int, np.integer)) and not isinstance(j, bool) for j in head_joints)
+        except (TypeError, ValueError):
+            hj, ok = [], False
+        if not ok or not (1 <= len(hj) <= _lib.SP_REDACT_MAX_HEAD_JOINTS) or any(j < 0 or j >= 64 for j in hj):
+            raise ValueError(f"head_joints: expected 1..{_lib.SP_REDACT_MAX_HEAD_JOINTS} joint indices in 0..63, got {head_joints!r}")
+        if fallback not in _lib.SP_REDACT_FALLBACKS:
+            raise ValueError(f"fallback: 'box_top', 'box' or 'none', got {fallback!r}")
+        if not isinstance(in_vis_thre, (int, float)) or isinstance(in_vis_thre, bool) or in_vis_thre != in_vis_thre:
+            raise ValueError(f"in_vis_thre: a number, got {in_vis_thre!r}")
+        try:
+            col = np.asarray(fill)
+        except (TypeError, ValueError):
+            col = np.zeros(0)
+        if col.shape != (3,) or col.dtype.kind not in "iu" or col.min() < 0 or col.max() > 255:
+            raise ValueError(f"fill: a BGR triple of ints in 0..255, got {fill!r}")
+        self.region, self.mode, self.cell, self.fallback = region, mode, int(cell), fallback
+        self.expand16, self.head_min256, self.top_frac256 = int(round(ex * 16)), int(round(hm * 256)), int(round(tf * 256))
+        self.head_joints, self.in_vis_thre = tuple(hj), float(in_vis_thre)
+        self.fill = tuple(int(c) for c in col)
+        st = _lib.RedactStyle()
+        st.region, st.mode, st.cell = _lib.SP_REDACT_REGIONS[region], _lib.SP_REDACT_MODES[mode], self.cell
+        st.expand, st.head_min, st.top_frac = self.expand16, self.head_min256, self.top_frac256
+        st.head_joints = len(hj)
+        for i, j in enumerate(hj):
+            st.head_joint[i] = j
+        st.fallback = _lib.SP_REDACT_FALLBACKS[fallback]
+        st.in_vis_thre = self.in_vis_thre
+        st.fill[0], st.fill[1], st.fill[2] = self.fill
+        self._style = st
+
+    def key(self) -> tuple:
+        """Everything the launches depend on: two redactors with equal keys write the same pixels (a captured graph is reused only then)."""
+        return (self.region, self.mode, self.cell, self.expand16, self.head_min256, self.head_joints, self.fallback, self.top_frac256,
+                self.in_vis_thre, self.fill)
+
+    @staticmethod
+    def workspace(rows: int, device) -> torch.Tensor:
+        """The region array of `rows` person slots."""
+        n = ctypes.c_int64()
+        _lib.check(_lib.lib().sp_redact_workspace_bytes(rows, ctypes.byref(n)), "sp_redact_workspace_bytes")
+        return torch.zeros((max(int(n.value), 4),), dtype=torch.uint8, device=device)
+
+    def launch(self, src, dst, kps, box, keep, keep_count, seg, image: int, rows: int, joints: int, workspace) -> None:
+        """sp_redact_u8c3 on the current stream of src's device; every argument a CUDA tensor.  `dst` may be `src` (in place)."""
+        h, w = int(src.shape[0]), int(src.shape[1])
+        _lib.check(_lib.lib().sp_redact_u8c3(P(src), P(dst), h, w, P(kps), P(box), P(keep), P(keep_count), P(seg), image, rows, joints,
+                                             ctypes.byref(self._style), P(workspace), _lib.current_stream(src.device)), "sp_redact_u8c3")
+
+    @torch.no_grad()
+    def redact(self, img, result, out=None, image: int = 0) -> torch.Tensor:
+        """`img`: uint8 BGR [H, W, 3], numpy or CUDA; `result`: a PoseResult (its `keypoints`, never `keypoints_smooth`, and its `box`).
+        Returns a CUDA uint8 [H, W, 3]: `out` when given (contiguous; it may be `img` itself when that is a contiguous CUDA tensor,
+        redacted in place), a new tensor otherwise.  `image`: the index the rows are filed under (any index gives the same pixels)."""
+        if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
+            raise ValueError(f"image: an image index in 0..4095, got {image!r}")
+        image = int(image)
+        img, out = _image_and_out(img, out)
+        kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
+        n = int(kps.shape[0])
+        if n == 0:
+            if out.data_ptr() != img.data_ptr():
+                out.copy_(img)
+            return out
+        J = int(kps.shape[1]) if kps.ndim == 3 else 0
+        if kps.ndim != 3 or kps.shape[2] != 3 or not (1 <= J <= 64):
+            raise ValueError(f"result.keypoints: expected [n, J <= 64, 3], got {tuple(kps.shape)}")
+        box = np.ascontiguousarray(result.box, dtype=np.float32)
+        if box.shape != (n, 5):
+            raise ValueError(f"result.box: expected [{n}, 5], got {tuple(box.shape)}")
+        dev = img.device
+        up = lambda a: torch.from_numpy(a).to(dev)
+        counts, segs = np.zeros(image + 1, np.int32), np.zeros(image + 2, np.int32)
+        counts[image], segs[image + 1:] = n, n
+        with torch.cuda.device(dev):
+            self.launch(img, out, up(kps), up(box), up(np.arange(n, dtype=np.int32)), up(counts), up(segs), image, n, J, self.workspace(n, dev))
         return out
