@@ -1128,6 +1128,56 @@ int sp_redact_u8c3(const unsigned char* src, unsigned char* dst, int h, int w, c
                    const int32_t* keep_count, const int32_t* seg, int image, int rows, int joints, const sp_redact_style* style_host,
                    void* workspace, void* stream);
 
+/* ---- heat overlay: the kept persons' joint heat maps blended into one image ----------------------------------------------------------------
+ * (No new ABI version: these are additions.)  uint8 BGR [h, w, 3] in and out, 1 <= h, w <= 16384.  hm: fp32 [>= rows, joints, hm_h, hm_w]
+ * (NCHW; slot `row` of the frame is map `row`), trans_inv fp32 [rows, 2, 3] (heat-map px -> image px, as sp_topdown_plan writes it).  The
+ * live persons of `image` are the rows keep[lo + p], p < n, with (n, lo) the clamped count and offset the overlay uses; a row outside
+ * 0 .. rows - 1 is skipped.  The rules (simple_pose_amd/csrc/sp_heat.h states them once for the device and the host; all integer
+ * but the three floating-point steps named here, each one correctly rounded IEEE operation or a sequence run with contraction off):
+ *   plane        per live person a u8 [hm_h, hm_w] plane: m(y, x) = the maximum of hm[row, j, y, x] over the joints j < joints whose bit is
+ *                set in joint_mask (a NaN loses against every number; no such bit: the person is skipped); q8 = sp_heat_q(m, scale):
+ *                v = m * scale (ONE fp32 multiply); NaN -> 0, v >= 255 -> 255, v > 0 -> (uint8) v by truncation, else 0.
+ *   forward map  F = sp_invert_affine((double) trans_inv[row]) (image px -> heat-map px, pixel centres), c[i] = (int64) rint(F[i] * 65536.0).
+ *                The person is skipped when an F[i] is not finite, when F[0] = F[1] = F[3] = F[4] = 0 (a singular trans_inv, a dead slot's
+ *                zeros included), when a linear coefficient has |F| > 1024 or an offset |F| > 2^20.  Image pixel (X, Y), int64:
+ *                U = c[0] X + c[1] Y + c[2], V = c[3] X + c[4] Y + c[5] (1/65536 px); u = U >> 8, v = V >> 8 (arithmetic);
+ *                xi = u >> 8, fx = u & 255, yi = v >> 8, fy = v & 255.
+ *   sample       taps p(xi + dx, yi + dy), dx, dy in {0, 1}; a tap outside [0, hm_w) x [0, hm_h) reads 0;
+ *                val = ((256 - fx)(256 - fy) p00 + fx (256 - fy) p10 + (256 - fx) fy p01 + fx fy p11 + 32768) >> 16, in 0 .. 255.
+ *   combine      Vmax = the maximum of val over the image's live persons (0 where none reaches): the order of the persons does not matter.
+ *   blend        Vmax < threshold (1 .. 255): the pixel keeps its source bytes.  Otherwise colour = lut[Vmax] (lut: 256 BGR triples in
+ *                DEVICE memory), w = opacity16 * a (opacity16 0 .. 16; a = 256 for SP_HEAT_ALPHA_CONSTANT, a = Vmax + (Vmax >> 7) for
+ *                SP_HEAT_ALPHA_VALUE), and per channel out = (src (4096 - w) + colour w + 2048) >> 12.
+ *   box          every record carries a pixel bounding box for binning persons to tiles: the image of [-2, hm_w + 1] x [-2, hm_h + 1]
+ *                under trans_inv, padded by 2 px and clipped to 0 .. 16383; the record kernel then proves in int64, on the four rectangles
+ *                around the box, that U and V cannot reach a tap there, and widens the box to everything when it cannot.  It never
+ *                changes a pixel's value.
+ * style_host is HOST memory, validated and copied into the kernel arguments (no host-to-device copy: capturable). */
+#define SP_HEAT_ALPHA_CONSTANT 0
+#define SP_HEAT_ALPHA_VALUE 1
+#define SP_HEAT_MAX_MAP 256
+typedef struct sp_heat_style {
+    uint64_t joint_mask;                                /* bit j: joint j takes part in the maximum */
+    float scale;                                        /* finite, >= 0; 255 maps [0, 1] onto 0 .. 255 */
+    int32_t threshold;                                  /* 1 .. 255 */
+    int32_t opacity16;                                  /* 0 .. 16 */
+    int32_t alpha;                                      /* SP_HEAT_ALPHA_* */
+} sp_heat_style;
+/* bytes of the records and the u8 planes of `rows` person slots (0 .. 2048) with hm_h x hm_w maps (1 .. 256 each way) */
+int sp_heat_overlay_workspace_bytes(int rows, int hm_h, int hm_w, int64_t* bytes);
+/* Two launches (heat_planes_kernel: one 256-thread workgroup per person slot; a dead slot gets an empty record and reads nothing, a live
+ * one has its `joints` maps reduced to the u8 plane - 16-byte loads along x when hm_w % 4 == 0 and hm is 16-byte aligned, scalar loads
+ * otherwise - and its record written: c[6] and the box.  heat_tile_kernel: one 256-thread workgroup per 64 x 16 pixel tile scans the
+ * records in chunks of 256 into an LDS list of the persons that can reach the tile, and every pixel takes the maximum over the listed
+ * persons and is blended); no copy, no synchronisation, capturable.  dst == src (in place) is allowed: a tile with an empty list is then
+ * neither read nor written; any other overlap of src and dst is refused; out of place such a tile is copied.  4-byte stores when
+ * w % 4 == 0 and both pointers are 4-byte aligned, bytes otherwise.  rows == 0 is a no-op in place and a copy out of place (hm .. workspace
+ * are not read).  workspace: sp_heat_overlay_workspace_bytes, 8-byte aligned device memory, overwritten by every call; hm and trans_inv
+ * 4-byte aligned. */
+int sp_heat_overlay_u8c3(const unsigned char* src, unsigned char* dst, int h, int w, const float* hm, int joints, int hm_h, int hm_w,
+                         const float* trans_inv, const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int image, int rows,
+                         const sp_heat_style* style, const unsigned char* lut, void* workspace, void* stream);
+
 /* ---- baseline JPEG decoding: file bytes in, uint8 BGR [H,W,3] images out ---------------------------------------------------------------------
  * (No new ABI version: these are additions.)  The pixels are libjpeg-turbo's default decode (cv2.imread, PIL) bit for bit: Huffman decode,
  * the "islow" integer IDCT, "fancy" chroma upsampling, 16.16 fixed-point YCbCr -> BGR; a grayscale file gives three equal channels.  EXIF

@@ -141,6 +141,16 @@ SP_REDACT_FALLBACKS = {"box_top": 0, "box": 1, "none": 2}
 SP_REDACT_CELLS = (4, 8, 16, 32, 64)
 SP_REDACT_MAX_HEAD_JOINTS = 8
 
+
+class HeatStyle(ctypes.Structure):
+    """Mirror of `sp_heat_style` (field order is ABI): host memory, copied into the kernel arguments by sp_heat_overlay_u8c3."""
+    _fields_ = [("joint_mask", ctypes.c_uint64), ("scale", c_float), ("threshold", c_int32), ("opacity16", c_int32), ("alpha", c_int32)]
+
+
+SP_HEAT_ALPHA_CONSTANT, SP_HEAT_ALPHA_VALUE = 0, 1
+SP_HEAT_ALPHAS = {"constant": SP_HEAT_ALPHA_CONSTANT, "value": SP_HEAT_ALPHA_VALUE}
+SP_HEAT_MAX_MAP = 256
+
 class TileRef(ctypes.Structure):
     """Mirror of `sp_tile_ref` (field order is ABI): one pass of tiled detection, a rectangle of a frame in device memory."""
     _fields_ = [("data", ctypes.c_uint64), ("h", c_int32), ("w", c_int32), ("pitch", c_int32), ("new_h", c_int32), ("new_w", c_int32),
@@ -332,6 +342,9 @@ SYMBOLS = {
     "sp_render_labels_u8c3": (c_int, [_P, c_int, c_int, _P, _P, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(LabelStyle), _P, _P, _P]),
     "sp_redact_workspace_bytes": (c_int, [c_int, ctypes.POINTER(c_int64)]),
     "sp_redact_u8c3": (c_int, [_P, _P, c_int, c_int, _P, _P, _P, _P, _P, c_int, c_int, c_int, ctypes.POINTER(RedactStyle), _P, _P]),
+    "sp_heat_overlay_workspace_bytes": (c_int, [c_int, c_int, c_int, ctypes.POINTER(c_int64)]),
+    "sp_heat_overlay_u8c3": (c_int, [_P, _P, c_int, c_int, _P, c_int, c_int, c_int, _P, _P, _P, _P, c_int, c_int, ctypes.POINTER(HeatStyle), _P,
+                                     _P, _P]),
     "sp_yuv420_to_bgr_u8c3": (c_int, [_P, _P, _P, c_int, c_int, c_int, c_int, c_int, c_int, c_int, _P, c_int, _P]),
     "sp_bgr_to_yuv420_u8c3": (c_int, [_P, c_int, c_int, c_int, c_int, c_int, c_int, _P, _P, _P, c_int, c_int, _P]),
     "sp_yuv420_to_bgr_images_u8c3": (c_int, [_P, c_int, c_int, c_int, _P]),

@@ -82,17 +82,5 @@ __device__ __forceinline__ int sp_block_scan256(int v, int* lds, int& total) {
     return base + x - v;
 }
 
-// cv::warpAffine without WARP_INVERSE_MAP: the forward 2x3 map inverted in double, this way.  ONE statement of it for the host callers
-// (sp_warp_affine_*) and the device caller (sp_topdown_plan), whose maps must agree bit for bit: contraction is off inside.
-__host__ __device__ inline void sp_invert_affine(const double* fwd, double* inv) {
-#pragma clang fp contract(off)
-    double M[6];
-    for (int i = 0; i < 6; ++i) M[i] = fwd[i];
-    double D = M[0] * M[4] - M[1] * M[3];
-    D = D != 0 ? 1. / D : 0;
-    const double A11 = M[4] * D, A22 = M[0] * D;
-    M[0] = A11; M[1] *= -D; M[3] *= -D; M[4] = A22;
-    const double b1 = -M[0] * M[2] - M[1] * M[5], b2 = -M[3] * M[2] - M[4] * M[5];
-    M[2] = b1; M[5] = b2;
-    for (int i = 0; i < 6; ++i) inv[i] = M[i];
-}
+// sp_invert_affine (cv::warpAffine's inversion of a forward 2x3 map): stated once in sp_affine.h, which the CPU test programs read too
+#include "sp_affine.h"

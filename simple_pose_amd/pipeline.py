@@ -26,6 +26,9 @@ With `redactor=Redactor(...)` (visualize.py) the canvas is produced from the sou
 persons' heads, or the whole persons, behind a mosaic or a constant colour, from this frame's raw key points and boxes.  The renderer's
 launches, if there is one, then run in place on that canvas - redaction, then capsules, then text - and `PoseResult.image` exists with a
 redactor or a renderer; the poses themselves are bit for bit what they are without one.
+With `heat_overlay=HeatOverlay(...)` (visualize.py) the kept persons' heat maps - the tensor the decode reads, with the flip test the merged
+maps - are blended into the canvas by sp_heat_overlay_u8c3 (two launches) through the frame's own `trans_inv`: after the redaction, under
+the capsules and the text; out of place from the source when it is the first stage, in place on the canvas otherwise.
 With `encoder=JpegEncoder(...)` (datasets.jpeg) every image's canvas - without a renderer or a redactor, the source - is encoded to a baseline JPEG file
 after the frame on the same stream (sp_jpeg_encode_batch, outside the graph: it uploads its descriptors), and `PoseResult.jpeg` holds the
 file's bytes; without one nothing is allocated or launched.
@@ -56,7 +59,7 @@ from .datasets.jpeg import JpegDecoder, JpegEncoder
 from .mixed_batch import MixedBatch, check_det_counts, check_images
 from .tiling import TilePlan, Tiling, plan_pass_groups
 from .video import YuvBatch, YuvFrame, convert_into, resolve
-from .visualize import PoseRenderer, Redactor
+from .visualize import HeatOverlay, PoseRenderer, Redactor
 
 P = _lib.ptr
 MAX_CAPACITY = 2048                  # the OKS-NMS group limit (sp_oks_nms)
@@ -139,6 +142,8 @@ class _Frame:
         self.canvas = None               # [B, H, W, 3]: allocated with the first frame of an estimator that has a renderer or a redactor
         self.render_ws = None            # the primitive array (a renderer's) and the region array (a redactor's), allocated likewise
         self.redact_ws = None
+        self.heat_ws = None              # the records and u8 planes of an estimator with a heat overlay, allocated likewise
+        self.hm = None                   # the heat maps the last _poses decoded (kept only for a heat overlay, which reads them)
         self.label_ws = None             # the record array, the captions [B, 64] and their pinned twin: allocated with the first frame of an
         self.caption = None              # estimator whose renderer draws text
         self.caption_host = None
@@ -169,14 +174,15 @@ class TopDownPoseEstimator(object):
     frames honour it, a list of differently sized images together with it is refused, `estimate_boxes` has no detector to tile.
     `renderer`: a `visualize.PoseRenderer` - the kept poses drawn into `PoseResult.image`; `redactor`: a `visualize.Redactor` - the kept
     persons' heads (or the persons) hidden in `PoseResult.image`, before anything is drawn; `encoder`: a `datasets.jpeg.JpegEncoder` -
-    `PoseResult.jpeg`.  Every entry point and the trackers honour the three."""
+    `PoseResult.jpeg`; `heat_overlay`: a `visualize.HeatOverlay` - the kept persons' joint heat maps blended into `PoseResult.image`, over the
+    redaction and under the poses.  Every entry point and the trackers honour the four."""
 
     MAX_GRAPHS = 8
     MAX_DET = 300                    # non_max_suppression's default, what single_predict uses
 
     def __init__(self, detector, pose_model, decoder=None, capacity: int = 32, person_cls: int = 0, min_box_score: float = 0.0,
                  in_vis_thre: float = 0.2, oks_thre: float = 0.9, input_shape=(192, 256), output_shape=(48, 64), flip_test: bool = False,
-                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None, tiling=None, redactor=None):
+                 joint_pairs=None, shift_heatmap: bool = False, renderer=None, encoder=None, tiling=None, redactor=None, heat_overlay=None):
         from .detector.yolov5_detector import YOLOv5Detector
         from .metrics import BasicKeyPointDecoder, GaussTaylorKeyPointDecoder
         if not isinstance(capacity, int) or isinstance(capacity, bool) or not (1 <= capacity <= MAX_CAPACITY):
@@ -205,6 +211,9 @@ class TopDownPoseEstimator(object):
         if redactor is not None and not isinstance(redactor, Redactor):
             raise TypeError(f"redactor: expected a simple_pose_amd.visualize.Redactor or None, got {type(redactor).__name__}")
         self.redactor = redactor
+        if heat_overlay is not None and not isinstance(heat_overlay, HeatOverlay):
+            raise TypeError(f"heat_overlay: expected a simple_pose_amd.visualize.HeatOverlay or None, got {type(heat_overlay).__name__}")
+        self.heat_overlay = heat_overlay
         if encoder is not None and not isinstance(encoder, JpegEncoder):
             raise TypeError(f"encoder: expected a simple_pose_amd.datasets.jpeg.JpegEncoder or None, got {type(encoder).__name__}")
         if encoder is not None and encoder.device != torch.device(detector.device):
@@ -254,17 +263,25 @@ class TopDownPoseEstimator(object):
         else:
             self._frames.pop(key)                # most recently used last
         self._frames[key] = fr
-        if (self.renderer is not None or self.redactor is not None) and fr.canvas is None:
+        if self._draws() and fr.canvas is None:
             fr.canvas = torch.zeros((B, H, W, 3), dtype=torch.uint8, device=self.device)
         if self.renderer is not None and fr.render_ws is None:
             fr.render_ws = PoseRenderer.workspace(self.capacity, J, self.device)
         if self.redactor is not None and fr.redact_ws is None:
             fr.redact_ws = Redactor.workspace(self.capacity, self.device)
+        if self.heat_overlay is not None and fr.heat_ws is None:
+            fr.heat_ws = HeatOverlay.workspace(self.capacity, self.output_shape[1], self.output_shape[0], self.device)
+        if self.heat_overlay is not None:
+            self.heat_overlay.table(self.device)         # uploaded here, ahead of any capture
         if self.renderer is not None and self.renderer.has_text and fr.label_ws is None:
             fr.label_ws = PoseRenderer.label_workspace(self.capacity, self.device)
             fr.caption = torch.zeros((B, _lib.SP_LABEL_CAPTION_BYTES), dtype=torch.uint8, device=self.device)
             fr.caption_host = torch.zeros((B, _lib.SP_LABEL_CAPTION_BYTES), dtype=torch.uint8).pin_memory()
         return fr
+
+    def _draws(self) -> bool:
+        """Does a frame have a canvas (`PoseResult.image`) ?  With a redactor, a heat overlay or a renderer."""
+        return self.renderer is not None or self.redactor is not None or self.heat_overlay is not None
 
     def _stage_caption(self, fr: _Frame) -> None:
         """`renderer.caption` as it reads now into the frame's caption buffer: through the pinned twin, by a copy on the frame's stream
@@ -332,7 +349,8 @@ class TopDownPoseEstimator(object):
         return (float(d.conf_thresh), float(d.iou_thresh), self.person_cls, self.min_box_score, self.in_vis_thre, self.oks_thre,
                 det_id, id(pose_prog), id(self.decoder), self.flip_test, tuple(self._perm or ()), self.shift_heatmap,
                 None if self.renderer is None else self.renderer.key(), None if self.tiling is None else self.tiling.key(),
-                None if self.redactor is None else self.redactor.key())
+                None if self.redactor is None else self.redactor.key()) + \
+            (() if self.heat_overlay is None else ((self.heat_overlay.key(), id(self.heat_overlay)),))
 
     def _det_program(self, B: int, H: int, W: int):
         """What `_detect` runs on B frames of H x W: the detector program of their letterboxed shape, or, with a tiling, the programs of
@@ -407,6 +425,8 @@ class TopDownPoseEstimator(object):
             hm = hm[:cap]                            # merged in place; the decode sees the first `capacity` maps only
             _lib.check(lib.sp_heat_map_flip_merge(P(hm), P(hm) + hm.numel() * 4, self._perm, cap, J, oh, ow, int(self.shift_heatmap), P(hm),
                                                   stream), "sp_heat_map_flip_merge")
+        if self.heat_overlay is not None:
+            fr.hm = hm                               # what the decode reads is what the overlay shows (_render)
         kps, mv = self.decoder(hm, fr.trans_inv)
         kps3 = torch.cat([kps, mv], -1)              # eval.py:138
         _lib.check(lib.sp_pose_rescore(P(kps3), P(fr.box_score), cap, J, self.in_vis_thre, P(fr.kps64), P(fr.score), stream), "sp_pose_rescore")
@@ -419,13 +439,17 @@ class TopDownPoseEstimator(object):
         smoothing tracker's kps_smooth).  A renderer with text then labels the canvas (sp_render_labels_u8c3, two more launches) from the
         frame's scores, ids and staged captions (_stage_caption, which the caller ran outside any capture).  With a redactor the canvas
         comes from sp_redact_u8c3 first (two launches, source -> canvas, always from the frame's raw kps64) and the renderer then draws in
-        place on it.  Nothing without a renderer and a redactor."""
-        if self.renderer is None and self.redactor is None:
+        place on it.  With a heat overlay sp_heat_overlay_u8c3 (two launches) runs between the two - from the source when nothing was
+        redacted, in place on the canvas otherwise - so the order is redaction, heat, capsules, text.  Nothing without any of the three."""
+        if not self._draws():
             return
         for b in range(fr.B):
             src = fr.src[b]
             if self.redactor is not None:
                 self.redactor.launch(src, fr.canvas[b], fr.kps64, fr.box, fr.keep, fr.keep_count, fr.seg, b, self.capacity, J, fr.redact_ws)
+                src = fr.canvas[b]
+            if self.heat_overlay is not None:
+                self.heat_overlay.launch(src, fr.canvas[b], fr.hm, fr.trans_inv, fr.keep, fr.keep_count, fr.seg, b, self.capacity, fr.heat_ws)
                 src = fr.canvas[b]
             if self.renderer is not None:
                 self.renderer.launch(src, fr.canvas[b], fr.kps64 if kps is None else kps, fr.box, fr.track_id if tracked else None, fr.keep,
@@ -442,12 +466,13 @@ class TopDownPoseEstimator(object):
         issue = lambda: self._issue(fr, det_prog, pose_prog, True)
         fr.graph, fr.params = capture_graph(self.device, issue, issue), self._params(det_prog, pose_prog)
         # the nodes hold raw pointers into both programs' activation pools: keep them alive whatever Program._alloc evicts later
-        fr.keepalive = (pose_prog, pose_prog.pool_for(self._pose_batch(), self.device)) + self._det_keepalive(fr, det_prog)
+        # (and, with a heat overlay, into the heat maps of the captured run: a fresh tensor per run, so the tensor itself is kept)
+        fr.keepalive = (pose_prog, pose_prog.pool_for(self._pose_batch(), self.device), fr.hm) + self._det_keepalive(fr, det_prog)
 
     def _results(self, fr: _Frame, tracked: bool = False, detected: bool = True) -> List[PoseResult]:
         """`tracked`: the frame carries track ids; `detected`: the detector's NMS wrote the status words of this frame."""
         # the frames as JPEG files: launched behind the frame on its stream, before the fetch that waits for both
-        drawn = self.renderer is not None or self.redactor is not None
+        drawn = self._draws()
         enc = None if self.encoder is None else self.encoder.encode_device(fr.canvas if drawn else fr.src)
         h = fr.fetch()
         files = [None] * fr.B if enc is None else self.encoder.collect(*enc)
@@ -480,6 +505,7 @@ class TopDownPoseEstimator(object):
         if graph:
             if fr.graph is None or fr.params != self._params(det_prog, pose_prog):
                 self._capture(fr, det_prog, pose_prog)
+            fr.hm = fr.keepalive[2]                  # the heat maps the graph writes (an eager run in between left its own; None without an overlay)
             fr.graph.replay()
         else:
             self._issue(fr, det_prog, pose_prog, False)
@@ -506,7 +532,7 @@ class TopDownPoseEstimator(object):
         and `canvas` a list of per-image canvases, which _render, the encoder and _results index like the dense blocks."""
         fr = self._frame(mb.B, 0, 0, max_det, J)
         fr.src = mb.srcs
-        if self.renderer is not None or self.redactor is not None:
+        if self._draws():
             fr.canvas = [torch.empty_like(s) for s in mb.srcs]
         return fr
 

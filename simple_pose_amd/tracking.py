@@ -291,12 +291,14 @@ class MultiStreamTracker(object):
         params = self._params(det_prog, pose_prog)
         if entry is not None and entry[0] is fr and entry[2] == params:
             self._graphs[key] = self._graphs.pop(key)  # most recently used last
+            fr.hm = entry[3][5]                      # the heat maps THIS graph writes (the frame's other graph, or an eager run, left its own)
             return entry[1]
         est = self.estimator
         graph = capture_graph(est.device, lambda: self._launch(fr, detect, det_prog, pose_prog, True, warm_up=True),
                               lambda: self._launch(fr, detect, det_prog, pose_prog, True))
         # the nodes hold raw pointers into both programs' activation pools for the batch sizes used: keep them alive
-        keepalive = (pose_prog, pose_prog.pool_for(est._pose_batch(), est.device), self._state, self._sim, self._smooth_state) + \
+        # (and, with a heat overlay on the estimator, the heat maps of the captured run: fr.hm, None without one)
+        keepalive = (pose_prog, pose_prog.pool_for(est._pose_batch(), est.device), self._state, self._sim, self._smooth_state, fr.hm) + \
             est._det_keepalive(fr, det_prog)
         self._graphs.pop(key, None)
         if len(self._graphs) >= self.MAX_GRAPHS:

@@ -27,7 +27,15 @@ the replay, so a captured frame shows the new text without being captured again.
 Redaction is sp_redact_u8c3 (csrc/redact.hip, the rules in csrc/sp_redact.h and include/simple_pose_hip.h), two launches: the frame is cut
 into `cell` x `cell` pixel cells, and every cell that a person's region meets - a disc around the visible head joints, or the box - becomes
 the mean of its source pixels (mosaic) or a constant colour (fill), as a whole.  Inside an estimator or a tracker it produces the canvas
-from the source ahead of the renderer's launches, from the RAW key points of this frame (under a smoothing tracker as well)."""
+from the source ahead of the renderer's launches, from the RAW key points of this frame (under a smoothing tracker as well).
+
+    h = HeatOverlay(colormap="jet", opacity=0.6, alpha="value", threshold=0.1)
+    out = h.overlay(img, heat_maps, trans_inv)                    # CUDA fp32 [n, J, h, w] maps through [n, 2, 3] maps -> image
+    est = TopDownPoseEstimator(detector, pose_model, heat_overlay=h)   # in the frame: the kept persons' maps, under the skeleton
+
+The heat overlay is sp_heat_overlay_u8c3 (csrc/heat.hip, the rules in csrc/sp_heat.h and include/simple_pose_hip.h), two launches: what
+the reference's draw_heat_map shows in a window - the maximum over the joints' maps times 255 - warped back into the frame through each
+kept person's trans_inv and blended in through a colour table."""
 from __future__ import annotations
 
 import ctypes
@@ -418,4 +426,149 @@ class Redactor(object):
         counts[image], segs[image + 1:] = n, n
         with torch.cuda.device(dev):
             self.launch(img, out, up(kps), up(box), up(np.arange(n, dtype=np.int32)), up(counts), up(segs), image, n, J, self.workspace(n, dev))
+        return out
+
+
+def _colormap(name: str) -> np.ndarray:
+    """The named table as uint8 [256, 3] BGR, by integer formulas (v = 0 .. 255, clamp to 0 .. 255):
+    "gray"  B = G = R = v;
+    "hot"   R = clamp(3 v), G = clamp(3 v - 255), B = clamp(3 v - 510): black, red, yellow, white;
+    "jet"   R = clamp((765 - |8 v - 1530|) >> 1), G = clamp((765 - |8 v - 1020|) >> 1), B = clamp((765 - |8 v - 510|) >> 1): the classic
+            piecewise-linear 255 * clamp(1.5 - |4 t - k|, 0, 1), t = v / 255, k = 3, 2, 1: dark blue, blue, cyan, yellow, red, dark red."""
+    v = np.arange(256, dtype=np.int64)
+    if name == "gray":
+        b = g = r = v
+    elif name == "hot":
+        r, g, b = 3 * v, 3 * v - 255, 3 * v - 510
+    elif name == "jet":
+        r, g, b = ((765 - np.abs(8 * v - k)) >> 1 for k in (1530, 1020, 510))
+    else:
+        raise ValueError(f"colormap: 'gray', 'hot', 'jet' or a [256, 3] uint8 BGR array, got {name!r}")
+    return np.clip(np.stack([b, g, r], 1), 0, 255).astype(np.uint8)
+
+
+class HeatOverlay(object):
+    """The kept persons' joint heat maps blended into the frame (sp_heat_overlay_u8c3: csrc/heat.hip, the rules in csrc/sp_heat.h and
+    include/simple_pose_hip.h), two launches: per person the maximum over the joints' maps, quantised to 0 .. 255 (`gain` 1 maps [0, 1]
+    onto it: the reference's draw_heat_map, `(merge_map * 255).astype(np.uint8)`), warped into the image through the inverse of the
+    person's `trans_inv` with bilinear sampling in fixed point; a pixel takes the maximum over the persons, and where that reaches
+    `threshold` it is blended with the colour the table gives it.
+
+    `colormap`: "gray" (the reference's GRAY2BGR), "hot", "jet" (integer formulas: `_colormap`) or a [256, 3] uint8 BGR array; uploaded
+    once per device.  `opacity`: 0 .. 1, quantised to 1/16.  `alpha`: "value" (the weight grows with the heat) or "constant".
+    `threshold`: 0 .. 1 of the quantised range, min(255, max(1, int(threshold * 255))).  `gain`: finite, >= 0; the maps are multiplied by
+    float32(255 * gain).  `joints`: None (every joint) or the joint indices (< 64) whose maps take part.  There is no CPU fallback.
+
+        h = HeatOverlay(colormap="jet", opacity=0.6, alpha="value", threshold=0.1, gain=1.0, joints=None)
+        out = h.overlay(img, heat_maps, trans_inv)                    # every row of heat_maps [n, J, h, w] / trans_inv [n, 2, 3]
+        est = TopDownPoseEstimator(detector, pose_model, heat_overlay=h)   # in the frame: under the skeleton, over the redaction"""
+
+    def __init__(self, colormap="jet", opacity: float = 0.6, alpha: str = "value", threshold: float = 0.1, gain: float = 1.0, joints=None):
+        if isinstance(colormap, str):
+            lut = _colormap(colormap)
+        else:
+            try:
+                lut = np.asarray(colormap)
+            except (TypeError, ValueError):
+                lut = np.zeros(0)
+            if lut.shape != (256, 3) or lut.dtype != np.uint8:
+                raise ValueError(f"colormap: 'gray', 'hot', 'jet' or a [256, 3] uint8 BGR array, got {type(colormap).__name__}"
+                                 f"{' ' + str(lut.shape) + ' ' + str(lut.dtype) if isinstance(colormap, np.ndarray) else ''}")
+        op = _number("opacity", opacity, 0.0, 1.0, "a value in 0..1")
+        if alpha not in _lib.SP_HEAT_ALPHAS:
+            raise ValueError(f"alpha: 'value' or 'constant', got {alpha!r}")
+        th = _number("threshold", threshold, 0.0, 1.0, "a fraction of the quantised range in 0..1")
+        g = _number("gain", gain, 0.0, float("inf"), "a finite factor >= 0")
+        with np.errstate(over="ignore"):
+            scale = np.float32(255.0 * g)
+        if not np.isfinite(scale):
+            raise ValueError(f"gain: a finite factor >= 0 (255 * gain must fit float32), got {gain!r}")
+        if joints is None:
+            mask, js = (1 << 64) - 1, None
+        else:
+            try:
+                js = [int(j) for j in joints]
+                ok = all(isinstance(j, (int, np.integer)) and not isinstance(j, bool) for j in joints)
+            except (TypeError, ValueError):
+                js, ok = [], False
+            if not ok or len(js) == 0 or any(j < 0 or j >= 64 for j in js):
+                raise ValueError(f"joints: None (every joint) or a non-empty list of joint indices in 0..63, got {joints!r}")
+            mask = 0
+            for j in js:
+                mask |= 1 << j
+            js = tuple(sorted(set(js)))
+        self.lut = np.ascontiguousarray(lut).copy()
+        self.colormap = colormap if isinstance(colormap, str) else None
+        self.opacity16, self.alpha = int(round(op * 16)), alpha
+        self.threshold = min(255, max(1, int(th * 255)))
+        self.gain, self.scale, self.joints, self.joint_mask = g, scale, js, mask
+        st = _lib.HeatStyle()
+        st.joint_mask, st.scale, st.threshold, st.opacity16, st.alpha = mask, float(scale), self.threshold, self.opacity16, _lib.SP_HEAT_ALPHAS[alpha]
+        self._style = st
+        self._lut_dev = {}
+
+    def key(self) -> tuple:
+        """Everything the launches depend on: two overlays with equal keys write the same pixels.  (A captured graph also holds the
+        pointer of one overlay's uploaded table, so an estimator adds the overlay's identity to its own key.)"""
+        return (self.lut.tobytes(), self.opacity16, self.alpha, self.threshold, float(self.scale), self.joint_mask)
+
+    def table(self, device) -> torch.Tensor:
+        """The colour table on `device`, uploaded with the first call (never inside a capture: an estimator's frame asks for it ahead)."""
+        dev = torch.device(device)
+        if dev.type == "cuda" and dev.index is None:
+            dev = torch.device("cuda", torch.cuda.current_device())
+        t = self._lut_dev.get(dev)
+        if t is None:
+            t = self._lut_dev[dev] = torch.from_numpy(self.lut).to(dev)
+        return t
+
+    @staticmethod
+    def workspace(rows: int, hm_h: int, hm_w: int, device) -> torch.Tensor:
+        """The records and the u8 planes of `rows` person slots with hm_h x hm_w maps."""
+        n = ctypes.c_int64()
+        _lib.check(_lib.lib().sp_heat_overlay_workspace_bytes(rows, hm_h, hm_w, ctypes.byref(n)), "sp_heat_overlay_workspace_bytes")
+        return torch.zeros((max(int(n.value), 8),), dtype=torch.uint8, device=device)
+
+    def launch(self, src, dst, hm, trans_inv, keep, keep_count, seg, image: int, rows: int, workspace) -> None:
+        """sp_heat_overlay_u8c3 on the current stream of src's device; every argument a CUDA tensor (hm: contiguous fp32 [>= rows, J, h, w]).
+        `dst` may be `src` (in place)."""
+        h, w = int(src.shape[0]), int(src.shape[1])
+        if rows > 0 and not (hm.is_cuda and hm.dtype == torch.float32 and hm.dim() == 4 and hm.is_contiguous() and hm.shape[0] >= rows):
+            raise ValueError(f"heat maps: expected contiguous CUDA float32 [>= {rows}, J, h, w], got {hm.dtype} {tuple(hm.shape)}")
+        J, mh, mw = (int(v) for v in hm.shape[1:]) if rows > 0 else (1, 1, 1)
+        _lib.check(_lib.lib().sp_heat_overlay_u8c3(P(src), P(dst), h, w, P(hm) if rows > 0 else None, J, mh, mw, P(trans_inv), P(keep),
+                                                   P(keep_count), P(seg), image, rows, ctypes.byref(self._style),
+                                                   P(self.table(src.device)), P(workspace), _lib.current_stream(src.device)),
+                   "sp_heat_overlay_u8c3")
+
+    @torch.no_grad()
+    def overlay(self, img, heat_maps, trans_inv, out=None) -> torch.Tensor:
+        """`img`: uint8 BGR [H, W, 3], numpy or CUDA; `heat_maps`: CUDA float32 [n, J <= 64, h, w] (h, w <= 256); `trans_inv`: CUDA
+        float32 [n, 2, 3], heat-map px -> image px.  Every row is drawn.  Returns a CUDA uint8 [H, W, 3]: `out` when given (contiguous;
+        it may be `img` itself when that is a contiguous CUDA tensor, drawn in place), a new tensor otherwise."""
+        img, out = _image_and_out(img, out)
+        for name, t in (("heat_maps", heat_maps), ("trans_inv", trans_inv)):
+            if not isinstance(t, torch.Tensor):
+                raise TypeError(f"{name}: expected a CUDA float32 tensor, got {type(t).__name__}")
+            if not t.is_cuda or t.device != img.device:
+                raise HipLibraryError(f"{name} is on {t.device}, the image on {img.device}; simple_pose_amd runs on the MI355X only (no CPU fallback)")
+            if t.dtype != torch.float32:
+                raise TypeError(f"{name}: expected float32, got {t.dtype}")
+        if heat_maps.dim() != 4:
+            raise ValueError(f"heat_maps: expected [n, J, h, w], got {tuple(heat_maps.shape)}")
+        n, J, mh, mw = (int(v) for v in heat_maps.shape)
+        if n > 2048 or not (1 <= J <= 64) or not (1 <= mh <= _lib.SP_HEAT_MAX_MAP and 1 <= mw <= _lib.SP_HEAT_MAX_MAP):
+            raise ValueError(f"heat_maps: expected [n <= 2048, J <= 64, h <= {_lib.SP_HEAT_MAX_MAP}, w <= {_lib.SP_HEAT_MAX_MAP}], got {tuple(heat_maps.shape)}")
+        if tuple(trans_inv.shape) != (n, 2, 3):
+            raise ValueError(f"trans_inv: expected [{n}, 2, 3], got {tuple(trans_inv.shape)}")
+        if n == 0:
+            if out.data_ptr() != img.data_ptr():
+                out.copy_(img)
+            return out
+        dev = img.device
+        keep = torch.arange(n, dtype=torch.int32, device=dev)
+        keep_count = torch.full((1,), n, dtype=torch.int32, device=dev)
+        seg = torch.tensor([0, n], dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            self.launch(img, out, heat_maps.contiguous(), trans_inv.contiguous(), keep, keep_count, seg, 0, n, self.workspace(n, mh, mw, dev))
         return out
