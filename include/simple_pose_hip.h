@@ -124,6 +124,22 @@ int sp_conv2d_fwd(const sp_conv_desc* desc, const void* x, const void* w_packed,
  * SP_CONV_TAP_SKIP=0 is the same switch read once, at the first launch.  Default: on. */
 int sp_conv_set_tap_skip(int on);
 
+/* Single LDS stage (an addition to ABI 36).  An fp32 inference launch of sp_conv2d_fwd on the implicit-GEMM kernel at tile 128x128 that would take
+ * the plain instantiation (whole K tiles per tap: c_in % 32 == 0, at most 32 taps; no groups) or the tap-skipping one keeps ONE operand stage in
+ * LDS instead of two (conv_igemm_single_kernel / conv_igemm_tapskip_single_kernel): 34,816 bytes instead of 67,584, so three workgroups are
+ * resident per CU instead of two and a launch of 3 x CUs workgroups is one round, at the price of a second barrier per K tile.  Same MFMA
+ * sequence per accumulator, same epilogue operations: same bits, no precondition.  The rule holds for every workgroup and K-tile count.
+ * sp_conv_set_single_stage(0) keeps the double-buffered kernels for every later launch of the process, sp_conv_set_single_stage(1) turns the
+ * form back on; the environment variable SP_CONV_SINGLE_STAGE=0 is the same switch read once, at the first launch.  Default: on.
+ * sp_conv2d_kernel_name answers with the same strings whatever the knob says; sp_conv2d_single_stage returns 1 when a launch of `desc` would
+ * take a single-stage kernel under the current knob, 0 when not (or when `desc` is invalid: sp_last_error).
+ * sp_conv_igemm_resident_workgroups: the workgroups of a 128x128 kernel one CU holds at the LDS size its launcher passes (which: 0 = plain
+ * double-buffered, 1 = tap-skipping double-buffered, 2 = plain single-stage, 3 = tap-skipping single-stage).  workgroups NULL: only the byte count
+ * (no GPU needed). */
+int sp_conv_set_single_stage(int on);
+int sp_conv2d_single_stage(const sp_conv_desc* desc, int has_residual);
+int sp_conv_igemm_resident_workgroups(int which, int* workgroups, int* lds_bytes);
+
 /* Direct (non-im2col) 3x3 stride-1 pad-1 convolution for 32 -> 32 and 64 -> 64 channels in bf16 (HRNet's two high-resolution branches,
  * nets/pose_hrnet.py BasicBlock; ResNet-50 layer1.*.conv2): the halo tile of an 8x16 / 16x8 output tile goes through LDS once instead of
  * once per tap; the filter stays in registers (32 channels) or in LDS in MFMA-fragment order (64 channels) for a persistent workgroup.  Same arguments and bit-identical results as sp_conv2d_fwd for

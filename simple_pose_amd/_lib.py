@@ -182,6 +182,9 @@ SYMBOLS = {
     "sp_nchw_to_nhwc4": (c_int, [_P, _P, c_int, c_int, c_int, c_int, _P]),
     "sp_conv2d_fwd": (c_int, [ctypes.POINTER(ConvDesc), _P, _P, _P, _P, _P, _P, _P]),
     "sp_conv_set_tap_skip": (c_int, [c_int]),
+    "sp_conv_set_single_stage": (c_int, [c_int]),
+    "sp_conv2d_single_stage": (c_int, [ctypes.POINTER(ConvDesc), c_int]),
+    "sp_conv_igemm_resident_workgroups": (c_int, [c_int, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
     "sp_conv2d_ring_ok": (c_int, [ctypes.POINTER(ConvDesc)]),
     "sp_conv2d_kernel_name": (c_int, [ctypes.POINTER(ConvDesc), c_int, c_int, ctypes.c_char_p, c_int]),
     "sp_conv2d_default_tile": (c_int, [ctypes.POINTER(ConvDesc), ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
@@ -384,6 +387,11 @@ def conv_kernel_name(desc, has_residual: bool = False, variant: int = 0) -> str:
     buf = ctypes.create_string_buffer(256)
     check(lib().sp_conv2d_kernel_name(desc, int(has_residual), variant, buf, 256), "sp_conv2d_kernel_name")
     return buf.value.decode()
+
+
+def conv_single_stage(desc, has_residual: bool = False) -> bool:
+    """True when a launch of `desc` would take a single-stage implicit-GEMM kernel under the current knob (sp_conv2d_single_stage)."""
+    return bool(lib().sp_conv2d_single_stage(desc, int(has_residual)))
 
 
 def check(rc: int, what: str = ""):

@@ -26,6 +26,13 @@
 // Pipeline: register-staged double buffer (issue global loads of tile t+1, run the 64 MFMAs of tile t,
 // then ds_write t+1, one barrier per tile).  A tile's MFMA work is >= 2048 cycles per wave, so HBM/L2
 // latency hides behind it at 2 workgroups per CU.
+//
+// SINGLE (conv_igemm_single_kernel / conv_igemm_tapskip_single_kernel; the plain fp32 inference launches at tile 128x128 when
+// sp_conv_set_single_stage is on): ONE LDS operand stage instead of two, 34,816 bytes instead of 67,584, so three workgroups are resident
+// per CU instead of two (3 x 256 CUs = 768: the 768-workgroup launches no longer end in a half round at one wave per SIMD).  Same loop, same
+// MFMA order: a tile's fragments are all in registers by the start of step 3, a first barrier there says so for every wave, the ds_writes of
+// tile t+1 then go into the SAME buffer, and the existing barrier publishes them: two barriers per K tile.  The NHWC epilogue transposes
+// 32 accumulator rows at a time through a wave-private 8 KB slice.  Bit-identical to the double-buffered kernels.
 #include "sp_common.h"
 #include <stdlib.h>
 #include <type_traits>
@@ -142,10 +149,13 @@ __device__ __forceinline__ float abn_elem(float v, float mu, float is, float g, 
 // of the tile, in ascending k: a skipped tile only ever added fma(+-0, w, acc) terms (the out-of-image load returns +0), which leave every bit
 // of an accumulator that started at +0 unchanged as long as w is finite - the precondition of the path.  Tiles differ in length (9 / 6 / 4 of
 // 9 taps), so positions are handed out longest first: interior before edges before corners, dealt round-robin over the eight XCD chunks.
-template <int BM, int BN, int WR, int WC, bool UNIFORM_TAP, bool BF16, bool OUT16, bool STATS, bool DEEP, bool BSTATS, bool ABN, bool SKIP = false>
+template <int BM, int BN, int WR, int WC, bool UNIFORM_TAP, bool BF16, bool OUT16, bool STATS, bool DEEP, bool BSTATS, bool ABN, bool SKIP = false,
+          bool SINGLE = false>
 __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     static_assert(!ABN || (UNIFORM_TAP && BF16 && OUT16 && STATS && !DEEP && !BSTATS), "ABN: the bf16 train-mode forward of a 1x1 conv");
     static_assert(!SKIP || (UNIFORM_TAP && !BF16 && !OUT16 && !STATS && !DEEP && !BSTATS && !ABN), "SKIP: the plain fp32 inference instantiation");
+    static_assert(!SINGLE || (UNIFORM_TAP && !BF16 && !OUT16 && !STATS && !DEEP && !BSTATS && !ABN), "SINGLE: the plain fp32 inference instantiation");
+    constexpr int NBUF = SINGLE ? 1 : 2; // LDS operand stages
     constexpr int ES = BF16 ? 2 : 4;     // element size of activations / weights
     constexpr int EPC = 16 / ES;         // elements per 16-byte chunk
     constexpr int BKE = 128 / ES;        // elements per K tile (one 128-byte LDS row)
@@ -165,9 +175,9 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     asm volatile("s_memrealtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(rt_entry)::"memory");
 #endif
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* As = smem;                    // [2][BM][32]
-    float* Bs = smem + 2 * BM * BK;      // [2][BN][32]
-    int* rowtab = reinterpret_cast<int*>(smem + 2 * (BM + BN) * BK);  // [BM][4]: in_base, iy0, ix0, out_off
+    float* As = smem;                    // [NBUF][BM][32]
+    float* Bs = smem + NBUF * BM * BK;   // [NBUF][BN][32]
+    int* rowtab = reinterpret_cast<int*>(smem + NBUF * (BM + BN) * BK);  // [BM][4]: in_base, iy0, ix0, out_off
 
     const int tid = threadIdx.x;
     const int lane = tid & 63;
@@ -473,16 +483,18 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     //           s_barrier; the first fragments of tile kt+1 are requested and the second half of step 3's MFMAs covers
     //           their LDS latency.  All reads of the current buffer were issued (into registers) before step 2's MFMAs,
     //           so the barrier also frees the current buffer for tile kt+2.
+    //   SINGLE: one buffer.  Step 3 opens with a barrier of its own (every wave holds all its fragments of tile kt), the ds_writes of
+    //           tile kt+1 then overwrite tile kt, and the barrier above publishes them.
 #ifdef SP_DIAG
     unsigned long long dg[8] = {0, 0, 0, 0, 0, 0, 0, 0};
 #endif
     auto k_tile = [&](int kt, auto more_tag) {
         constexpr bool MORE = decltype(more_tag)::value;
-        const int cur = kt & 1;
+        const int cur = SINGLE ? 0 : kt & 1, nxt = SINGLE ? 0 : cur ^ 1;
         const float* a = As + cur * BM * BK + (wr * WM) * BK;
         const float* b = Bs + cur * BN * BK + (wc * WN) * BK;
-        const float* an = As + (cur ^ 1) * BM * BK + (wr * WM) * BK;
-        const float* bn = Bs + (cur ^ 1) * BN * BK + (wc * WN) * BK;
+        const float* an = As + nxt * BM * BK + (wr * WM) * BK;
+        const float* bn = Bs + nxt * BN * BK + (wc * WN) * BK;
         // ---- step 0 (slot 0) ----
         SP_STAMP(s0)
         read_frags(a, b, 1, 1);
@@ -512,13 +524,16 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
         for (int q = 0; q < NM; ++q) mfma_q(0, q);
         SP_SB();
         SP_STAMP(s3)
+        if constexpr (SINGLE) {
+            if (MORE) __syncthreads();       // every wave has read its last fragments of tile kt: the buffer is free for tile kt+1
+        }
         SP_STAMP(s3w)
         // ---- step 3 (slot 1), first half + the ds_writes ----
         constexpr int H3 = NM / 2;   // MFMAs of step 3 issued before the barrier (0 for the single-MFMA bf16 64x64 tile)
         if constexpr (H3 == 0) {
             if (MORE) {
 #pragma unroll
-                for (int o = 0; o < NOPS; ++o) store_piece(cur ^ 1, o, I0{});
+                for (int o = 0; o < NOPS; ++o) store_piece(nxt, o, I0{});
             }
         } else {
 #pragma unroll
@@ -526,7 +541,7 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
                 mfma_q(1, q);
                 if (MORE) {
 #pragma unroll
-                    for (int o = (q * NOPS) / H3; o < ((q + 1) * NOPS) / H3; ++o) store_piece(cur ^ 1, o, I0{});
+                    for (int o = (q * NOPS) / H3; o < ((q + 1) * NOPS) / H3; ++o) store_piece(nxt, o, I0{});
                 }
                 SP_SB();
             }
@@ -659,15 +674,20 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
     const __amdgpu_buffer_rsrc_t yr = __builtin_amdgcn_make_buffer_rsrc(p.y, (short)0, p.y_bytes, 0x00020000);
     const __amdgpu_buffer_rsrc_t rr = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p.res ? p.res : p.y), (short)0, p.y_bytes, 0x00020000);
     if (!nchw && (p.c_out % (16 / ESO)) == 0) {
-        static_assert(BM * BN <= 2 * (BM + BN) * BK, "transpose area must fit in the staging buffers");
-        float* tr = smem + wave * (WM * WN);
+        // SINGLE: the one operand stage holds a quarter of the tile per wave, so the transpose goes 32 accumulator rows (one i of TM) at a
+        // time through a wave-private slice of 32 x WN floats: written, read back and stored before the next i overwrites it.  No workgroup
+        // barrier: the slice belongs to one wave, whose LDS operations complete in order.
+        static_assert(SINGLE ? BM * BN / TM <= (BM + BN) * BK : BM * BN <= 2 * (BM + BN) * BK, "transpose area must fit in the staging buffers");
+        float* tr = smem + wave * (SINGLE ? 32 * WN : WM * WN);
+        if constexpr (!SINGLE) {
 #pragma unroll
-        for (int i = 0; i < TM; ++i)
+            for (int i = 0; i < TM; ++i)
 #pragma unroll
-            for (int n = 0; n < TN; ++n)
+                for (int n = 0; n < TN; ++n)
 #pragma unroll
-                for (int r = 0; r < 16; ++r)
-                    tr[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * WN + n * 32 + fr] = acc[i][n][r];
+                    for (int r = 0; r < 16; ++r)
+                        tr[(i * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh) * WN + n * 32 + fr] = acc[i][n][r];
+        }
         constexpr int CPL = 16 / ESO;    // channels per lane = one 16-byte store (4 fp32 / 8 bf16)
         constexpr int CPR = WN / CPL;    // 16-byte output chunks per tile row
         constexpr int RPI = 64 / CPR;    // tile rows covered by one wave-instruction
@@ -734,9 +754,22 @@ __device__ __forceinline__ void conv_igemm_body(const ConvArgs& p) {
 #pragma unroll
         for (int it = 0; it < NIT; ++it) {
             float v[CPL];
+            if constexpr (SINGLE) {
+                static_assert(32 % RPI == 0, "a wave-instruction stays inside one 32-row group");
+                if ((it * RPI) % 32 == 0) {
+                    __builtin_amdgcn_wave_barrier();      // (compiler only: the reads of the previous group stay ahead of these writes)
+#pragma unroll
+                    for (int n = 0; n < TN; ++n)
+#pragma unroll
+                        for (int r = 0; r < 16; ++r)
+                            tr[((r & 3) + 8 * (r >> 2) + 4 * fh) * WN + n * 32 + fr] = acc[(it * RPI) / 32][n][r];
+                    __builtin_amdgcn_wave_barrier();
+                }
+            }
 #pragma unroll
             for (int e4 = 0; e4 < CPL / 4; ++e4) {
-                const f32x4 t = *reinterpret_cast<const f32x4*>(tr + (it * RPI + rsub) * WN + chunk * CPL + 4 * e4);
+                const f32x4 t = SINGLE ? *reinterpret_cast<const f32x4*>(tr + ((it * RPI) % 32 + rsub) * WN + chunk * CPL + 4 * e4)
+                                       : *reinterpret_cast<const f32x4*>(tr + (it * RPI + rsub) * WN + chunk * CPL + 4 * e4);
                 v[4 * e4] = t[0]; v[4 * e4 + 1] = t[1]; v[4 * e4 + 2] = t[2]; v[4 * e4 + 3] = t[3];
             }
 #pragma unroll
@@ -973,6 +1006,17 @@ __global__ __launch_bounds__(256, (BM * BN > 128 * 128) ? 1 : 2) void conv_igemm
     conv_igemm_body<BM, BN, WR, WC, true, false, false, false, false, false, false, true>(p);
 }
 
+// SINGLE: one LDS operand stage, three workgroups per CU (kernels of their own names; the 128x128 tile only)
+template <int BM, int BN, int WR, int WC>
+__global__ __launch_bounds__(256, 3) void conv_igemm_single_kernel(const ConvArgs p) {
+    conv_igemm_body<BM, BN, WR, WC, true, false, false, false, false, false, false, false, true>(p);
+}
+
+template <int BM, int BN, int WR, int WC>
+__global__ __launch_bounds__(256, 3) void conv_igemm_tapskip_single_kernel(const ConvArgs p) {
+    conv_igemm_body<BM, BN, WR, WC, true, false, false, false, false, false, false, true, true>(p);
+}
+
 template <int BM, int BN, int WR, int WC, bool BF16, bool OUT16, bool STATS, bool DEEP = false, bool BSTATS = false>
 int launch_t(const ConvArgs& a, int phases, bool uniform, hipStream_t stream) {
     if constexpr (!DEEP && BF16) {
@@ -1047,11 +1091,55 @@ int launch_tapskip(const ConvArgs& a, int phases, hipStream_t stream) {
     return sp_check_launch("conv_igemm_tapskip_kernel");
 }
 
+// SP_CONV_SINGLE_STAGE=0 (or sp_conv_set_single_stage(0)): every 128x128 launch keeps the double-buffered kernels - same-box A/Bs
+int g_single_stage = -1;                                 // -1: not decided yet (the environment is read at the first launch)
+thread_local int g_single_taken = 0;                     // name query (per thread, as its state in capi.hip): the launch resolved to a SINGLE kernel (sp_conv2d_single_stage)
+bool single_stage_enabled() {
+    if (g_single_stage < 0) { const char* e = getenv("SP_CONV_SINGLE_STAGE"); g_single_stage = (e && atoi(e) == 0) ? 0 : 1; }
+    return g_single_stage != 0;
+}
+
+// the single-stage forms of the plain fp32 inference kernel (SKIP false) and of the tap-skipping one (SKIP true); a name query answers
+// with the name of the double-buffered kernel it stands in for: the strings of sp_conv2d_kernel_name do not depend on the knob
+template <int BM, int BN, int WR, int WC, bool SKIP>
+int launch_single(const ConvArgs& a, int phases, hipStream_t stream) {
+    if (sp_name_query_active()) {
+        g_single_taken = 1;
+        if (SKIP) sp_name_query_set("conv_igemm_tapskip_kernel<%d, %d, %d, %d>", BM, BN, WR, WC);
+        else sp_name_query_set("conv_igemm_kernel<%d, %d, %d, %d, true, false, false, false, false, false>", BM, BN, WR, WC);
+        return SP_OK;
+    }
+    ConvArgs p = a;
+    p.tiles_m = (a.M + BM - 1) / BM;
+    p.tiles_n = a.n_pad / BN;
+    const size_t lds = (size_t)(BM + BN) * BK * sizeof(float) + (size_t)BM * 4 * sizeof(int);
+    const dim3 grid(p.tiles_m * p.tiles_n, phases, 1), block(256, 1, 1);
+    if constexpr (SKIP) {
+        if (sp_reserve_lds<&conv_igemm_tapskip_single_kernel<BM, BN, WR, WC>>((int)lds, "conv_igemm_tapskip_single")) return SP_ELAUNCH;
+        hipLaunchKernelGGL((conv_igemm_tapskip_single_kernel<BM, BN, WR, WC>), grid, block, lds, stream, p);
+        return sp_check_launch("conv_igemm_tapskip_single_kernel");
+    } else {
+        if (sp_reserve_lds<&conv_igemm_single_kernel<BM, BN, WR, WC>>((int)lds, "conv_igemm_single")) return SP_ELAUNCH;
+        hipLaunchKernelGGL((conv_igemm_single_kernel<BM, BN, WR, WC>), grid, block, lds, stream, p);
+        return sp_check_launch("conv_igemm_single_kernel");
+    }
+}
+
 // tap_skip: the launch passed every tile-independent test of conv_fwd_impl (see there); what is left is the tile's own: at least half a
-// tile of images per output position, so that a tile spans at most three positions
+// tile of images per output position, so that a tile spans at most three positions.
+// Single stage: a launch that would take the tap-skipping kernel or the plain fp32 inference instantiation (uniform taps, no groups, no
+// per-phase geometry) at tile 128x128 takes its SINGLE form when the knob is on.  Grouped launches and the per-phase-geometry launches of the
+// training dgrad compile to the same plain instantiation but stay on the double-buffered kernel: no measured launch and no bitwise test
+// of this change covers them (the headline has neither), so the rule does not claim them.
 template <int BM, int BN, int WR, int WC>
 int launch(const ConvArgs& a, int phases, bool uniform, bool tap_skip, hipStream_t stream) {
-    if (tap_skip && a.batch >= BM / 2) return launch_tapskip<BM, BN, WR, WC>(a, phases, stream);
+    constexpr bool HAS_SINGLE = BM == 128 && BN == 128;
+    if (tap_skip && a.batch >= BM / 2) {
+        if constexpr (HAS_SINGLE) {
+            if (single_stage_enabled()) return launch_single<BM, BN, WR, WC, true>(a, phases, stream);
+        }
+        return launch_tapskip<BM, BN, WR, WC>(a, phases, stream);
+    }
     if (a.abn_mean) return launch_abn<BM, BN, WR, WC>(a, stream);
     if (a.bz) {                                        // dgrad launch that also reduces the BN backward sums of the tensor it writes
         if ((a.flags & SP_CONV_BF16) && !(a.flags & SP_CONV_OUT_F32)) return launch_t<BM, BN, WR, WC, true, true, false, false, true>(a, phases, uniform, stream);
@@ -1065,6 +1153,9 @@ int launch(const ConvArgs& a, int phases, bool uniform, bool tap_skip, hipStream
     if (a.flags & SP_CONV_BF16) {
         if (a.flags & SP_CONV_OUT_F32) return launch_t<BM, BN, WR, WC, true, false, false>(a, phases, uniform, stream);
         return launch_t<BM, BN, WR, WC, true, true, false>(a, phases, uniform, stream);
+    }
+    if constexpr (HAS_SINGLE) {
+        if (uniform && !a.c_in_g && !a.ph_n && single_stage_enabled()) return launch_single<BM, BN, WR, WC, false>(a, phases, stream);
     }
     return launch_t<BM, BN, WR, WC, false, false, false>(a, phases, uniform, stream);
 }
@@ -1087,6 +1178,11 @@ static bool tap_skip_enabled() {
 }
 extern "C" int sp_conv_set_tap_skip(int on) {
     g_tap_skip = on ? 1 : 0;
+    return SP_OK;
+}
+
+extern "C" int sp_conv_set_single_stage(int on) {
+    g_single_stage = on ? 1 : 0;
     return SP_OK;
 }
 
@@ -1309,6 +1405,49 @@ extern "C" int sp_conv2d_kernel_name(const sp_conv_desc* d, int has_residual, in
     const char* name = sp_name_query_end();
     if (rc != SP_OK) return rc;
     snprintf(buf, (size_t)cap, "%s", name);
+    return SP_OK;
+}
+
+// 1: a launch of `d` through sp_conv2d_fwd would take a single-stage kernel under the current knob; 0: it would not (or `d` is invalid:
+// sp_last_error says why).  Nothing is launched.
+extern "C" int sp_conv2d_single_stage(const sp_conv_desc* d, int has_residual) {
+    if (!d) { sp_set_error("sp_conv2d_single_stage: null pointer"); return 0; }
+    void* const dummy = reinterpret_cast<void*>(16);
+    sp_name_query_begin();
+    g_single_taken = 0;
+    const int rc = conv_fwd_impl(d, dummy, dummy, nullptr, nullptr, has_residual ? dummy : nullptr, dummy, nullptr, nullptr, 0, nullptr);
+    sp_name_query_end();
+    const int taken = g_single_taken;
+    g_single_taken = 0;
+    return rc == SP_OK ? taken : 0;
+}
+
+// Workgroups of a 128x128 fp32 inference kernel that fit one CU at the dynamic LDS size its launcher passes
+// (hipOccupancyMaxActiveBlocksPerMultiprocessor).  which: 0 = conv_igemm_kernel (uniform taps), 1 = conv_igemm_tapskip_kernel, 2 =
+// conv_igemm_single_kernel, 3 = conv_igemm_tapskip_single_kernel.  Three resident workgroups are the point of the single-stage kernels.
+extern "C" int sp_conv_igemm_resident_workgroups(int which, int* workgroups, int* lds_bytes) {
+    SP_REQUIRE(lds_bytes && which >= 0 && which <= 3, "sp_conv_igemm_resident_workgroups: which = 0..3 and a result pointer");
+    const int rowtab = 128 * 4 * (int)sizeof(int);
+    const int lds = (which >= 2 ? 1 : 2) * (128 + 128) * BK * (int)sizeof(float) + rowtab;
+    *lds_bytes = lds;
+    if (!workgroups) return SP_OK;                       // the byte count alone: no GPU needed
+    const void* f = nullptr;
+    int rc = SP_OK;
+    switch (which) {
+        case 0: f = reinterpret_cast<const void*>(&conv_igemm_kernel<128, 128, 2, 2, true, false, false, false, false, false>);
+                rc = sp_reserve_lds<&conv_igemm_kernel<128, 128, 2, 2, true, false, false, false, false, false>>(lds, "conv_igemm"); break;
+        case 1: f = reinterpret_cast<const void*>(&conv_igemm_tapskip_kernel<128, 128, 2, 2>);
+                rc = sp_reserve_lds<&conv_igemm_tapskip_kernel<128, 128, 2, 2>>(lds, "conv_igemm_tapskip"); break;
+        case 2: f = reinterpret_cast<const void*>(&conv_igemm_single_kernel<128, 128, 2, 2>);
+                rc = sp_reserve_lds<&conv_igemm_single_kernel<128, 128, 2, 2>>(lds, "conv_igemm_single"); break;
+        default: f = reinterpret_cast<const void*>(&conv_igemm_tapskip_single_kernel<128, 128, 2, 2>);
+                rc = sp_reserve_lds<&conv_igemm_tapskip_single_kernel<128, 128, 2, 2>>(lds, "conv_igemm_tapskip_single"); break;
+    }
+    if (rc) return SP_ELAUNCH;
+    int n = 0;
+    const hipError_t e = hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, f, 256, (size_t)lds);
+    if (e != hipSuccess) { sp_set_error("sp_conv_igemm_resident_workgroups: %s", hipGetErrorString(e)); return SP_ELAUNCH; }
+    *workgroups = n;
     return SP_OK;
 }
 
