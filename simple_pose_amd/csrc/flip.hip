@@ -13,7 +13,7 @@
 
 namespace {
 
-constexpr int FLIP_MAX_JOINTS = 64;
+constexpr int FLIP_MAX_JOINTS = SP_MAX_JOINTS;
 
 struct FlipPerm { unsigned char p[FLIP_MAX_JOINTS]; };
 struct u32x3 { unsigned a, b, c; };                      // four uint8x3 pixels (4-byte aligned)
@@ -109,13 +109,6 @@ __global__ __launch_bounds__(256) void flip_merge_x4_kernel(const f32x4* hm, con
     }
 }
 
-inline bool ranges_overlap(const void* a, const void* b, unsigned long long bytes) {
-    const unsigned long long pa = (unsigned long long)(uintptr_t)a, pb = (unsigned long long)(uintptr_t)b;
-    return pa < pb + bytes && pb < pa + bytes;
-}
-
-inline bool aligned_to(const void* p, unsigned n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 }  // namespace
 
 extern "C" int sp_mirror_w(const void* src, void* dst, int64_t rows, int w, int elem_bytes, void* stream) {
@@ -125,10 +118,10 @@ extern "C" int sp_mirror_w(const void* src, void* dst, int64_t rows, int w, int 
     if (rows == 0) return SP_OK;
     const long long total = (long long)rows * w;
     SP_REQUIRE(total < (1ll << 40), "sp_mirror_w: %lld elements (tensor too large)", total);
-    SP_REQUIRE(!ranges_overlap(src, dst, (unsigned long long)total * elem_bytes),
+    SP_REQUIRE(!sp_ranges_overlap(src, dst, (unsigned long long)total * elem_bytes),
                "sp_mirror_w: src and dst overlap (out of place only; dst may be the second half of src's allocation)");
     const hipStream_t s = (hipStream_t)stream;
-    const bool wide = w % 4 == 0 && aligned_to(src, elem_bytes == 4 ? 16 : 4) && aligned_to(dst, elem_bytes == 4 ? 16 : 4);
+    const bool wide = w % 4 == 0 && sp_aligned_to(src, elem_bytes == 4 ? 16 : 4) && sp_aligned_to(dst, elem_bytes == 4 ? 16 : 4);
     const bool small = total < (1ll << 31);                   // 32-bit index arithmetic in the kernel
 #define SP_MIRROR_LAUNCH(kernel, n, ...)                                                                                        \
     do {                                                                                                                        \
@@ -146,7 +139,7 @@ extern "C" int sp_mirror_w(const void* src, void* dst, int64_t rows, int w, int 
     const unsigned char* sb = static_cast<const unsigned char*>(src);
     unsigned char* db = static_cast<unsigned char*>(dst);
     if (elem_bytes == 4) {
-        SP_REQUIRE(aligned_to(src, 4) && aligned_to(dst, 4), "sp_mirror_w: fp32 pointers must be 4-byte aligned");
+        SP_REQUIRE(sp_aligned_to(src, 4) && sp_aligned_to(dst, 4), "sp_mirror_w: fp32 pointers must be 4-byte aligned");
         if (small) hipLaunchKernelGGL((mirror_w_kernel<4, unsigned>), dim3(sp_grid_for(total, 256)), dim3(256), 0, s, sb, db, w, (unsigned)total);
         else hipLaunchKernelGGL((mirror_w_kernel<4, long long>), dim3(sp_grid_for(total, 256)), dim3(256), 0, s, sb, db, w, total);
     } else {
@@ -176,11 +169,11 @@ extern "C" int sp_heat_map_flip_merge(const float* hm, const float* hm_flipped, 
     for (int j = joints; j < FLIP_MAX_JOINTS; ++j) perm.p[j] = 0;
     if (total == 0) return SP_OK;
     const unsigned long long bytes = (unsigned long long)total * 4;
-    SP_REQUIRE(!ranges_overlap(out, hm_flipped, bytes), "sp_heat_map_flip_merge: out overlaps hm_flipped (in place only on hm)");
-    SP_REQUIRE(out == hm || !ranges_overlap(out, hm, bytes), "sp_heat_map_flip_merge: out overlaps hm without being hm");
-    SP_REQUIRE(aligned_to(hm, 4) && aligned_to(hm_flipped, 4) && aligned_to(out, 4), "sp_heat_map_flip_merge: pointers must be 4-byte aligned");
+    SP_REQUIRE(!sp_ranges_overlap(out, hm_flipped, bytes), "sp_heat_map_flip_merge: out overlaps hm_flipped (in place only on hm)");
+    SP_REQUIRE(out == hm || !sp_ranges_overlap(out, hm, bytes), "sp_heat_map_flip_merge: out overlaps hm without being hm");
+    SP_REQUIRE(sp_aligned_to(hm, 4) && sp_aligned_to(hm_flipped, 4) && sp_aligned_to(out, 4), "sp_heat_map_flip_merge: pointers must be 4-byte aligned");
     const hipStream_t s = (hipStream_t)stream;
-    if (w % 4 == 0 && aligned_to(hm, 16) && aligned_to(hm_flipped, 16) && aligned_to(out, 16)) {
+    if (w % 4 == 0 && sp_aligned_to(hm, 16) && sp_aligned_to(hm_flipped, 16) && sp_aligned_to(out, 16)) {
         hipLaunchKernelGGL(flip_merge_x4_kernel, dim3(sp_grid_for(total / 4, 256)), dim3(256), 0, s, reinterpret_cast<const f32x4*>(hm),
                            reinterpret_cast<const f32x4*>(hm_flipped), perm, joints, h, w / 4, shift ? 1 : 0, reinterpret_cast<f32x4*>(out),
                            (int)(total / 4));

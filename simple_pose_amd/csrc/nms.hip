@@ -10,7 +10,7 @@
 
 namespace {
 
-constexpr int NMS_MAX_GROUP = 2048;
+constexpr int NMS_MAX_GROUP = SP_MAX_ROWS;
 
 // eval.py:166-174: score = box_score * mean(kpt_scores[kpt_scores > in_vis_thre]) (0 without a visible joint); also widens the
 // fp32 decoder output to the float64 the reference's JSON round trip produces.

@@ -1,9 +1,12 @@
 // redact.hip - redaction on the device: the heads or the whole persons of one image (what sp_oks_nms leaves behind) hidden behind a mosaic
 // or a constant colour, so that a frame that is stored or forwarded stays one stream of launches (capturable with the rest of the frame)
 // and never visits the host on the way.  The reference has no such code; the rules live in sp_redact.h (shared with
-// tests/redact_core_main.cpp) and are restated for numpy in tests/redact_ref.py.  Integer arithmetic and sp_render_q: contraction OFF for
-// the whole file.
-#include "sp_common.h"
+// tests/redact_core_main.cpp) and are restated for numpy in tests/redact_ref.py; the box test, the limits and the entry point's
+// frame checks are sp_frame_tile.h's, shared with the other overlays.  The tile kernel keeps its own coordinates and packed pixel words
+// (its tile is 16 * RB rows high, RB row blocks per thread, and its scan fills a cell mask, no list): written on sp_tile and sp_px4 the
+// cell-4 mosaic measured 2 to 4 % slower in two sessions (docs/LAB_NOTES.md, section 14); as it stands the kernels compile to the
+// instructions they had before the header existed.  Integer arithmetic and sp_render_q: contraction OFF for the whole file.
+#include "sp_frame_tile.h"
 #include "sp_redact.h"
 
 #include <stdint.h>
@@ -12,19 +15,15 @@
 
 namespace {
 
-constexpr int RDC_NT = 256;
-constexpr int RDC_TILE_W = 64;                   // a tile is 64 x (16 * RB) pixels, RB = max(16, cell) / 16: a whole number of cells both ways
+constexpr int RDC_TILE_W = SP_TILE_W;            // a tile is 64 x (16 * RB) pixels, RB = max(16, cell) / 16: a whole number of cells both ways
 constexpr int RDC_MAX_CELLS = 64;                // cell 4: 16 x 4 cells per tile
-constexpr int RDC_MAX_ROWS = 2048;               // the OKS-NMS group limit
-constexpr int RDC_MAX_JOINTS = 64;
-constexpr int RDC_MAX_DIM = 16384;
 
 // One thread per person slot: dead slots are written as empty records, so the tile kernel needs no count.
-__global__ __launch_bounds__(RDC_NT) void redact_regions_kernel(const sp_redact_style st, int joints, int rows, int image,
+__global__ __launch_bounds__(SP_TILE_NT) void redact_regions_kernel(const sp_redact_style st, int joints, int rows, int image,
                                                                 const double* __restrict__ kps, const float* __restrict__ box,
                                                                 const int32_t* __restrict__ keep, const int32_t* __restrict__ keep_count,
                                                                 const int32_t* __restrict__ seg, sp_redact_rec* __restrict__ recs) {
-    const int i = blockIdx.x * RDC_NT + threadIdx.x;
+    const int i = blockIdx.x * SP_TILE_NT + threadIdx.x;
     if (i >= rows) return;
     recs[i] = sp_redact_region_at(st, joints, rows, image, kps, box, keep, keep_count, seg, i);
 }
@@ -37,7 +36,7 @@ __global__ __launch_bounds__(RDC_NT) void redact_regions_kernel(const sp_redact_
 //    by xor-shuffles over the lanes of the same cell, then one LDS atomic per wave and cell; 3 * cells threads turn the sums into means.
 // 3. write: the pixels of hit cells are replaced; in place only those are stored.
 template <bool WIDE, int RB>
-__global__ __launch_bounds__(RDC_NT) void redact_tile_kernel(const unsigned char* src, unsigned char* dst, int h, int w,
+__global__ __launch_bounds__(SP_TILE_NT) void redact_tile_kernel(const unsigned char* src, unsigned char* dst, int h, int w,
                                                              const sp_redact_rec* __restrict__ recs, int total, int lc, int mode,
                                                              uint32_t fill) {
     __shared__ unsigned int mask[2];
@@ -48,14 +47,14 @@ __global__ __launch_bounds__(RDC_NT) void redact_tile_kernel(const unsigned char
     const int tx1 = min(tx0 + RDC_TILE_W, w) - 1, ty1 = min(ty0 + 16 * RB, h) - 1;      // the tile's last pixels inside the image
     const bool in_place = dst == src;
     if (tid < 2) mask[tid] = 0u;
-    for (int i = tid; i < RDC_MAX_CELLS * 3; i += RDC_NT) sums[i] = 0u;
+    for (int i = tid; i < RDC_MAX_CELLS * 3; i += SP_TILE_NT) sums[i] = 0u;
     __syncthreads();
     // ---- 1. which cells are hit -------------------------------------------------------------------------------------------------------
-    for (int base = 0; base < total; base += RDC_NT) {
+    for (int base = 0; base < total; base += SP_TILE_NT) {
         const int i = base + tid;
         if (i >= total) break;
         const sp_redact_rec r = recs[i];
-        if (!(r.x0 <= tx1 && r.x1 >= tx0 && r.y0 <= ty1 && r.y1 >= ty0)) continue;                                 // (empty: x0 > x1)
+        if (!sp_box_meets(r, tx0, ty0, tx1, ty1)) continue;
         const int cx0 = (max(r.x0, tx0) - tx0) >> lc, cx1 = (min(r.x1, tx1) - tx0) >> lc;
         const int cy0 = (max(r.y0, ty0) - ty0) >> lc, cy1 = (min(r.y1, ty1) - ty0) >> lc;
         for (int cy = cy0; cy <= cy1; ++cy)
@@ -151,13 +150,6 @@ __global__ __launch_bounds__(RDC_NT) void redact_tile_kernel(const unsigned char
     }
 }
 
-bool ranges_overlap(const void* a, const void* b, unsigned long long bytes) {
-    const unsigned long long x = (unsigned long long)(uintptr_t)a, y = (unsigned long long)(uintptr_t)b;
-    return x < y + bytes && y < x + bytes;
-}
-
-bool aligned_to(const void* p, unsigned n) { return ((uintptr_t)p & (n - 1)) == 0; }
-
 template <bool WIDE>
 void launch_tiles(hipStream_t s, const unsigned char* src, unsigned char* dst, int h, int w, const sp_redact_rec* recs, int total,
                   const sp_redact_style& st) {
@@ -167,18 +159,19 @@ void launch_tiles(hipStream_t s, const unsigned char* src, unsigned char* dst, i
     const int rb = st.cell <= 16 ? 1 : st.cell / 16;
     const dim3 grid(sp_ceil_div(w, RDC_TILE_W), sp_ceil_div(h, 16 * rb));
     if (rb == 1)
-        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 1>), grid, dim3(RDC_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
+        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 1>), grid, dim3(SP_TILE_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
     else if (rb == 2)
-        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 2>), grid, dim3(RDC_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
+        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 2>), grid, dim3(SP_TILE_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
     else
-        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 4>), grid, dim3(RDC_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
+        hipLaunchKernelGGL((redact_tile_kernel<WIDE, 4>), grid, dim3(SP_TILE_NT), 0, s, src, dst, h, w, recs, total, lc, st.mode, fill);
 }
 
 }  // namespace
 
 extern "C" int sp_redact_workspace_bytes(int rows, int64_t* bytes) {
     SP_REQUIRE(bytes, "sp_redact_workspace_bytes: null pointer");
-    SP_REQUIRE(rows >= 0 && rows <= RDC_MAX_ROWS, "sp_redact_workspace_bytes: rows %d (0..%d, the OKS-NMS group limit)", rows, RDC_MAX_ROWS);
+    const int rc = sp_frame_rows_check("sp_redact_workspace_bytes", rows);
+    if (rc != SP_OK) return rc;
     *bytes = (int64_t)rows * (int64_t)sizeof(sp_redact_rec);
     return SP_OK;
 }
@@ -186,11 +179,10 @@ extern "C" int sp_redact_workspace_bytes(int rows, int64_t* bytes) {
 extern "C" int sp_redact_u8c3(const unsigned char* src, unsigned char* dst, int h, int w, const double* kps, const float* box,
                               const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int image, int rows, int joints,
                               const sp_redact_style* style_host, void* workspace, void* stream) {
-    SP_REQUIRE(src && dst && style_host, "sp_redact_u8c3: null pointer");
-    SP_REQUIRE(h >= 1 && h <= RDC_MAX_DIM && w >= 1 && w <= RDC_MAX_DIM, "sp_redact_u8c3: image %dx%d (1..%d each way)", w, h, RDC_MAX_DIM);
-    SP_REQUIRE(image >= 0, "sp_redact_u8c3: image index %d", image);
-    SP_REQUIRE(rows >= 0 && rows <= RDC_MAX_ROWS, "sp_redact_u8c3: rows %d (0..%d, the OKS-NMS group limit)", rows, RDC_MAX_ROWS);
-    SP_REQUIRE(joints >= 1 && joints <= RDC_MAX_JOINTS, "sp_redact_u8c3: joints %d (1..%d)", joints, RDC_MAX_JOINTS);
+    SP_REQUIRE(style_host, "sp_redact_u8c3: null pointer");
+    int rc = sp_frame_check("sp_redact_u8c3", src, dst, h, w, image, rows);
+    if (rc != SP_OK) return rc;
+    SP_REQUIRE(joints >= 1 && joints <= SP_MAX_JOINTS, "sp_redact_u8c3: joints %d (1..%d)", joints, SP_MAX_JOINTS);
     const sp_redact_style st = *style_host;
     SP_REQUIRE(st.region == SP_REDACT_HEAD || st.region == SP_REDACT_PERSON, "sp_redact_u8c3: region %d", st.region);
     SP_REQUIRE(st.mode == SP_REDACT_MOSAIC || st.mode == SP_REDACT_FILL, "sp_redact_u8c3: mode %d", st.mode);
@@ -205,22 +197,20 @@ extern "C" int sp_redact_u8c3(const unsigned char* src, unsigned char* dst, int 
         for (int i = 0; i < st.head_joints; ++i)
             SP_REQUIRE(st.head_joint[i] >= 0 && st.head_joint[i] < joints, "sp_redact_u8c3: head_joint[%d] = %d is no joint index (0..%d)", i,
                        st.head_joint[i], joints - 1);
-    const unsigned long long bytes = (unsigned long long)h * w * 3;
-    SP_REQUIRE(dst == src || !ranges_overlap(src, dst, bytes), "sp_redact_u8c3: src and dst overlap without being equal (in place, or apart)");
     if (rows == 0 && dst == src) return SP_OK;
     if (rows > 0) {
         SP_REQUIRE(kps && box && keep && keep_count && seg && workspace, "sp_redact_u8c3: null pointer");
-        SP_REQUIRE(aligned_to(workspace, 4) && aligned_to(kps, 8), "sp_redact_u8c3: workspace must be 4-byte, kps 8-byte aligned");
+        SP_REQUIRE(sp_aligned_to(workspace, 4) && sp_aligned_to(kps, 8), "sp_redact_u8c3: workspace must be 4-byte, kps 8-byte aligned");
     }
     const hipStream_t s = (hipStream_t)stream;
     sp_redact_rec* recs = reinterpret_cast<sp_redact_rec*>(workspace);
     if (rows > 0) {
-        hipLaunchKernelGGL(redact_regions_kernel, dim3(sp_ceil_div(rows, RDC_NT)), dim3(RDC_NT), 0, s, st, joints, rows, image, kps, box, keep,
+        hipLaunchKernelGGL(redact_regions_kernel, dim3(sp_ceil_div(rows, SP_TILE_NT)), dim3(SP_TILE_NT), 0, s, st, joints, rows, image, kps, box, keep,
                            keep_count, seg, recs);
-        const int rc = sp_check_launch("redact_regions_kernel");
+        rc = sp_check_launch("redact_regions_kernel");
         if (rc != SP_OK) return rc;
     }
-    if (w % 4 == 0 && aligned_to(src, 4) && aligned_to(dst, 4))
+    if (sp_frame_wide(w, src, dst))
         launch_tiles<true>(s, src, dst, h, w, recs, rows, st);
     else
         launch_tiles<false>(s, src, dst, h, w, recs, rows, st);

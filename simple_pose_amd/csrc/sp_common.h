@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdarg.h>
+#include <stdint.h>
 #include <stdio.h>
 
 #include "simple_pose_hip.h"
@@ -28,6 +29,19 @@ void sp_name_query_set(const char* fmt, ...);
     } while (0)
 
 static inline int sp_ceil_div(long long a, long long b) { return (int)((a + b - 1) / b); }
+
+// ---- limits every entry point that takes a frame's buffers shares ---------------------------------
+constexpr int SP_MAX_ROWS = 2048;                // rows of one frame: the OKS-NMS group limit
+constexpr int SP_MAX_JOINTS = 64;
+constexpr int SP_MAX_DIM = 16384;                // image height and width
+
+// ---- pointer checks of the host entry points -------------------------------------------------------
+static inline bool sp_ranges_overlap(const void* a, const void* b, unsigned long long bytes) {
+    const unsigned long long x = (unsigned long long)(uintptr_t)a, y = (unsigned long long)(uintptr_t)b;
+    return x < y + bytes && y < x + bytes;
+}
+
+static inline bool sp_aligned_to(const void* p, unsigned n) { return ((uintptr_t)p & (n - 1)) == 0; }
 
 // ---- launch helpers (the ONE place these two rules live; every launcher goes through them) -------
 // CUs of the current device, cached per device index; 256 (the MI355X) when the query fails or the index is outside the cache.

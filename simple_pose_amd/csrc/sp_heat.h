@@ -106,13 +106,11 @@ SP_RENDER_HD void sp_heat_box(const float* trans_inv, const int64_t* c, int hm_h
     r.x0 = x0; r.y0 = y0; r.x1 = x1; r.y1 = y1;
 }
 
-// The row of person slot p of the image, or -1: slots >= n (the clamped count) and rows outside the frame are dead.
+// The row of person slot p of the image (pick position p: the order does not matter here), or -1: sp_render_kept_row, which clamps the
+// count as sp_render_live(..) does and refuses rows outside the frame.
 SP_RENDER_HD int sp_heat_row_at(const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int image, int rows, int p) {
-    int lo;
-    const int n = sp_render_live(keep_count, seg, image, rows, lo);
-    if (p >= n) return -1;
-    const int row = keep[lo + p];
-    return (row < 0 || row >= rows) ? -1 : row;
+    int pick;
+    return sp_render_kept_row(keep, keep_count, seg, image, rows, p, false, &pick);
 }
 
 // The record of a live slot (the caller found its row and a joint to draw); empty when the forward map is refused.

@@ -74,22 +74,14 @@ SP_RENDER_HD void sp_label_place(sp_label_rec* r, int x0, int y0, int h, int w) 
     }
 }
 
-SP_RENDER_HD uint32_t sp_label_palette(const sp_label_style& st, int i) {
-    const unsigned char* c = st.palette[i % st.palette_n];
-    return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
-}
-
 // Record p of the image: the label of the pose at pick position n - 1 - p, empty for p >= n (and for a row outside the frame).
 SP_RENDER_HD void sp_label_person(const sp_label_style& st, int h, int w, int rows, int image, const float* box, const double* score,
                                   const int32_t* track_id, const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int p,
                                   sp_label_rec* r) {
     sp_label_clear(r);
-    int lo;
-    const int n = sp_render_live(keep_count, seg, image, rows, lo);
-    if (p >= n) return;
-    const int pick = n - 1 - p;
-    const int row = keep[lo + pick];
-    if (row < 0 || row >= rows) return;
+    int pick;
+    const int row = sp_render_kept_row(keep, keep_count, seg, image, rows, p, true, &pick);
+    if (row < 0) return;
     const float* b = box + (size_t)row * 5;
     int32_t qx, qy;
     if (!(sp_render_q((double)b[0], qx) && sp_render_q((double)b[1], qy))) return;
@@ -101,7 +93,7 @@ SP_RENDER_HD void sp_label_person(const sp_label_style& st, int h, int w, int ro
         else if (c == SP_LABEL_FIELD_CONF) sp_label_put_number(r, SP_LABEL_MAX_CHARS, (double)b[4]);
         else sp_label_put(r, SP_LABEL_MAX_CHARS, sp_label_printable(c) ? c : '?');
     }
-    r->plate = sp_label_palette(st, id > 0 ? (id - 1) % st.palette_n : pick % st.palette_n);
+    r->plate = sp_render_palette(st.palette, st.palette_n, id > 0 ? (id - 1) % st.palette_n : pick % st.palette_n);
     const int lum = 29 * (int)(r->plate & 255u) + 150 * (int)((r->plate >> 8) & 255u) + 77 * (int)((r->plate >> 16) & 255u);
     r->text = lum >= 32768 ? 0u : 0xFFFFFFu;
     r->alpha = 16 * st.label_opacity;

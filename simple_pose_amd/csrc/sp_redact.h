@@ -93,11 +93,9 @@ SP_RENDER_HD sp_redact_rec sp_redact_person_region(const sp_redact_style& st, co
 // outside the frame, are empty.
 SP_RENDER_HD sp_redact_rec sp_redact_region_at(const sp_redact_style& st, int joints, int rows, int image, const double* kps, const float* box,
                                                const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int p) {
-    int lo;
-    const int n = sp_render_live(keep_count, seg, image, rows, lo);
-    if (p >= n) return sp_redact_empty();
-    const int row = keep[lo + p];
-    if (row < 0 || row >= rows) return sp_redact_empty();
+    int pick;                                    // (sp_render_kept_row: the count as sp_render_live(..) clamps it, and the row check)
+    const int row = sp_render_kept_row(keep, keep_count, seg, image, rows, p, false, &pick);
+    if (row < 0) return sp_redact_empty();
     return sp_redact_person_region(st, kps + (size_t)row * joints * 3, box + (size_t)row * 5);
 }
 

@@ -59,8 +59,9 @@ SP_RENDER_HD sp_render_prim sp_render_capsule(double ax, double ay, double bx, d
     return p;
 }
 
-SP_RENDER_HD uint32_t sp_render_palette(const sp_render_style& st, int i) {
-    const unsigned char* c = st.palette[i % st.palette_n];
+// entry i (cyclic) of a style's palette of n BGR triples, as B | G << 8 | R << 16
+SP_RENDER_HD uint32_t sp_render_palette(const unsigned char (*palette)[3], int n, int i) {
+    const unsigned char* c = palette[i % n];
     return (uint32_t)c[0] | (uint32_t)c[1] << 8 | (uint32_t)c[2] << 16;
 }
 
@@ -68,7 +69,7 @@ SP_RENDER_HD uint32_t sp_render_palette(const sp_render_style& st, int i) {
 // kps: the person's [joints, 3] (x, y, c); box: its (x1, y1, x2, y2, ..); pick: its position in the pick order; track_id: 0 when there is none.
 SP_RENDER_HD sp_render_prim sp_render_person_prim(const sp_render_style& st, int joints, int slot, const double* kps, const float* box, int pick,
                                                   int track_id) {
-    const uint32_t person = sp_render_palette(st, track_id > 0 ? (track_id - 1) % st.palette_n : pick % st.palette_n);
+    const uint32_t person = sp_render_palette(st.palette, st.palette_n, track_id > 0 ? (track_id - 1) % st.palette_n : pick % st.palette_n);
     const bool by_part = st.colour_by == SP_RENDER_COLOUR_PART;
     if (slot < SP_RENDER_BOX_SLOTS) {
         if (st.box_r == 0) return sp_render_empty();
@@ -85,12 +86,12 @@ SP_RENDER_HD sp_render_prim sp_render_person_prim(const sp_render_style& st, int
         const double* a = kps + 3 * st.edge[slot][0];
         const double* b = kps + 3 * st.edge[slot][1];
         if (!(a[2] > st.in_vis_thre && b[2] > st.in_vis_thre)) return sp_render_empty();      // (a NaN c is not visible)
-        return sp_render_capsule(a[0], a[1], b[0], b[1], st.limb_r, by_part ? sp_render_palette(st, slot) : person);
+        return sp_render_capsule(a[0], a[1], b[0], b[1], st.limb_r, by_part ? sp_render_palette(st.palette, st.palette_n, slot) : person);
     }
     slot -= st.edges;
     const double* a = kps + 3 * slot;
     if (!(a[2] > st.in_vis_thre)) return sp_render_empty();
-    return sp_render_capsule(a[0], a[1], a[0], a[1], st.joint_r, by_part ? sp_render_palette(st, slot) : person);
+    return sp_render_capsule(a[0], a[1], a[0], a[1], st.joint_r, by_part ? sp_render_palette(st.palette, st.palette_n, slot) : person);
 }
 
 // the image's kept persons: n (clamped to the rows and to the keep list's end, as track.hip's frame_poses) and the offset of its keep list
@@ -103,6 +104,18 @@ SP_RENDER_HD int sp_render_live(const int32_t* keep_count, const int32_t* seg, i
     return n > rows - lo ? rows - lo : n;
 }
 
+// The row of person slot `slot` of the image, or -1: slots >= n (the clamped count) and rows outside the frame are dead.  `pick`: the
+// slot's position in the pick order, counted from the list's start or (from_end) from its end, n - 1 - slot.
+SP_RENDER_HD int sp_render_kept_row(const int32_t* keep, const int32_t* keep_count, const int32_t* seg, int image, int rows, int slot,
+                                    bool from_end, int* pick) {
+    int lo;
+    const int n = sp_render_live(keep_count, seg, image, rows, lo);
+    if (slot >= n) return -1;
+    *pick = from_end ? n - 1 - slot : slot;
+    const int row = keep[lo + *pick];
+    return (row < 0 || row >= rows) ? -1 : row;
+}
+
 // Primitive `index` = p * slots + slot of the image.  Person slot p < n holds the pose at pick position n - 1 - p: applying the primitives
 // by ascending index paints the persons in reverse pick order, the best pose last.  Person slots >= n (and rows outside the frame) are empty.
 SP_RENDER_HD sp_render_prim sp_render_prim_at(const sp_render_style& st, int joints, int rows, int image, const double* kps, const float* box,
@@ -110,12 +123,9 @@ SP_RENDER_HD sp_render_prim sp_render_prim_at(const sp_render_style& st, int joi
                                               int index) {
     const int per = sp_render_slots(st, joints);
     const int p = index / per, slot = index - p * per;
-    int lo;
-    const int n = sp_render_live(keep_count, seg, image, rows, lo);
-    if (p >= n) return sp_render_empty();
-    const int pick = n - 1 - p;
-    const int row = keep[lo + pick];
-    if (row < 0 || row >= rows) return sp_render_empty();
+    int pick;
+    const int row = sp_render_kept_row(keep, keep_count, seg, image, rows, p, true, &pick);
+    if (row < 0) return sp_render_empty();
     return sp_render_person_prim(st, joints, slot, kps + (size_t)row * joints * 3, box + (size_t)row * 5, pick, track_id ? track_id[row] : 0);
 }
 

@@ -14,7 +14,7 @@
 namespace {
 
 constexpr int PLAN_NT = 256;
-constexpr int PLAN_MAX_CAPACITY = 2048;          // the OKS-NMS group limit (nms.hip NMS_MAX_GROUP)
+constexpr int PLAN_MAX_CAPACITY = SP_MAX_ROWS;   // the OKS-NMS group limit (nms.hip NMS_MAX_GROUP)
 
 struct PlanGeom {
     float ar;                                    // in_w / in_h as the float32 a weak Python float becomes next to a float32 operand

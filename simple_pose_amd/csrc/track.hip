@@ -325,7 +325,7 @@ static int track_associate(const char* who, const double* kps, const double* are
     SP_REQUIRE(slots >= 1 && slots <= TRK_MAX_SLOTS, "%s: slots %d (1..%d)", who, slots, TRK_MAX_SLOTS);
     SP_REQUIRE(joints >= 1 && joints <= NMS_MAX_JOINTS, "%s: joints %d (1..%d)", who, joints, NMS_MAX_JOINTS);
     SP_REQUIRE(sigmas_host || joints == 17, "%s: the default sigmas are COCO's 17; pass sigmas for %d joints", who, joints);
-    SP_REQUIRE(rows >= 1 && rows <= 2048, "%s: rows %d (1..2048, the OKS-NMS group limit)", who, rows);
+    SP_REQUIRE(rows >= 1 && rows <= SP_MAX_ROWS, "%s: rows %d (1..%d, the OKS-NMS group limit)", who, rows, SP_MAX_ROWS);
     SP_REQUIRE(max_age >= 0, "%s: max_age %d", who, max_age);
     NmsVar var;
     sp_oks_fill_var(var, sigmas_host, joints);

@@ -39,6 +39,7 @@ kept person's trans_inv and blended in through a colour table."""
 from __future__ import annotations
 
 import ctypes
+from types import SimpleNamespace
 
 import numpy as np
 import torch
@@ -124,6 +125,60 @@ def _image_and_out(img, out):
     return img, out
 
 
+def _joint_indices(values, least: int, most, message: str, pairs: bool = False) -> list:
+    """`values` (with `pairs`: pairs of them, returned flat) as a list of `least` .. `most` (None: any number of) joint indices in 0..63;
+    anything else: ValueError(message)."""
+    try:
+        flat = [v for a, b in values for v in (a, b)] if pairs else list(values)
+        ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in flat)
+        out = [int(v) for v in flat] if ok else []
+    except (TypeError, ValueError):
+        out, ok = [], False
+    if not ok or len(out) < least or (most is not None and len(out) > most) or any(v < 0 or v >= 64 for v in out):
+        raise ValueError(message)
+    return out
+
+
+def _workspace(entry: str, least: int, device, *shape) -> torch.Tensor:
+    """What the library's `entry`(*shape, &bytes) asks for as a zeroed uint8 tensor, of at least `least` bytes (so that it has a pointer)."""
+    n = ctypes.c_int64()
+    _lib.check(getattr(_lib.lib(), entry)(*shape, ctypes.byref(n)), entry)
+    return torch.zeros((max(int(n.value), least),), dtype=torch.uint8, device=device)
+
+
+def _copy_through(img, out):
+    """Nothing is kept, so nothing is drawn: `out` holds the image."""
+    if out.data_ptr() != img.data_ptr():
+        out.copy_(img)
+    return out
+
+
+def _host_frame(img, out, result, image):
+    """A PoseResult that is on the host as the frame's buffers of one image at index `image`, whose keep list is rows 0 .. n.  Checks the
+    index, the images (`_image_and_out`) and, with n > 0, the key points and boxes; returns img, out, image, n, J, `up` (numpy -> the image's
+    device), the host arrays counts and segs and, with n > 0 (nothing is uploaded without), kps, box, keep, keep_count and seg on the device."""
+    if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
+        raise ValueError(f"image: an image index in 0..4095, got {image!r}")
+    image = int(image)
+    img, out = _image_and_out(img, out)
+    kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
+    n = int(kps.shape[0])
+    J = int(kps.shape[1]) if kps.ndim == 3 else 0
+    up = lambda a: torch.from_numpy(a).to(img.device)
+    counts, segs = np.zeros(image + 1, np.int32), np.zeros(image + 2, np.int32)
+    counts[image], segs[image + 1:] = n, n
+    f = SimpleNamespace(img=img, out=out, image=image, n=n, J=J, up=up, counts=counts, segs=segs)
+    if n == 0:
+        return f
+    if kps.ndim != 3 or kps.shape[2] != 3 or not (1 <= J <= 64):
+        raise ValueError(f"result.keypoints: expected [n, J <= 64, 3], got {tuple(kps.shape)}")
+    box = np.ascontiguousarray(result.box, dtype=np.float32)
+    if box.shape != (n, 5):
+        raise ValueError(f"result.box: expected [{n}, 5], got {tuple(box.shape)}")
+    f.kps, f.box, f.keep, f.keep_count, f.seg = up(kps), up(box), up(np.arange(n, dtype=np.int32)), up(counts), up(segs)
+    return f
+
+
 class PoseRenderer(object):
     """`skeleton`: the limbs as pairs of joint indices (at most 64; default COCO's 19).  `joint_radius`, `limb_width`, `box_width`: pixels
     (radius 0 .. 64, widths 0 .. 128), quantised to 1/16 px (a limb or box edge is a capsule of half the width); `box_width=0` draws no
@@ -140,13 +195,9 @@ class PoseRenderer(object):
     def __init__(self, skeleton=COCO_SKELETON, joint_radius: float = 3.0, limb_width: float = 2.0, box_width: float = 1.0, opacity: float = 1.0,
                  in_vis_thre: float = 0.2, colour_by: str = "person", palette=None, label=None, label_scale: int = 2,
                  label_opacity: float = 1.0, caption=None, caption_scale: int = 2, caption_corner: str = "tl", caption_opacity: float = 0.75):
-        try:
-            sk = [(int(a), int(b)) for a, b in skeleton]
-            ok = all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for e in skeleton for v in e)
-        except (TypeError, ValueError):
-            sk, ok = [], False
-        if not ok or len(sk) > _lib.SP_RENDER_MAX_EDGES or any(v < 0 or v >= 64 for e in sk for v in e):
-            raise ValueError(f"skeleton: expected at most {_lib.SP_RENDER_MAX_EDGES} pairs of joint indices in 0..63, got {skeleton!r}")
+        ends = _joint_indices(skeleton, 0, 2 * _lib.SP_RENDER_MAX_EDGES,
+                              f"skeleton: expected at most {_lib.SP_RENDER_MAX_EDGES} pairs of joint indices in 0..63, got {skeleton!r}", pairs=True)
+        sk = list(zip(ends[0::2], ends[1::2]))
         jr = _number("joint_radius", joint_radius, 0.0, MAX_RADIUS_PX, f"a radius in 0..{MAX_RADIUS_PX:g} px")
         lw = _number("limb_width", limb_width, 0.0, 2 * MAX_RADIUS_PX, f"a width in 0..{2 * MAX_RADIUS_PX:g} px")
         bw = _number("box_width", box_width, 0.0, 2 * MAX_RADIUS_PX, f"a width in 0..{2 * MAX_RADIUS_PX:g} px (0: no boxes)")
@@ -244,16 +295,12 @@ class PoseRenderer(object):
     @staticmethod
     def workspace(rows: int, joints: int, device) -> torch.Tensor:
         """The primitive array of `rows` person slots, sized for any skeleton (64 limbs)."""
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().sp_render_workspace_bytes(rows, joints, _lib.SP_RENDER_MAX_EDGES, ctypes.byref(n)), "sp_render_workspace_bytes")
-        return torch.zeros((max(int(n.value), 8),), dtype=torch.uint8, device=device)
+        return _workspace("sp_render_workspace_bytes", 8, device, rows, joints, _lib.SP_RENDER_MAX_EDGES)
 
     @staticmethod
     def label_workspace(rows: int, device) -> torch.Tensor:
         """The record array of `rows` person slots and the caption."""
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().sp_render_labels_workspace_bytes(rows, ctypes.byref(n)), "sp_render_labels_workspace_bytes")
-        return torch.zeros((int(n.value),), dtype=torch.uint8, device=device)
+        return _workspace("sp_render_labels_workspace_bytes", 0, device, rows)
 
     def launch(self, src, dst, kps, box, track_id, keep, keep_count, seg, image: int, rows: int, joints: int, workspace, score=None,
                caption=None, label_workspace=None) -> None:
@@ -286,47 +333,29 @@ class PoseRenderer(object):
         CUDA uint8 [H, W, 3]: `out` when given (contiguous; it may be `img` itself when that is a contiguous CUDA tensor, drawn in
         place), a new tensor otherwise.  A non-contiguous `img` is copied first, so it cannot also be `out`.  Labels take `result.score`
         and `result.track_id`; `image`: the index {image} prints and, with a list of captions, the one that is drawn."""
-        if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
-            raise ValueError(f"image: an image index in 0..4095, got {image!r}")
-        image = int(image)
-        img, out = _image_and_out(img, out)
-        kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
-        n = int(kps.shape[0])
-        J = int(kps.shape[1]) if kps.ndim == 3 else 0
-        dev = img.device
-        up = lambda a: torch.from_numpy(a).to(dev)
+        f = _host_frame(img, out, result, image)
+        dev, n = f.img.device, f.n
         cap = None
         if self._caption is not None:
             cb = self._caption_bytes
-            if isinstance(cb, list) and image >= len(cb):
-                raise ValueError(f"caption: a list of {len(cb)} strings has none for image {image}")
-            cap = up(self.caption_rows(len(cb) if isinstance(cb, list) else image + 1))
-        # the frame's bookkeeping for one image at index `image`: its keep list is rows 0 .. n
-        counts, segs = np.zeros(image + 1, np.int32), np.zeros(image + 2, np.int32)
-        counts[image], segs[image + 1:] = n, n
+            if isinstance(cb, list) and f.image >= len(cb):
+                raise ValueError(f"caption: a list of {len(cb)} strings has none for image {f.image}")
+            cap = f.up(self.caption_rows(len(cb) if isinstance(cb, list) else f.image + 1))
         if n == 0:
-            if out.data_ptr() != img.data_ptr():
-                out.copy_(img)
+            _copy_through(f.img, f.out)
             if cap is not None:
                 with torch.cuda.device(dev):
-                    self.launch_labels(out, None, None, None, None, up(counts), up(segs), image, 0, cap, self.label_workspace(0, dev))
-            return out
-        if kps.ndim != 3 or kps.shape[2] != 3 or not (1 <= J <= 64):
-            raise ValueError(f"result.keypoints: expected [n, J <= 64, 3], got {tuple(kps.shape)}")
-        box = np.ascontiguousarray(result.box, dtype=np.float32)
-        if box.shape != (n, 5):
-            raise ValueError(f"result.box: expected [{n}, 5], got {tuple(box.shape)}")
-        tid = None if result.track_id is None else up(np.ascontiguousarray(result.track_id, dtype=np.int32).reshape(n))
-        d_kps, d_box = up(kps), up(box)
-        keep, keep_count, seg = up(np.arange(n, dtype=np.int32)), up(counts), up(segs)
-        ws = self.workspace(n, J, dev)
+                    self.launch_labels(f.out, None, None, None, None, f.up(f.counts), f.up(f.segs), f.image, 0, cap, self.label_workspace(0, dev))
+            return f.out
+        tid = None if result.track_id is None else f.up(np.ascontiguousarray(result.track_id, dtype=np.int32).reshape(n))
         score = lws = None
         if self.has_text:
-            score = up(np.ascontiguousarray(result.score, dtype=np.float64).reshape(n))
+            score = f.up(np.ascontiguousarray(result.score, dtype=np.float64).reshape(n))
             lws = self.label_workspace(n, dev)
         with torch.cuda.device(dev):
-            self.launch(img, out, d_kps, d_box, tid, keep, keep_count, seg, image, n, J, ws, score=score, caption=cap, label_workspace=lws)
-        return out
+            self.launch(f.img, f.out, f.kps, f.box, tid, f.keep, f.keep_count, f.seg, f.image, n, f.J, self.workspace(n, f.J, dev), score=score,
+                        caption=cap, label_workspace=lws)
+        return f.out
 
 
 class Redactor(object):
@@ -349,13 +378,8 @@ class Redactor(object):
         ex = _number("expand", expand, 1.0, 4.0, "a factor in 1..4")
         hm = _number("head_min", head_min, 0.0, 1.0, "a fraction of the box side in 0..1")
         tf = _number("top_frac", top_frac, 0.0, 1.0, "a fraction of the box height in 0..1")
-        try:
-            hj = [int(j) for j in head_joints]
-            ok = all(isinstance(j, (int, np.integer)) and not isinstance(j, bool) for j in head_joints)
-        except (TypeError, ValueError):
-            hj, ok = [], False
-        if not ok or not (1 <= len(hj) <= _lib.SP_REDACT_MAX_HEAD_JOINTS) or any(j < 0 or j >= 64 for j in hj):
-            raise ValueError(f"head_joints: expected 1..{_lib.SP_REDACT_MAX_HEAD_JOINTS} joint indices in 0..63, got {head_joints!r}")
+        hj = _joint_indices(head_joints, 1, _lib.SP_REDACT_MAX_HEAD_JOINTS,
+                            f"head_joints: expected 1..{_lib.SP_REDACT_MAX_HEAD_JOINTS} joint indices in 0..63, got {head_joints!r}")
         if fallback not in _lib.SP_REDACT_FALLBACKS:
             raise ValueError(f"fallback: 'box_top', 'box' or 'none', got {fallback!r}")
         if not isinstance(in_vis_thre, (int, float)) or isinstance(in_vis_thre, bool) or in_vis_thre != in_vis_thre:
@@ -389,9 +413,7 @@ class Redactor(object):
     @staticmethod
     def workspace(rows: int, device) -> torch.Tensor:
         """The region array of `rows` person slots."""
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().sp_redact_workspace_bytes(rows, ctypes.byref(n)), "sp_redact_workspace_bytes")
-        return torch.zeros((max(int(n.value), 4),), dtype=torch.uint8, device=device)
+        return _workspace("sp_redact_workspace_bytes", 4, device, rows)
 
     def launch(self, src, dst, kps, box, keep, keep_count, seg, image: int, rows: int, joints: int, workspace) -> None:
         """sp_redact_u8c3 on the current stream of src's device; every argument a CUDA tensor.  `dst` may be `src` (in place)."""
@@ -404,29 +426,12 @@ class Redactor(object):
         """`img`: uint8 BGR [H, W, 3], numpy or CUDA; `result`: a PoseResult (its `keypoints`, never `keypoints_smooth`, and its `box`).
         Returns a CUDA uint8 [H, W, 3]: `out` when given (contiguous; it may be `img` itself when that is a contiguous CUDA tensor,
         redacted in place), a new tensor otherwise.  `image`: the index the rows are filed under (any index gives the same pixels)."""
-        if not isinstance(image, (int, np.integer)) or isinstance(image, bool) or not (0 <= image < 4096):
-            raise ValueError(f"image: an image index in 0..4095, got {image!r}")
-        image = int(image)
-        img, out = _image_and_out(img, out)
-        kps = np.ascontiguousarray(result.keypoints, dtype=np.float64)
-        n = int(kps.shape[0])
-        if n == 0:
-            if out.data_ptr() != img.data_ptr():
-                out.copy_(img)
-            return out
-        J = int(kps.shape[1]) if kps.ndim == 3 else 0
-        if kps.ndim != 3 or kps.shape[2] != 3 or not (1 <= J <= 64):
-            raise ValueError(f"result.keypoints: expected [n, J <= 64, 3], got {tuple(kps.shape)}")
-        box = np.ascontiguousarray(result.box, dtype=np.float32)
-        if box.shape != (n, 5):
-            raise ValueError(f"result.box: expected [{n}, 5], got {tuple(box.shape)}")
-        dev = img.device
-        up = lambda a: torch.from_numpy(a).to(dev)
-        counts, segs = np.zeros(image + 1, np.int32), np.zeros(image + 2, np.int32)
-        counts[image], segs[image + 1:] = n, n
-        with torch.cuda.device(dev):
-            self.launch(img, out, up(kps), up(box), up(np.arange(n, dtype=np.int32)), up(counts), up(segs), image, n, J, self.workspace(n, dev))
-        return out
+        f = _host_frame(img, out, result, image)
+        if f.n == 0:
+            return _copy_through(f.img, f.out)
+        with torch.cuda.device(f.img.device):
+            self.launch(f.img, f.out, f.kps, f.box, f.keep, f.keep_count, f.seg, f.image, f.n, f.J, self.workspace(f.n, f.img.device))
+        return f.out
 
 
 def _colormap(name: str) -> np.ndarray:
@@ -486,13 +491,7 @@ class HeatOverlay(object):
         if joints is None:
             mask, js = (1 << 64) - 1, None
         else:
-            try:
-                js = [int(j) for j in joints]
-                ok = all(isinstance(j, (int, np.integer)) and not isinstance(j, bool) for j in joints)
-            except (TypeError, ValueError):
-                js, ok = [], False
-            if not ok or len(js) == 0 or any(j < 0 or j >= 64 for j in js):
-                raise ValueError(f"joints: None (every joint) or a non-empty list of joint indices in 0..63, got {joints!r}")
+            js = _joint_indices(joints, 1, None, f"joints: None (every joint) or a non-empty list of joint indices in 0..63, got {joints!r}")
             mask = 0
             for j in js:
                 mask |= 1 << j
@@ -525,9 +524,7 @@ class HeatOverlay(object):
     @staticmethod
     def workspace(rows: int, hm_h: int, hm_w: int, device) -> torch.Tensor:
         """The records and the u8 planes of `rows` person slots with hm_h x hm_w maps."""
-        n = ctypes.c_int64()
-        _lib.check(_lib.lib().sp_heat_overlay_workspace_bytes(rows, hm_h, hm_w, ctypes.byref(n)), "sp_heat_overlay_workspace_bytes")
-        return torch.zeros((max(int(n.value), 8),), dtype=torch.uint8, device=device)
+        return _workspace("sp_heat_overlay_workspace_bytes", 8, device, rows, hm_h, hm_w)
 
     def launch(self, src, dst, hm, trans_inv, keep, keep_count, seg, image: int, rows: int, workspace) -> None:
         """sp_heat_overlay_u8c3 on the current stream of src's device; every argument a CUDA tensor (hm: contiguous fp32 [>= rows, J, h, w]).
@@ -562,9 +559,7 @@ class HeatOverlay(object):
         if tuple(trans_inv.shape) != (n, 2, 3):
             raise ValueError(f"trans_inv: expected [{n}, 2, 3], got {tuple(trans_inv.shape)}")
         if n == 0:
-            if out.data_ptr() != img.data_ptr():
-                out.copy_(img)
-            return out
+            return _copy_through(img, out)
         dev = img.device
         keep = torch.arange(n, dtype=torch.int32, device=dev)
         keep_count = torch.full((1,), n, dtype=torch.int32, device=dev)

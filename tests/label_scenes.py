@@ -7,6 +7,8 @@ import numpy as np
 from tests import label_ref
 
 CHUNK = 256                    # labels.hip's scan step
+LIST = 512                     # labels.hip's LBL_LIST: record indices a tile collects before it applies them
+TILE_W, TILE_H = 64, 16
 T_FULL = b"#\x01 \x02 \x03"    # "#{id} {score} {conf}"
 T_SHORT = b"#\x01 \x02"
 
@@ -64,6 +66,16 @@ def crowd(persons=260, seed=5):
     return _frame(_background(h, w, 3), boxes, rng.uniform(0, 1, persons).tolist(), list(range(1, persons + 1)), spare_rows=0, seed=4)
 
 
+def crowd_one_tile(persons=600, seed=13):
+    """128 x 64, `persons` kept rows, the first corner of every box inside the tile x 0 .. 63, y 16 .. 31: a label sits above its corner, so
+    nearly all plates meet that one tile, more than its list holds (`cases` asserts it), and the tile applies its list before the scan ends."""
+    rng = np.random.default_rng(seed)
+    h, w = 64, 128
+    boxes = [(rng.uniform(0, TILE_W - 1), rng.uniform(TILE_H, 2 * TILE_H - 1), w, h, rng.uniform(0, 1)) for _ in range(persons)]
+    assert all(0 <= b[0] < TILE_W and TILE_H <= b[1] < 2 * TILE_H for b in boxes)
+    return _frame(_background(h, w, 12), boxes, rng.uniform(0, 1, persons).tolist(), list(range(1, persons + 1)), spare_rows=0, seed=14)
+
+
 def two_images():
     """Two images' persons in one set of buffers (seg = [0, 2, 5]): image 0 keeps two rows, image 1 keeps three."""
     rng = np.random.default_rng(21)
@@ -115,6 +127,9 @@ def cases():
     add("crowd_count0", big, S(b"\x01"), caption=capn, keep_count=[0])
     add("rows0_caption", big, S(b"\x01"), caption=capn, rows=0)
     add("rows0", big, S(b"\x01"), rows=0, draws=False)
+    add("crowd600_one_tile", crowd_one_tile(600), S(b"\x01", label_opacity=8))           # half opacity: the order of the plates shows
+    most = int(tile_hits(plate_rects(out[-1]), 64, 128).max())
+    assert most > LIST, f"crowd600_one_tile: {most} plates in the fullest tile, the list holds {LIST}"
     two = two_images()
     cap2 = captions([b"first \x05", b"cam \x05: \x04"])
     add("two_images_1", two, S(T_SHORT, caption_corner="bl"), image=1, caption=cap2)
@@ -135,6 +150,35 @@ def reference(case):
         box, score, tid = box[:0], score[:0], None if tid is None else tid[:0]
     cap = None if case["caption"] is None else case["caption"][case["image"]]
     return label_ref.render(sc["img"], case["style"], box, score, tid, n, case["image"], cap)
+
+
+def plate_rects(case):
+    """The plates label_ref pastes for the case, as it places and sizes them: (x0, y0, x1, y1), inclusive, clipped to the image."""
+    h, w = case["scene"]["img"].shape[:2]
+    rects, paste = [], label_ref.paste
+
+    def record(img, text, s, x0, y0, *colours):
+        if text:
+            ph, pw = label_ref.plate_bitmap(text, s).shape
+            r = (max(x0, 0), max(y0, 0), min(x0 + pw, w) - 1, min(y0 + ph, h) - 1)
+            if r[0] <= r[2] and r[1] <= r[3]:
+                rects.append(r)
+        paste(img, text, s, x0, y0, *colours)
+
+    label_ref.paste = record
+    try:
+        reference(case)
+    finally:
+        label_ref.paste = paste
+    return rects
+
+
+def tile_hits(rects, h, w):
+    """int [tiles down, tiles across]: how many of the rectangles meet each 64 x 16 tile."""
+    hits = np.zeros(((h + TILE_H - 1) // TILE_H, (w + TILE_W - 1) // TILE_W), np.int64)
+    for x0, y0, x1, y1 in rects:
+        hits[y0 // TILE_H:y1 // TILE_H + 1, x0 // TILE_W:x1 // TILE_W + 1] += 1
+    return hits
 
 
 def style_struct(style):
